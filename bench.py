@@ -8,9 +8,15 @@ Workload at N=1: BASELINE.json configs[1]  (batch 64, T=128, vdim 1024, L=20, C=
 layers).  N>1: one process per GPU (torch.distributed, RCCL), weak scaling (64 clips per GPU), gradients averaged
 with one flat all-reduce per step.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value (clips/s), unit, higher_is_better, dtype, ms_per_step and the run's config.
+A plain run sets up, warms up, times --steps steps and prints the line; nothing else.  --full adds the legs measured after the
+timed region, each reported in the same line:
   roofline     - dominant kernel (by total time), every launch timed by its own dispatch events (hual_prof_*)
   cpu_baseline - the CPU oracle (oracle/seqpan_ref.py, "port") timed on this host on a bounded sample
+  other_feature_dtype, forward_only, host_fed, epoch_loop, epoch_loop_anet, rccl (data parallel)
+--dump-outputs DIR: after the timed steps, the timed path (the same step graph) runs once more from the seeded starting state and
+what it computed (losses, logits, match scores, spans, updated parameters) goes to DIR/<name>.npy, before any leg runs.  Its inputs
+depend on the arguments only, so two builds can be compared output for output (dump_outputs says why not the trajectory's end).
 """
 import argparse
 import ctypes
@@ -114,6 +120,42 @@ def synth_batch(B, T, L, C, vdim, num_words, num_chars, seed):
     y1, y2, m, i = data.make_labels(s, e, lens, max_len=T)
     return dict(video=video, lens=lens, word_ids=word_ids, char_ids=char_ids, y1=y1, y2=y2, match=m,
                 inner=i.astype(np.float32), s_ind=s, e_ind=e)
+
+
+def dump_outputs(out_dir, trainer, model, start, lr, drop, write=True):
+    """--dump-outputs: one more step of the timed path (trainer.step: the captured step graph) from `start`, the seeded state the
+    timed run began in (parameters, zero Adam slots, dropout stream), and what a caller receives from it - the fetches of the
+    reference's sess.run([train_op, loss, start_index, end_index]), the heads' logits and the parameters train_op leaves behind
+    (1.2 M floats at the default shape: about 5 MB in all).  Rank 0's shard when data parallel; every rank steps (collectives).
+    Why not the end of the timed trajectory: parameter gradients are summed with float atomics (last-bit differences from run to
+    run) and Adam turns those of near-zero gradients into whole-size updates, so two runs of one build end
+    hundreds of steps later with logits whole units apart.  From the seeded state the forward outputs are bit-reproducible and
+    the updated parameters agree to rounding (a gradient whose sign is rounding noise could move its weight by one Adam step,
+    ~3 x lr).  The trained state is put back afterwards: the --full legs see what they saw before."""
+    state = (model.params, model.adam_m, model.adam_v, model.rng_state)
+    trained = [t.clone() for t in state]
+    for t, s in zip(state, start):
+        t.copy_(s)
+    trainer.step(lr=lr, drop_rate=drop)
+    torch.cuda.synchronize()
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    arrays = dict(loss=np.array([float(trainer.last_loss())], dtype=np.float64),
+                  loss_terms=f32(trainer.loss_terms),
+                  start_logits=f32(trainer.start_logits), end_logits=f32(trainer.end_logits),
+                  match_scores=f32(trainer.match_scores),
+                  start_index=trainer.start_index.detach().cpu().numpy().astype(np.float64),
+                  end_index=trainer.end_index.detach().cpu().numpy().astype(np.float64),
+                  params=f32(model.params))
+    for t, s in zip(state, trained):
+        t.copy_(s)
+    model.global_step -= 1
+    torch.cuda.synchronize()
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+        print('[bench] outputs of the timed step from the seeded state written to %s (%s)' % (out_dir, ', '.join(sorted(arrays))),
+              file=sys.stderr, flush=True)
 
 
 def cpu_baseline(seconds_budget=20.0):
@@ -408,9 +450,15 @@ def main():
     ap.add_argument('--vdim', type=int, default=1024)
     ap.add_argument('--drop', type=float, default=0.2)
     ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying a hipGraph')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-epoch-loop', action='store_true', help='skip the epoch-loop leg (varying padded shapes, after the timed region)')
+    ap.add_argument('--full', action='store_true',
+                    help='run the legs after the timed region too (roofline, CPU baseline, other feature dtype, forward only, host fed, '
+                         'epoch loops, all-reduce figures); a plain run times the headline steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, run the timed step once more from the seeded starting state and write its outputs '
+                         '(rank 0) as DIR/<name>.npy, float32 / float64')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and the single-GPU legs after it')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the roofline leg')
+    ap.add_argument('--no-epoch-loop', action='store_true', help='with --full: skip the epoch-loop leg (varying padded shapes, after the timed region)')
     ap.add_argument('--epoch-samples', type=int, default=4096)
     ap.add_argument('--anet-samples', type=int, default=8192, help='queries drawn from the ActivityNet length fixture for the epoch_loop_anet legs')
     ap.add_argument('--prewarm', type=int, default=200, help='untimed steps before the warm-up steps (clock ramp)')
@@ -452,6 +500,8 @@ def main():
     trainer = Trainer(model, world=world, use_graph=not args.no_graph, force_dp=dp)
     vdt = torch.bfloat16 if args.video_dtype == 'bf16' else torch.float32
     trainer.set_batch(b['video'], b['lens'], b['word_ids'], b['char_ids'], b['y1'], b['y2'], b['match'], b['inner'], video_dtype=vdt)
+    # --dump-outputs: the seeded starting state, for the one step after the timed region that is written out (dump_outputs)
+    start = [t.clone() for t in (model.params, model.adam_m, model.adam_v, model.rng_state)] if args.dump_outputs else None
 
     def barrier():
         if dp:
@@ -478,6 +528,8 @@ def main():
         dt = float(t.item())
     loss = float(trainer.last_loss())
     clips = args.batch * world * args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer, model, start, 1e-4, args.drop, write=rank == 0)
 
     # Everything below rides in the same line but is not the measurement: the legs report into `legs` as they finish, and a deadline
     # (HUAL_BENCH_LEG_DEADLINE_S, default 900 s after the timed region) prints the line with what has finished and ends every rank - a
@@ -522,7 +574,7 @@ def main():
     watchdog.start()
 
     rccl = None
-    if dp:
+    if dp and args.full:
         # the step's one collective of size: all-reduce(sum) of the flat fp32 gradient bucket, timed on its own
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(5):
@@ -588,7 +640,7 @@ def main():
     legs['rccl'] = rccl
     roof = None
     print('[bench] timed region done: %.3f ms/step' % (dt / args.steps * 1e3), file=sys.stderr, flush=True)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # roofline leg: same step launched eagerly; every launch carries start/stop events of its own dispatch
         l = lib.load()
         eager = Trainer(model, world=1, use_graph=False)
@@ -723,9 +775,10 @@ def main():
                                  tflops=round(d['flops'] / d['us'] / 1e6, 2) if d['flops'] > 0 else None,
                                  gbs=round(d['bytes'] / d['us'] / 1e3, 1) if d['bytes'] > 0 else None) for d in fam]
     legs['roofline'] = roof
-    print('[bench] roofline leg done', file=sys.stderr, flush=True)
+    if args.full:
+        print('[bench] roofline leg done', file=sys.stderr, flush=True)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
         try:
             cpu['gpu_at_cpu_shape'] = gpu_at_cpu_shape(dev, args.drop)
@@ -735,7 +788,7 @@ def main():
 
     legs['cpu_baseline'] = cpu
     other_feed = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the same step with the clip features held in HBM in the other element type (BASELINE configs[1] says bf16 features;
         # the headline number is measured on the reference's float32 placeholder)
         try:
@@ -757,7 +810,7 @@ def main():
 
     legs['other_feature_dtype'] = other_feed
     fwd_only = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the evaluation fetch set on its own (runner_utils.py:166: start / end index; all five fetches come out of the one pass), eager launches
         try:
             dv = [torch.as_tensor(b[k]).to(dev) for k in ('video', 'lens', 'word_ids', 'char_ids')]
@@ -778,7 +831,7 @@ def main():
 
     legs['forward_only'] = fwd_only
     host_fed = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # The PCIe-inclusive rate (never `value`): the same step fed from HOST batches the way the reference feeds it
         # (runner_utils.py:141-147: a numpy batch per step through feed_dict), as hual_amd/feeder.py pipelines it - batch k + 1 uploads
         # from pinned memory on a copy stream while step k runs.  `pinned`: the producer wrote the batch into the pinned slot itself
@@ -832,7 +885,7 @@ def main():
 
     legs['host_fed'] = host_fed
     epoch_loop, epoch_anet = None, None
-    if not args.no_epoch_loop and (world == 1 or dp):
+    if args.full and not args.no_epoch_loop and (world == 1 or dp):
         # every rank runs these legs when the job is data parallel (collectives inside); rank 0 reports
         def leg(name, **kw):
             try:

@@ -8,7 +8,7 @@ port=$((29300 + RANDOM % 200))
 pids=()
 for r in $(seq 0 $((N - 1))); do
   HUAL_BENCH_ONE_DEVICE=1 HUAL_BENCH_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 WORLD_SIZE=$N RANK=$r LOCAL_RANK=$r MASTER_ADDR=127.0.0.1 MASTER_PORT=$port \
-    timeout -k 10 500 python $R/bench.py --gpus $N --batch 8 --T 32 --L 8 --C 5 --vdim 256 --steps 4 --warmup 1 --prewarm 2 --no-cpu-baseline \
+    timeout -k 10 500 python $R/bench.py --gpus $N --batch 8 --T 32 --L 8 --C 5 --vdim 256 --steps 4 --warmup 1 --prewarm 2 --full --no-cpu-baseline \
     --epoch-samples 256 --anet-samples 512 > $R/gpurun_out/rehearsal_$r.out 2> $R/gpurun_out/rehearsal_$r.err &
   pids+=($!)
 done

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; out=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf $out/prof_eg
-timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace -d $out/prof_eg -o p --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --prewarm 10 --no-cpu-baseline --no-roofline > $out/eg_bench.json 2> $out/eg.err || { tail -5 $out/eg.err; exit 2; }
+timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace -d $out/prof_eg -o p --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --prewarm 10 --full --no-cpu-baseline --no-roofline > $out/eg_bench.json 2> $out/eg.err || { tail -5 $out/eg.err; exit 2; }
 tr=$(ls $out/prof_eg/*/*kernel_trace.csv $out/prof_eg/*kernel_trace.csv 2>/dev/null | head -1)
 python3 - "$tr" <<'PY'
 import csv, sys

@@ -1,7 +1,7 @@
 R=$GRAFT_REPO_ROOT; out=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf $out/prof_ep
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof_ep -o p --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --prewarm 10 --no-cpu-baseline --no-roofline > $out/ep_bench.json 2> $out/ep.err || { tail -5 $out/ep.err; exit 2; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof_ep -o p --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --prewarm 10 --full --no-cpu-baseline --no-roofline > $out/ep_bench.json 2> $out/ep.err || { tail -5 $out/ep.err; exit 2; }
 st=$(ls $out/prof_ep/*/*kernel_stats.csv $out/prof_ep/*kernel_stats.csv 2>/dev/null | head -1)
 python3 - "$st" <<'PY'
 import csv, sys

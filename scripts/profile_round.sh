@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU-box call that produces the round's measurement artefacts under gpurun_out/<tag>_*:
-#   1. plain default bench (incl. the epoch-loop leg)         -> <tag>_bench.json
+#   1. default bench with every leg (--full, incl. the epoch-loop leg) -> <tag>_bench.json
 #   2. rocprofv3 --kernel-trace --stats of the same command without the epoch-loop leg (other shapes, assembly launches: they would
 #      mix into the timeline)                                 -> <tag>_bench_kernel_stats.csv, <tag>_bench_under_rocprof.json,
 #                                                               <tag>_step_timeline.txt
@@ -13,11 +13,11 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out
 mkdir -p $out
 cd $R
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
 echo "[1] bench: $(cut -c1-160 $out/${tag}_bench.json)"
 cd /tmp && export TMPDIR=/tmp
 rm -rf $out/prof_$tag
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/prof_$tag -o p --output-format csv -- python3 $R/bench.py --no-epoch-loop > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err || { tail -5 $out/${tag}_rocprof.err; exit 2; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/prof_$tag -o p --output-format csv -- python3 $R/bench.py --full --no-epoch-loop > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err || { tail -5 $out/${tag}_rocprof.err; exit 2; }
 st=$(ls $out/prof_$tag/*/*kernel_stats.csv $out/prof_$tag/*kernel_stats.csv 2>/dev/null | head -1)
 tr=$(ls $out/prof_$tag/*/*kernel_trace.csv $out/prof_$tag/*kernel_trace.csv 2>/dev/null | head -1)
 cp "$st" $out/${tag}_bench_kernel_stats.csv

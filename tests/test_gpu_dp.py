@@ -119,7 +119,7 @@ def test_bench_multi_rank_path_on_one_rank(tmp_path):
     env = dict(os.environ, HUAL_DP_FORCE_COLLECTIVES='1', WORLD_SIZE='1', RANK='0', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1',
                MASTER_PORT=str(29900 + os.getpid() % 90))
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--batch', '8', '--T', '32', '--L', '8', '--C', '5',
-                        '--vdim', '256', '--steps', '4', '--warmup', '1', '--prewarm', '2', '--no-cpu-baseline', '--no-roofline',
+                        '--vdim', '256', '--steps', '4', '--warmup', '1', '--prewarm', '2', '--full', '--no-cpu-baseline', '--no-roofline',
                         '--epoch-samples', '256', '--anet-samples', '512'],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -148,7 +148,7 @@ def test_bench_line_survives_a_leg_that_does_not_finish():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HUAL_BENCH_LEG_DEADLINE_S='2')
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--batch', '8', '--T', '32', '--L', '8', '--C', '5', '--vdim', '256',
-                        '--steps', '4', '--warmup', '1', '--prewarm', '2'], env=env, capture_output=True, text=True, timeout=600)
+                        '--steps', '4', '--warmup', '1', '--prewarm', '2', '--full'], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1
@@ -172,7 +172,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
         env = dict(os.environ, HUAL_BENCH_ONE_DEVICE='1', HUAL_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0', WORLD_SIZE='2',
                    RANK=str(r), LOCAL_RANK=str(r), MASTER_ADDR='127.0.0.1', MASTER_PORT=port)
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--batch', '8', '--T', '32', '--L', '8',
-                                       '--C', '5', '--vdim', '256', '--steps', '4', '--warmup', '1', '--prewarm', '2', '--no-cpu-baseline',
+                                       '--C', '5', '--vdim', '256', '--steps', '4', '--warmup', '1', '--prewarm', '2', '--full', '--no-cpu-baseline',
                                        '--epoch-samples', '256', '--anet-samples', '512'],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=900) for p in procs]
