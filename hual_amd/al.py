@@ -196,6 +196,26 @@ def iou_metrics(ious):
     return tuple(float(np.mean(a >= t) * 100.0) for t in (0.3, 0.5, 0.7)) + (float(np.mean(a) * 100.0),)
 
 
+def topk_ious(records, starts, ends):
+    """IoU [N,k] (float64 of the float32 values) of every proposal column through ious_of_spans; a -1 slot (no proposal) counts as 0"""
+    n = len(records)
+    st = np.asarray(starts, dtype=np.int64).reshape(n, -1)
+    en = np.asarray(ends, dtype=np.int64).reshape(n, -1)
+    out = np.zeros(st.shape, dtype=np.float64)
+    for c in range(st.shape[1]):
+        pad = (st[:, c] < 0) | (en[:, c] < 0)
+        iou = np.asarray(ious_of_spans(records, np.where(pad, 0, st[:, c]), np.where(pad, 0, en[:, c])), dtype=np.float64)
+        out[:, c] = np.where(pad, 0.0, iou) if n else iou
+    return out
+
+
+def recall_at_k(records, starts, ends, thresholds=(0.3, 0.5, 0.7)):
+    """R@k in percent for each IoU threshold: the share of clips with at least one of its k proposals (starts / ends [N,k] frame
+    indices, -1 = none) at IoU >= threshold.  k = 1 is the R@1 of iou_metrics."""
+    best = topk_ious(records, starts, ends).max(axis=1, initial=0.0)
+    return tuple(float(np.mean(best >= t) * 100.0) for t in thresholds)
+
+
 # ---------------------------------------------------------------- label update -------------------
 def _round_half_even_index(t, duration, vlen):
     """time_to_index_v2 (update_label.py:41-48): python round() of t / duration * (vlen - 1)"""

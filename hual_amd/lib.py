@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HUAL_LIB_PATH: an experiment build of the library (scripts/exp/tl_variant.sh) - the in-tree file is never overwritten
 LIB_PATH = os.environ.get('HUAL_LIB_PATH') or os.path.join(_HERE, 'libhual_seqpan.so')
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lib = None
 
@@ -131,6 +131,7 @@ def load():
                                        vp, f32, i32, vp]
     lib.hual_attention_keep_row_bytes.argtypes = [i32]
     lib.hual_span_argmax.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    lib.hual_span_topk.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]
     lib.hual_linear_dw.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, u64, vp]
     lib.hual_al_score.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
     lib.hual_al_renew.argtypes = [P(hual_al_set), vp, i32, vp, vp, vp, P(ctypes.c_double), vp, vp]
@@ -219,3 +220,30 @@ def linear_dw(A, dY, dW, db=None, workgroups=0):
     scratch = torch.empty(256, dtype=torch.float32, device=A.device)
     check(load().hual_linear_dw(ptr(A), A.stride(0), ptr(dY), dY.stride(0), ptr(dW), dW.stride(0), ptr(db), M, K, N,
                                 workgroups, ptr(scratch), 1024, stream_ptr()))
+
+
+def span_topk(start_logits, end_logits, video_seq_len, k, max_len=0, nms_iou=1.0, out=None):
+    """the k best spans of each clip after greedy temporal NMS (hual_span_topk): start_logits / end_logits f32 [B,T] and
+    video_seq_len [B] on the device -> (start [B,k] int64, end [B,k] int64, score [B,k] float32), enqueued on the current stream.
+    Slots no candidate fills are -1 (score -1.0).  out: three contiguous device tensors of those shapes to write into instead."""
+    import torch
+    if start_logits.dtype != torch.float32 or end_logits.dtype != torch.float32:
+        raise HualError('span_topk: float32 logits required')
+    if start_logits.dim() != 2 or end_logits.shape != start_logits.shape:
+        raise HualError('span_topk: start / end logits must both be [B,T]')
+    s, e = start_logits.contiguous(), end_logits.contiguous()
+    B, T = s.shape
+    vl = video_seq_len.to(device=s.device, dtype=torch.int32).contiguous()
+    if vl.numel() != B:
+        raise HualError('span_topk: video_seq_len must hold B = %d lengths' % B)
+    k = int(k)
+    if out is None:
+        out = (torch.empty(B, k, dtype=torch.int64, device=s.device), torch.empty(B, k, dtype=torch.int64, device=s.device),
+               torch.empty(B, k, dtype=torch.float32, device=s.device))
+    else:
+        for o, dt in zip(out, (torch.int64, torch.int64, torch.float32)):
+            if o.dtype != dt or tuple(o.shape) != (B, k) or not o.is_contiguous():
+                raise HualError('span_topk: out tensors must be contiguous [B,k] int64, int64, float32')
+    check(load().hual_span_topk(ptr(s), ptr(e), ptr(vl), B, T, k, int(max_len), ctypes.c_float(nms_iou), ptr(out[0]), ptr(out[1]),
+                                ptr(out[2]), stream_ptr()))
+    return out

@@ -130,6 +130,60 @@ class Runner:
             ious = hdist.broadcast_object([x for p in parts for x in p] if self.rank == 0 else None)
         return al.iou_metrics(ious)
 
+    # ------------------------------------------------------------------ R@k evaluation (top-k proposals after temporal NMS)
+    def evaluate(self, dataset=None, k=5, nms_iou=0.5, max_len=0, return_proposals=False):
+        """R1 and R<k> at IoU 0.3 / 0.5 / 0.7 and mIoU (percent) of the k best spans per clip after greedy temporal NMS
+        (hual_span_topk).  Batches and ranks as test_epoch; the proposals of all batches collect on the device and come back in one
+        transfer.  R1 and mIoU are those of the first proposal, which is the span test_epoch scores.  return_proposals: also a list
+        with one entry per clip of the dataset, [(start_sec, end_sec, score), ...] best first (data.index_to_time)."""
+        ds = dataset or self.test_set
+        N, bs, k = len(ds), self.batch_size, int(k)
+        mine = [(lo, min(N, lo + bs)) for b, lo in enumerate(range(0, N, bs)) if b % self.world == self.rank]
+        n = sum(hi - lo for lo, hi in mine)
+        dev = self.model.device
+        # one buffer for the three outputs: starts | ends (int64) | scores (float32), each [n,k]
+        buf = torch.empty(n * k * 20, dtype=torch.uint8, device=dev)
+        st = buf[:8 * n * k].view(torch.int64).view(n, k)
+        en = buf[8 * n * k:16 * n * k].view(torch.int64).view(n, k)
+        sc = buf[16 * n * k:].view(torch.float32).view(n, k)
+        pos = 0
+        for lo, hi in mine:
+            sel = np.arange(lo, hi)
+            f = ds.assemble(sel, labels=False, min_chars=4)
+            o = self.model.forward(f['video'], f['video_seq_len'], f['word_ids'], f['char_ids'], drop_rate=0.0)
+            lib.span_topk(o['start_logits'], o['end_logits'], f['video_seq_len'], k, max_len=max_len, nms_iou=nms_iou,
+                          out=(st[pos:pos + hi - lo], en[pos:pos + hi - lo], sc[pos:pos + hi - lo]))
+            pos += hi - lo
+        h = buf.cpu().numpy()
+        ids = np.concatenate([np.arange(lo, hi) for lo, hi in mine]) if mine else np.zeros(0, dtype=np.int64)
+        part = (ids, h[:8 * n * k].view(np.int64).reshape(n, k), h[8 * n * k:16 * n * k].view(np.int64).reshape(n, k),
+                h[16 * n * k:].view(np.float32).reshape(n, k))
+        if self.world > 1:
+            parts = hdist.gather_objects(part)
+            if self.rank == 0:
+                part = tuple(np.concatenate([p[x] for p in parts]) for x in range(4))
+            part = hdist.broadcast_object(part if self.rank == 0 else None)
+        ids, S, E, SC = part
+        recs = [ds.records[i] for i in ids]
+        ious = al.topk_ious(recs, S, E)
+        r1 = al.iou_metrics(ious[:, 0])
+        rk = al.recall_at_k(recs, S, E)
+        res = {'R1@0.3': r1[0], 'R1@0.5': r1[1], 'R1@0.7': r1[2], 'R%d@0.3' % k: rk[0], 'R%d@0.5' % k: rk[1], 'R%d@0.7' % k: rk[2],
+               'mIoU': r1[3]}
+        self.log.info('EVAL (k={}, nms_iou={}):\tR1 {:.2f}\t{:.2f}\t{:.2f}\tR{} {:.2f}\t{:.2f}\t{:.2f}\tmIoU {:.2f}'.format(
+            k, nms_iou, r1[0], r1[1], r1[2], k, rk[0], rk[1], rk[2], r1[3]))
+        if not return_proposals:
+            return res
+        props = [None] * N
+        for row, i in enumerate(ids):
+            r, p = ds.records[i], []
+            for s, e, x in zip(S[row], E[row], SC[row]):
+                if s >= 0:
+                    t0, t1 = data.index_to_time((s, e), r['v_len'], r['duration'])
+                    p.append((float(t0), float(t1), float(x)))
+            props[i] = p
+        return res, props
+
     # ------------------------------------------------------------------ main.py --mode train (:50-78)
     def train(self, epochs=None):
         epochs = int(epochs if epochs is not None else self.configs['train']['epochs'])

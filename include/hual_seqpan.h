@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define HUAL_ABI_VERSION 8
+#define HUAL_ABI_VERSION 9
 
 #define HUAL_OK 0
 #define HUAL_ERR_INVALID (-1)
@@ -339,6 +339,23 @@ int hual_attention_bwd(const float* Q, int ldq, const float* K, const float* V, 
  * over rows of the row maxima, end = argmax over columns of the column maxima, first index on ties.  T <= 256. */
 int hual_span_argmax(const float* start_logits, const float* end_logits, const float* vmask, int64_t* start_index,
                      int64_t* end_index, int B, int T, void* stream);
+
+/* the k best spans of each clip (R@k evaluation, ABI 9): softmax of the masked start / end logits exactly as hual_span_argmax computes
+ * it, candidates p_s[i] * p_e[j] (one fp32 product) for 0 <= i <= j < video_seq_len[b] (and j - i < max_len when max_len > 0), greedy
+ * temporal NMS.  1 <= k <= 16, 1 <= T <= 256, 0 < nms_iou <= 1 (1 = plain top-k of distinct spans), max_len >= 0.
+ *  - order: higher score first; equal scores by the smaller key i * 256 + j (smaller i, then smaller j).
+ *  - NMS on the half-open frame intervals [i, j + 1): inter = max(0, min(j1, j2) + 1 - max(i1, i2)), union = len1 + len2 - inter; a
+ *    candidate is suppressed iff (float)inter >= nms_iou * (float)union (fp32) for any span already selected.
+ *  - outputs [B, k] row major: start_index, end_index (int64), score (float).  Slots beyond the surviving candidates: -1, -1, -1.0f.
+ *    A NaN logit at t < video_seq_len[b] gives the whole row -1 (the poison rule of hual_span_argmax).  video_seq_len[b] > T reads as
+ *    T, < 1 as an empty clip (all -1).  Logits at t >= video_seq_len[b] are not read.
+ *  - slot 0 equals hual_span_argmax whenever the maximal pairs form a product set (equal-probability plateaus included): both then pick
+ *    the smallest start and the smallest end.  They can differ only when two DIFFERENT products round to the same maximal float and
+ *    the smallest start and smallest end among those pairs are not a pair of them: ans_predictor then reports that mixed pair, which
+ *    need not even be a maximal span, and this function the maximal pair with the smallest (i, j).
+ * Allocates nothing and does not synchronise: capturable in a hipGraph.  Argument errors return before any HIP call. */
+int hual_span_topk(const float* start_logits, const float* end_logits, const int32_t* video_seq_len, int B, int T, int k, int max_len,
+                   float nms_iou, int64_t* start_index, int64_t* end_index, float* score, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Device-side batch assembly: TrainLoader.process_batch / TestLoader.process_batch
