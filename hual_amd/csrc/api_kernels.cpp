@@ -16,6 +16,7 @@ using namespace hual;
 extern "C" {
 
 int hual_abi_version(void) { return HUAL_ABI_VERSION; }
+uint64_t hual_cfg_bytes(void) { return sizeof(hual_cfg); }
 const char* hual_last_error(void) { return hual::last_error_cstr(); }
 
 int hual_linear_dw(const float* A, int lda, const float* dY, int ldy, float* dW, int ldw, float* db, int M, int K,

@@ -1,5 +1,6 @@
 // Text-encoder front end: word lookup + char CNN (+ their backward).
-//   word_embs  /root/reference/models/modules.py:8-16   table = [zeros; unk; frozen GloVe]
+//   word_embs  /root/reference/models/modules.py:8-16   table = [zeros; unk; GloVe] (GloVe frozen, or trainable with
+//              hual_cfg.finetune_word_emb: its gradient rides in char_pool_bwd_kernel beside the unk row's)
 //   char_embs  /root/reference/models/modules.py:19-38  lookup ([zeros; char_table]) -> 4 x conv2d VALID
 //              (widths 1..4 -> 10/20/30/40 channels) + bias -> relu -> max over chars (padding not masked)
 // Output row = [word_emb(300) | char features(100)] (model.py:41), consumed by the query_conv1d GEMM.
@@ -66,7 +67,8 @@ __global__ __launch_bounds__(256) void char_pool_kernel(EmbedArgs a, int nrows) 
 
 // ------------------------------------------------------------------------------------------------------
 // backward 1: dYall (in place of Yall): channel gradient at the arg-max start row, zero elsewhere;
-//             the unk row gradient; zero the packed filter-gradient scratch.
+//             the unk row gradient (and, hual_cfg.finetune_word_emb, the word table's: a scatter-add of the same rows by id);
+//             zero the packed filter-gradient scratch.
 __global__ __launch_bounds__(256) void char_pool_bwd_kernel(EmbedArgs a, EmbedGrads gr, DropCfg drop, int nrows, int CP,
                                                             int ntask_pool) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
@@ -85,13 +87,17 @@ __global__ __launch_bounds__(256) void char_pool_bwd_kernel(EmbedArgs a, EmbedGr
   }
   int x = gid - ntask_pool;
   const int ngw = wd >> 2;
-  if (x < nrows * ngw) {             // unk row: d unk += dropout'(dcat[:, :wd]) over the words that ARE unk
-    const int row = x / ngw, c4 = x - row * ngw;
-    if (a.word_ids[row] == 1) {
+  if (x < nrows * ngw) {             // word rows: d unk += dropout'(dcat[:, :wd]) over the words that ARE unk and - a fine-tuned
+    const int row = x / ngw, c4 = x - row * ngw;      // table (gr.dword_table) - d word_table[id - 2] += the same for ids >= 2
+    const int wid = a.word_ids[row];
+    float* dst = nullptr;
+    if (wid == 1) dst = gr.dunk;
+    else if (wid >= 2 && wid - 2 < gr.dword_rows) dst = gr.dword_table + (size_t)(wid - 2) * wd;      // (dword_rows 0: frozen)
+    if (dst) {
       float4 g = ld4(gr.dcat + (size_t)row * gr.lddcat + 4 * c4);
       if (drop.enabled) g = apply_drop4(drop, HUAL_SITE_WORD, (uint32_t)row, (uint32_t)c4, g);
-      atomicAdd(gr.dunk + 4 * c4, g.x); atomicAdd(gr.dunk + 4 * c4 + 1, g.y);
-      atomicAdd(gr.dunk + 4 * c4 + 2, g.z); atomicAdd(gr.dunk + 4 * c4 + 3, g.w);
+      atomicAdd(dst + 4 * c4, g.x); atomicAdd(dst + 4 * c4 + 1, g.y);
+      atomicAdd(dst + 4 * c4 + 2, g.z); atomicAdd(dst + 4 * c4 + 3, g.w);
     }
     return;
   }

@@ -8,7 +8,7 @@ namespace hual {
 struct EmbedArgs {
   const int32_t* word_ids;      // [Nq]
   const int32_t* char_ids;      // [Nq, C]
-  const float* word_table;      // frozen [num_words-2, word_dim]
+  const float* word_table;      // [num_words-2, word_dim]: the frozen GloVe table or the params entry (hual_cfg.finetune_word_emb)
   const float* unk;             // [word_dim]
   const float* char_table;      // [num_chars-1, char_dim]
   const float* filt[4];         // filter_i [k_i, char_dim, ch_i]
@@ -25,6 +25,7 @@ struct EmbedArgs {
 struct EmbedGrads {
   const float* dcat; int lddcat;
   float* dunk; float* dchar_table; float* dfilt[4]; float* dfbias[4];
+  float* dword_table; int dword_rows;      // hual_cfg.finetune_word_emb: d word_table [dword_rows = num_words-2, word_dim]; 0: frozen
 };
 
 }  // namespace hual

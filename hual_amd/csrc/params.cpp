@@ -14,6 +14,8 @@ int validate_cfg(const hual_cfg& c) {
   HUAL_REQUIRE(c.attn_layer >= 1 && c.attn_layer <= HUAL_MAX_ATTN_LAYERS, "attn_layer in [1,8]");
   HUAL_REQUIRE(c.num_chars >= 2 && c.num_words >= 2, "num_chars / num_words too small");
   HUAL_REQUIRE(c.no_gumbel || c.tau > 0.f, "loss.tau must be positive when loss.no_gumbel is false");
+  HUAL_REQUIRE(c.finetune_word_emb == 0 || c.finetune_word_emb == 1, "model.finetune_word_emb must be 0 or 1");
+  HUAL_REQUIRE(!c.finetune_word_emb || c.num_words >= 3, "model.finetune_word_emb needs a word table of at least one row");
   return 0;
 }
 
@@ -139,6 +141,8 @@ int build_param_map(const hual_cfg& c, ParamMap& m) {
   m.ehid = b.dense("predictor/end_hidden", 2 * D, D);
   m.sdense = b.dense("predictor/start_dense", D, 1);
   m.edense = b.dense("predictor/end_dense", D, 1);
+  // modules.py:10-14 with finetune=True: behind every other entry, so that the layout of the frozen model is a prefix of this one
+  m.word_table = c.finetune_word_emb ? b.add("word_embs/word_table", {c.num_words - 2, c.word_dim}) : (size_t)-1;
   m.total = b.cur;
   return 0;
 }

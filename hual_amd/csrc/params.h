@@ -42,6 +42,7 @@ struct ParamMap {
   size_t pool_w; DenseP cqcat; DenseP match; size_t label_emb;
   size_t fe_pos; ConvBlockP fe_cb; LnP fe_ln1, fe_ln2; DenseP fe_q, fe_k, fe_v, fe_dense;
   LnP sln, eln; DenseP shid, ehid, sdense, edense;
+  size_t word_table; // hual_cfg.finetune_word_emb: the trainable GloVe table, the last entry; (size_t)-1 while it is frozen
   size_t total;      // padded flat size in floats (multiple of 4)
   size_t count;      // true number of trainable scalars
   std::vector<ParamEntry> entries;

@@ -260,8 +260,9 @@ int setup_ctx(Ctx& c, const hual_cfg* cfg, int B, int T, int L, int C) {
     }
     std::sort(c.dense.begin(), c.dense.end(), [](const Ctx::DenseW& a, const Ctx::DenseW& b) { return a.off < b.off; });
     // the image of a transposed weight takes ceil(K/128) blocks of 64 KB: it fits the weight's own byte range when K is a
-    // multiple of 128; the others (query_conv1d, K = word_dim + 100) go behind the end of the parameter range
-    size_t extra = pm.total * 4;
+    // multiple of 128; the others (query_conv1d, K = word_dim + 100) go behind the end of the parameter range - of the range the
+    // dense weights live in: a fine-tuned word table (the last entry, never an image source) is left out of the image buffers
+    size_t extra = (pm.word_table != (size_t)-1 ? pm.word_table : pm.total) * 4;
     extra = (extra + 255) & ~(size_t)255;
     for (auto& d : c.dense)
       if (d.K % 128) { d.boff = extra; extra += (size_t)((d.K + 127) / 128) * HUAL_PACK_BLOCK_BYTES; }
@@ -1210,6 +1211,7 @@ int backward_graph(Ctx& c, const hual_batch* bt, const hual_labels* lab, const h
   if (c.live()) {
     fill_embed_args(c, ea, bt, cat, catw, char_arg, embed_scratch);
     eg.dcat = d_cat; eg.lddcat = catw; eg.dunk = c.g(pm.unk); eg.dchar_table = c.g(pm.char_table);
+    if (pm.word_table != (size_t)-1) { eg.dword_table = c.g(pm.word_table); eg.dword_rows = c.cfg->num_words - 2; }      // hual_cfg.finetune_word_emb
     for (int i = 0; i < 4; ++i) { eg.dfilt[i] = c.g(pm.filt[i]); eg.dfbias[i] = c.g(pm.fbias[i]); }
     // (its last step - folding the window gradients into the char table's - rides in the launch that folds the partial sums, below)
     c.chk(launch_embed_bwd(ea, eg, Nq, c.drop, c.stream, &embed_dw, false));
@@ -1306,6 +1308,21 @@ int hual_seqpan_ws_table(const hual_cfg* cfg, int B, int T, int L, int C, hual_w
   return n;
 }
 
+// the lookup table of the word embedding: the caller's frozen table, or - hual_cfg.finetune_word_emb - the params entry, where the
+// caller's pointer must be NULL or that very address (a different table would silently not be the one that trains)
+static int resolve_word_table(const Ctx& c, const float* params, const float* word_table, bool required, const float** out) {
+  if (c.pm.word_table == (size_t)-1) {
+    HUAL_REQUIRE(!required || word_table != nullptr, "null word_table");
+    *out = word_table;
+    return 0;
+  }
+  const float* own = params + c.pm.word_table;
+  HUAL_REQUIRE(word_table == nullptr || word_table == own,
+               "model.finetune_word_emb: word_table must be NULL or the address of the params entry word_embs/word_table");
+  *out = own;
+  return 0;
+}
+
 static int check_common(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts,
                         void* workspace) {
   HUAL_REQUIRE(cfg && params && batch && opts && workspace, "null argument");
@@ -1324,7 +1341,6 @@ int hual_seqpan_forward(const hual_cfg* cfg, const float* params, const float* w
                         uint64_t ws_bytes, void* stream) {
   int rc = check_common(cfg, params, batch, opts, workspace);
   if (rc) return rc;
-  HUAL_REQUIRE(word_table != nullptr, "null word_table");
   HUAL_REQUIRE(out && out->start_logits && out->end_logits && out->match_scores && out->start_index && out->end_index,
                "null output tensor");
   if (labels) HUAL_REQUIRE(labels->y1 && labels->y2 && labels->match_labels && labels->inner_labels, "null label tensor");
@@ -1336,7 +1352,7 @@ int hual_seqpan_forward(const hual_cfg* cfg, const float* params, const float* w
   c.base = (char*)workspace;
   c.stream = (hipStream_t)stream;
   c.P = params;
-  c.word_table = word_table;
+  if ((rc = resolve_word_table(c, params, word_table, true, &c.word_table))) return rc;
   c.drop = make_dropcfg(opts->rng_state, opts->drop_rate);
   c.want_bwd = labels != nullptr;
   c.debug_taps = opts->debug_taps != 0;
@@ -1365,7 +1381,7 @@ int hual_seqpan_backward(const hual_cfg* cfg, const float* params, const float* 
   HUAL_REQUIRE(!opts->dw_table || ((uintptr_t)opts->dw_table & 15) == 0, "unaligned hual_run_opts.dw_table");
   c.ext_table = opts->dw_table;
   c.ext_table_bytes = (size_t)opts->dw_table_bytes;
-  c.word_table = word_table;
+  if ((rc = resolve_word_table(c, params, word_table, false, &c.word_table))) return rc;
   c.drop = make_dropcfg(opts->rng_state, opts->drop_rate);
   c.rs.rowmask = c.vec("rowmask");
   c.rsv.rowmask = c.rs.rowmask;
@@ -1438,7 +1454,7 @@ int run_block(const hual_cfg* cfg, const float* params, const float* word_table,
   c.stream = (hipStream_t)stream;
   c.P = params;
   c.G = grads;
-  c.word_table = word_table;
+  if ((rc = resolve_word_table(c, params, word_table, false, &c.word_table))) return rc;
   c.drop = make_dropcfg(opts->rng_state, opts->drop_rate);
   c.sel_stage = stage; c.sel_sub = sub; c.want_bwd = true;
   c.debug_taps = opts->debug_taps != 0;
@@ -1485,7 +1501,7 @@ extern "C" {
 
 int hual_video_proj_ln_fwd(const hual_cfg* cfg, const float* params, const float* word_table, const hual_batch* batch,
                            const hual_run_opts* opts, float* x0, void* workspace, uint64_t ws_bytes, void* stream) {
-  HUAL_REQUIRE(cfg && batch && x0 && word_table, "hual_video_proj_ln_fwd: null argument");
+  HUAL_REQUIRE(cfg && batch && x0 && (word_table || cfg->finetune_word_emb), "hual_video_proj_ln_fwd: null argument");
   const size_t R = (size_t)batch->B * (batch->T + batch->L);
   return run_block(cfg, params, word_table, batch, opts, nullptr, workspace, ws_bytes, stream, ST_INPUT, 0, false, {},
                    {BlkCopy{"cb.x0", nullptr, x0, 0, R}}, nullptr);

@@ -2,7 +2,7 @@
 "gloo" in the CPU tests).  The reference is single-process; data parallelism is the build's addition
 and is exact, i.e. N ranks x B clips reproduce the single-process gradient of the N*B-clip batch:
 
-  * gradients: ONE flat fp32 bucket (the whole parameter layout, ~4.75 MB) summed with all_reduce, then scaled by
+  * gradients: ONE flat fp32 bucket (the whole parameter layout, ~4.75 MB; longer with a trainable word table) summed with all_reduce, then scaled by
     1/world inside the fused clip+AdamWD kernel (grad_prescale);
   * matching loss (layers.py:172-173) divides by the GLOBAL valid-frame count: every rank uses the denominator
     n_global/world so that the rank average equals the global masked mean;

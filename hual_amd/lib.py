@@ -20,7 +20,7 @@ class hual_cfg(ctypes.Structure):
                 ('word_dim', ctypes.c_int32), ('char_dim', ctypes.c_int32), ('max_vlen', ctypes.c_int32),
                 ('attn_layer', ctypes.c_int32), ('num_chars', ctypes.c_int32), ('num_words', ctypes.c_int32),
                 ('no_gumbel', ctypes.c_int32), ('match_lambda', ctypes.c_float), ('tau', ctypes.c_float),
-                ('clip_norm', ctypes.c_float)]
+                ('clip_norm', ctypes.c_float), ('finetune_word_emb', ctypes.c_int32)]
 
 
 class hual_param_entry(ctypes.Structure):
@@ -85,6 +85,9 @@ def load():
     v = lib.hual_abi_version()
     if v != ABI_VERSION:
         raise HualError('libhual_seqpan.so ABI %d != python binding %d: rebuild' % (v, ABI_VERSION))
+    lib.hual_cfg_bytes.restype = ctypes.c_uint64
+    if lib.hual_cfg_bytes() != ctypes.sizeof(hual_cfg):
+        raise HualError('libhual_seqpan.so hual_cfg is %d bytes, python binding %d: rebuild' % (lib.hual_cfg_bytes(), ctypes.sizeof(hual_cfg)))
     lib.hual_seqpan_dw_table_bytes.restype = ctypes.c_uint64
     vp, i32, u64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_float
     P = ctypes.POINTER
@@ -161,7 +164,7 @@ def stream_ptr(stream=None):
 def make_cfg(**kw):
     c = hual_cfg()
     d = dict(vdim=1024, dim=128, num_heads=8, word_dim=300, char_dim=50, max_vlen=64, attn_layer=2, num_chars=40,
-             num_words=500, no_gumbel=1, match_lambda=1.0, tau=0.3, clip_norm=1.0)
+             num_words=500, no_gumbel=1, match_lambda=1.0, tau=0.3, clip_norm=1.0, finetune_word_emb=0)
     d.update(kw)
     for k, v in d.items():
         setattr(c, k, v)

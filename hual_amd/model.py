@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import lib
-from .params import ParamTable
+from .params import WORD_TABLE, ParamTable
 
 
 def _get(cfg, path, default=None):
@@ -48,7 +48,8 @@ def cfg_from_configs(configs, num_words):
         attn_layer=int(_get(configs, 'model.attn_layer')), num_chars=int(_get(configs, 'num_chars')),
         num_words=int(num_words), no_gumbel=1 if _get(configs, 'loss.no_gumbel', True) else 0,
         match_lambda=float(_get(configs, 'loss.match_lambda', 1.0)), tau=float(_get(configs, 'loss.tau', 0.3)),
-        clip_norm=float(_get(configs, 'train.clip_norm', 1.0)))
+        clip_norm=float(_get(configs, 'train.clip_norm', 1.0)),
+        finetune_word_emb=1 if _get(configs, 'model.finetune_word_emb', False) else 0)
 
 
 class SeqPAN:
@@ -62,8 +63,13 @@ class SeqPAN:
         lib.check(lib.load().hual_seqpan_validate(ctypes.byref(self.cfg)))
         assert wv.shape == (self.cfg.num_words - 2, self.cfg.word_dim), 'word_vectors must be [num_words-2, word_dim]'
         self.table = ParamTable(self.cfg)
-        self.word_table = torch.from_numpy(wv).to(self.device).contiguous()
-        self.params = torch.from_numpy(self.table.init_flat(seed)).to(self.device)
+        self.finetune_word_emb = bool(self.cfg.finetune_word_emb)
+        self.params = torch.from_numpy(self.table.init_flat(seed, wv if self.finetune_word_emb else None)).to(self.device)
+        if self.finetune_word_emb:      # model.finetune_word_emb: the GloVe table is the last entry of the flat layout, trained with it
+            e = self.table.by_name[WORD_TABLE]
+            self.word_table = self.params[e['offset']:e['offset'] + e['size']].view(*e['shape'])
+        else:
+            self.word_table = torch.from_numpy(wv).to(self.device).contiguous()
         self.grads = torch.zeros_like(self.params)
         self.adam_m = torch.zeros_like(self.params)
         self.adam_v = torch.zeros_like(self.params)
@@ -88,6 +94,15 @@ class SeqPAN:
         return self.table.unpack(self.params.detach().cpu().numpy())
 
     def load_state_dict(self, named):
+        """named: TF name -> array.  A fine-tuning model (model.finetune_word_emb) keeps its current word table when `named` has
+        none (a frozen model's checkpoint: fine-tuning starts from GloVe); a frozen model refuses a checkpoint that holds a trained
+        table - dropping it would change the predictions."""
+        if WORD_TABLE in named and not self.finetune_word_emb:
+            raise lib.HualError('the checkpoint holds a trained %s: load it into a model with model.finetune_word_emb: true'
+                                % WORD_TABLE)
+        if self.finetune_word_emb and WORD_TABLE not in named:
+            named = dict(named)
+            named[WORD_TABLE] = self.word_table.detach().cpu().numpy()
         self.params.copy_(torch.from_numpy(self.table.pack(named)).to(self.device))
 
     def grads_dict(self):

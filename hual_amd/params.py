@@ -25,6 +25,9 @@ def _glorot_limit(shape):
     return math.sqrt(6.0 / (fan_in + fan_out))
 
 
+WORD_TABLE = 'word_embs/word_table'      # the GloVe table's TF name (modules.py:10); a layout entry only with model.finetune_word_emb
+
+
 def init_kind(name):
     if name.endswith('layer_norm_scale'):
         return 'ones'
@@ -44,13 +47,20 @@ class ParamTable:
     def names(self):
         return [e['name'] for e in self.entries]
 
-    def init_flat(self, seed=12345):
-        """numpy float32 [padded] with the reference initialisers."""
+    def init_flat(self, seed=12345, word_vectors=None):
+        """numpy float32 [padded] with the reference initialisers.  A fine-tuned word table (model.finetune_word_emb) starts
+        as the GloVe matrix `word_vectors` (modules.py:10-12, initializer=word_vectors) and draws nothing from the generator:
+        every other entry gets the values it gets without the table."""
         g = np.random.default_rng(seed)
         flat = np.zeros(self.padded, dtype=np.float32)
         for e in self.entries:
             shape, kind = e['shape'], init_kind(e['name'])
-            if kind == 'ones':
+            if e['name'] == WORD_TABLE:
+                if word_vectors is None:
+                    raise lib.HualError('init_flat: %s is trainable (model.finetune_word_emb): word_vectors required' % WORD_TABLE)
+                a = np.asarray(word_vectors, dtype=np.float32)
+                assert list(a.shape) == shape, (WORD_TABLE, a.shape, shape)
+            elif kind == 'ones':
                 a = np.ones(shape)
             elif kind == 'zeros':
                 a = np.zeros(shape)

@@ -26,6 +26,7 @@ from . import al, data, lib
 from . import dist as hdist
 from .dataset import DeviceDataset
 from .model import SeqPAN
+from .params import WORD_TABLE
 from .train import Trainer
 
 
@@ -243,4 +244,7 @@ class Runner:
 
     def load(self, path):
         with np.load(path) as z:
-            self.model.load_state_dict({k.replace('|', '/'): z[k] for k in z.files})
+            named = {k.replace('|', '/'): z[k] for k in z.files}
+        if self.model.finetune_word_emb and WORD_TABLE not in named:
+            self.log.info('%s holds no %s: fine-tuning starts from the GloVe table' % (path, WORD_TABLE))
+        self.model.load_state_dict(named)

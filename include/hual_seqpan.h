@@ -65,16 +65,26 @@ typedef struct hual_cfg {
   float match_lambda;  /* loss.match_lambda */
   float tau;           /* loss.tau (> 0; unused when no_gumbel) */
   float clip_norm;     /* train.clip_norm */
+  int32_t finetune_word_emb;   /* model.finetune_word_emb (absent = 0; modules.py:8-16 `finetune`): 1 makes the GloVe table
+                                  `word_embs/word_table` [num_words-2, word_dim] a trainable variable.  It is then the LAST entry
+                                  of the flat parameter layout (every other offset unchanged), the forward reads the lookup table
+                                  there, the backward scatters its gradient there (after the word-dropout mask; PAD rows add
+                                  nothing, unk rows go to word_embs/unk as before), and clip + AdamWeightDecay treat it as any
+                                  other decayed variable: a DENSE update of every row every step (ops.py:166-170). */
 } hual_cfg;
 
 int hual_abi_version(void);
+/* sizeof(hual_cfg) as this library was compiled: a binding checks it against its own copy of the struct (the layout grew a
+ * trailing field, finetune_word_emb, without a change of HUAL_ABI_VERSION) */
+uint64_t hual_cfg_bytes(void);
 const char* hual_last_error(void);
 
 /* ------------------------------------------------------------------------------------------
  * Parameters.  One flat fp32 device buffer in the layout reported by hual_seqpan_param_table():
  * every trainable TF variable of models/model.py under its TF scope name and TF
  * shape, each tensor 16-byte aligned.  Gradients and both Adam slots use the same layout.
- * The frozen GloVe table `word_embs/word_table` [num_words-2, word_dim] (modules.py:10) is separate.
+ * The GloVe table `word_embs/word_table` [num_words-2, word_dim] (modules.py:10) is separate while it is frozen (the
+ * reference's SeqPAN, model.py:36); with hual_cfg.finetune_word_emb it is the last entry of the layout.
  * ------------------------------------------------------------------------------------------ */
 typedef struct hual_param_entry {
   char name[112];
@@ -86,7 +96,8 @@ typedef struct hual_param_entry {
 } hual_param_entry;
 
 int hual_seqpan_validate(const hual_cfg* cfg);
-/* *padded_floats = size of the flat buffer, *count = number of trainable scalars (1,186,508 for Charades) */
+/* *padded_floats = size of the flat buffer, *count = number of trainable scalars (1,186,508 for Charades; with
+ * finetune_word_emb plus (num_words-2) * word_dim) */
 int hual_seqpan_param_count(const hual_cfg* cfg, uint64_t* padded_floats, uint64_t* count);
 /* returns the number of entries (fills at most max_entries) or a negative error */
 int hual_seqpan_param_table(const hual_cfg* cfg, hual_param_entry* out, int max_entries);
@@ -174,7 +185,10 @@ typedef struct hual_ws_entry {
 } hual_ws_entry;
 int hual_seqpan_ws_table(const hual_cfg* cfg, int B, int T, int L, int C, hual_ws_entry* out, int max_entries);
 
-/* the graph of model.py:29-118: all five fetch tensors in ONE pass (the reference runs five).  With `labels`
+/* word_table: the frozen GloVe table [num_words-2, word_dim] (device).  With cfg->finetune_word_emb the table is the params entry
+ * `word_embs/word_table`: pass NULL or exactly that address (any other pointer is an error, not a silent choice between the two);
+ * the same rule holds for hual_video_proj_ln_fwd.
+ * The graph of model.py:29-118: all five fetch tensors in ONE pass (the reference runs five).  With `labels`
  * it also evaluates model.py:76-120 (losses) and keeps what backward needs in the workspace.
  * Dense weights travel as fp16 hi + lo images scaled by 2^10: a weight with |w| >= 63 does not fit.  The pass does not fail
  * silently on one: with labels the four loss terms are NaN, without labels the start / end logits are NaN and the span
@@ -183,8 +197,9 @@ int hual_seqpan_forward(const hual_cfg* cfg, const float* params, const float* w
                         const hual_labels* labels, const hual_outputs* out, const hual_run_opts* opts, void* workspace,
                         uint64_t ws_bytes, void* stream);
 
-/* tf.gradients(loss, tvars) (ops.py:126): fills `grads` (flat layout, overwritten).  Must follow a forward with
- * labels on the same workspace, batch and rng_state. */
+/* tf.gradients(loss, tvars) (ops.py:126): fills `grads` (flat layout, overwritten; with finetune_word_emb the gradient of the
+ * word table included, in the same launch as the unk row's).  Must follow a forward with labels on the same workspace, batch
+ * and rng_state. */
 int hual_seqpan_backward(const hual_cfg* cfg, const float* params, const float* word_table, const hual_batch* batch,
                          const hual_labels* labels, const hual_run_opts* opts, float* grads, void* workspace,
                          uint64_t ws_bytes, void* stream);
