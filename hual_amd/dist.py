@@ -106,7 +106,7 @@ def check_padded_length(local_longest, T):
 
 
 def global_min(local_value):
-    """min of a python integer over ranks (the collective graph-or-eager decision of Trainer._step_dp)"""
+    """min of a python integer over ranks (the collective graph-or-eager decision of Trainer._capture_dp_collective)"""
     t = torch.tensor([int(local_value)], dtype=torch.int64)
     if world_size() > 1:
         if dist.get_backend() == 'nccl':

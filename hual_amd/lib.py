@@ -154,6 +154,28 @@ def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _addr(t):
+    return None if t is None else t.data_ptr()
+
+
+def batch_struct(video, video_seq_len, word_ids, char_ids):
+    """hual_batch over device tensors: video [B,T,V] float32 or bfloat16 (-> video_dtype), word_ids [B,L], char_ids [B,L,C]"""
+    import torch
+    (B, T), L, C = video.shape[:2], word_ids.shape[1], char_ids.shape[2]
+    return hual_batch(_addr(video), _addr(video_seq_len), _addr(word_ids), _addr(char_ids), B, T, L, C,
+                      1 if video.dtype == torch.bfloat16 else 0)
+
+
+def labels_struct(y1, y2, match_labels, inner_labels):
+    return hual_labels(_addr(y1), _addr(y2), _addr(match_labels), _addr(inner_labels))
+
+
+def outputs_struct(start_logits, end_logits, match_scores, start_index, end_index, loss_terms=None):
+    """hual_outputs over device tensors (loss_terms None: a forward without labels)"""
+    return hual_outputs(_addr(start_logits), _addr(end_logits), _addr(match_scores), _addr(start_index), _addr(end_index),
+                        _addr(loss_terms))
+
+
 def stream_ptr(stream=None):
     import torch
     s = torch.cuda.current_stream() if stream is None else stream

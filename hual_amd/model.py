@@ -181,9 +181,7 @@ class SeqPAN:
         L, C = w.shape[1], c.shape[2]
         if C < 4:   # pad_char_seq can produce < 4 chars; the reference's VALID width-4 conv would fail too
             raise ValueError('char_ids needs at least 4 chars per word')
-        bt = lib.hual_batch(lib.ptr(v).value, lib.ptr(ln).value, lib.ptr(w).value, lib.ptr(c).value, B, T, L, C,
-                            1 if vdt == torch.bfloat16 else 0)
-        return bt, (v, ln, w, c), (B, T, L, C)
+        return lib.batch_struct(v, ln, w, c), (v, ln, w, c), (B, T, L, C)
 
     def _outputs(self, B, T, with_loss):
         o = dict(start_logits=torch.empty(B, T, device=self.device), end_logits=torch.empty(B, T, device=self.device),
@@ -191,15 +189,12 @@ class SeqPAN:
                  start_index=torch.empty(B, dtype=torch.int64, device=self.device),
                  end_index=torch.empty(B, dtype=torch.int64, device=self.device))
         lt = torch.zeros(4, device=self.device) if with_loss else None
-        st = lib.hual_outputs(lib.ptr(o['start_logits']).value, lib.ptr(o['end_logits']).value,
-                              lib.ptr(o['match_scores']).value, lib.ptr(o['start_index']).value,
-                              lib.ptr(o['end_index']).value, None if lt is None else lib.ptr(lt).value)
-        return o, lt, st
+        return o, lt, lib.outputs_struct(loss_terms=lt, **o)
 
     def _labels(self, y1, y2, match_labels, inner_labels):
         t = (self._to_dev(y1, torch.float32), self._to_dev(y2, torch.float32), self._to_dev(match_labels, torch.int32),
              self._to_dev(inner_labels, torch.float32))
-        return lib.hual_labels(*[lib.ptr(x).value for x in t]), t
+        return lib.labels_struct(*t), t
 
     debug_taps = False       # True: forward also writes the tensors only parity tests read (hual_run_opts.debug_taps)
 

@@ -15,41 +15,74 @@ from . import dist as hdist
 from . import lib
 
 
+class _Step:
+    """One launchable step: the ABI structs over one set of feed and fetch buffers, the job table of its weight-gradient launch and -
+    once captured - its launcher.  The static mode (set_batch) owns one, the device-fed mode (set_batch_device) a cache of them."""
+    __slots__ = ('bt', 'lab', 'out', 'table', 'tables_ready', 'seen', 'nograph', 'graph', 'drop')
+
+    def __init__(self, bt, lab, out, table):
+        self.bt, self.lab, self.out = bt, lab, out
+        # the step's OWN job table (hual_run_opts.dw_table), never in the workspace: that is shared with every other user of the
+        # model (model.forward at another shape, a second Trainer, the other padded shapes of a loop) and static_tables must not
+        # depend on what they leave there.  tables_ready: a backward on these buffers HAS written it - from then on nothing rewrites
+        # it (five launches fewer per step, eager or replayed)
+        self.table, self.tables_ready = table, False
+        self.seen = 0             # eager launches of this step so far
+        self.nograph = False      # a capture of it was refused: eager launches for good
+        self.graph = None         # the captured launcher: one CUDAGraph, or the three segment graphs of a data-parallel step ...
+        self.drop = None          # ... and the drop rate recorded in it
+
+
+# Trainer.dp_launch of a replayed data-parallel step, by "its launcher is a list of segment graphs"
+_DP_LAUNCH = {True: 'three hipGraphs of the launches, the two collectives eager between them',
+              False: 'hipGraph with the collectives captured'}
+
+
 class Trainer:
     def __init__(self, model, world=1, use_graph=True, force_dp=False):
         self.m = model
         self.world = world
         self.dp = world > 1 or force_dp          # force_dp: run the data-parallel code path on one rank (tests)
         self.use_graph = use_graph and not self.dp
-        self.dp_graph = use_graph and self.dp     # data-parallel step as a graph (nccl backend only, see _step_dp)
-        self._dp_graph_failed = False
+        self.dp_graph = use_graph and self.dp     # data-parallel step as graph(s): _dp_mode
         self.dp_launch = 'eager'                  # how the last data-parallel step was launched: eager / segment graphs / one graph
         self._prezero_token = ctypes.c_uint64(0)
-        self.graph = None
-        self.graph_drop = None
         self.shape = None
-        self._tables_ready = False
         self._lib = lib.load()
-        # device-fed mode (set_batch_device): per-shape cache of ABI structs and step graphs, outputs at the largest shape seen
+        self._cur = None             # the _Step that _opts / _forward / _backward / step work on
+        # device-fed mode (set_batch_device): per-shape cache of steps, outputs at the largest shape seen
         self.dynamic = False
-        self.graph_shapes = use_graph and not self.dp
         # per-shape cache of the device-fed mode.  The reference's own annotations give ~340 distinct (L, C) padded shapes per
         # ActivityNet epoch at batch 16 and more with varying T (tests/golden/lengths_anet.npz): the bound is far above that (an entry
         # is a few ctypes structs, a 60 KB job table and - once captured - a hipGraphExec of ~55 kernel nodes), evictions are counted
         self.cache_limit = 8192
         self.capture_after = 1       # sightings of a shape that are launched eagerly before its step graph is captured
         self._cache = {}
-        self._entry = None
         self._out_cap = None
-        self._dp_B = None
+        self._dp_bufs = {}
         self._cap_stream = None
         self._host_denom = None      # data-parallel epoch loop: the matching-loss denominator computed on the host (shard_plan)
         self._loop = None            # run_epoch: ids / cursor / span bank of the device-side epoch position, the dataset, the current views
+        self._loop_state = None
+        self._feeds = self._feed_owner = None      # run_epoch: the max-shape feed buffers and the dataset they were made for
         self._table_bytes = int(self._lib.hual_seqpan_dw_table_bytes())
-        self._dw_table = None        # static mode: this trainer's own job table (hual_run_opts.dw_table), never in the shared workspace
         if self.dp and world > 1:
             hdist.enable_custom_allreduce(model.grads)      # collective; a no-op unless HUAL_ALLREDUCE=custom (default: RCCL)
         self.stats = dict(eager=0, captured=0, replayed=0, evicted=0, capture_failed=0)
+
+    # the current step's ABI structs and launcher, for readers outside (graph: None until that step has been captured)
+    bt = property(lambda self: self._cur.bt)
+    lab = property(lambda self: self._cur.lab)
+    out = property(lambda self: self._cur.out)
+    graph = property(lambda self: None if self._cur is None else self._cur.graph)
+
+    def _new_step(self):
+        """a _Step over the feed and fetch tensors the trainer points at now"""
+        return _Step(lib.batch_struct(self.video, self.lens, self.word_ids, self.char_ids),
+                     lib.labels_struct(self.y1, self.y2, self.match, self.inner),
+                     lib.outputs_struct(self.start_logits, self.end_logits, self.match_scores, self.start_index, self.end_index,
+                                        self.loss_terms),
+                     torch.empty(self._table_bytes, dtype=torch.uint8, device=self.m.device))
 
     # ------------------------------------------------------------------ static batch buffers
     def set_batch(self, video, lens, word_ids, char_ids, y1, y2, match_labels, inner_labels, video_dtype=torch.float32):
@@ -69,8 +102,6 @@ class Trainer:
         if shape != self.shape or self.dynamic:
             self.dynamic = False
             self.shape = shape
-            self.graph = None
-            self._tables_ready = False
             f32, i32 = torch.float32, torch.int32
             self.video = torch.empty(B, T, V, device=dev, dtype=video_dtype)
             self.lens = torch.empty(B, device=dev, dtype=i32)
@@ -87,17 +118,9 @@ class Trainer:
             self.end_index = torch.empty(B, device=dev, dtype=torch.int64)
             self.loss_terms = torch.zeros(4, device=dev)
             self.ws = m._workspace(B, T, L, C)
-            # the job table of the weight-gradient launch is this trainer's own: the workspace is shared with every other user of the
-            # model (model.forward at another shape, a second Trainer), static_tables must not depend on what they leave there
-            self._dw_table = torch.empty(self._table_bytes, dtype=torch.uint8, device=dev)
             self._cache.clear()       # (entries of an earlier device-fed phase hold the addresses of the old fetch tensors)
             self._out_cap = None
-            p = lib.ptr
-            self.bt = lib.hual_batch(p(self.video).value, p(self.lens).value, p(self.word_ids).value,
-                                     p(self.char_ids).value, B, T, L, C, 1 if video_dtype == torch.bfloat16 else 0)
-            self.lab = lib.hual_labels(p(self.y1).value, p(self.y2).value, p(self.match).value, p(self.inner).value)
-            self.out = lib.hual_outputs(p(self.start_logits).value, p(self.end_logits).value, p(self.match_scores).value,
-                                        p(self.start_index).value, p(self.end_index).value, p(self.loss_terms).value)
+            self._cur = self._new_step()
             if self.dp:
                 self._alloc_dp(B)
 
@@ -118,14 +141,11 @@ class Trainer:
         alignment loss, its value, and the device scalar holding the matching-loss denominator.  One set per local batch size, kept for
         the trainer's lifetime: the segment graphs of a padded shape hold their addresses (an epoch's ragged last batch comes back
         every epoch)."""
-        if not hasattr(self, '_dp_bufs'):
-            self._dp_bufs = {}
         if B not in self._dp_bufs:
             dev, Bg = self.m.device, B * self.world
             self._dp_bufs[B] = (torch.empty(2 * Bg * Bg + Bg, device=dev), torch.empty(Bg, 256, device=dev), torch.zeros(1, device=dev),
                                 torch.zeros(1, device=dev))
         self.align_scratch, self.feat_all, self.align_loss, self.denom_dev = self._dp_bufs[B]
-        self.graph = None
 
     def _update_match_denominator(self):
         """exact data parallel: the masked matching loss divides by the GLOBAL valid-frame count; every rank
@@ -153,7 +173,7 @@ class Trainer:
         happen outside any capture) and captured the second time; with static feed buffers (DeviceDataset.feed_buffers) and
         the one workspace of SeqPAN.reserve() every later batch of that shape is ONE graph launch.  Nothing is allocated,
         filled or synchronised when the shape changes."""
-        m, dev = self.m, self.m.device
+        m = self.m
         B, T, V = feeds['video'].shape
         L, C = feeds['word_ids'].shape[1], feeds['char_ids'].shape[2]
         self.dynamic = True
@@ -163,39 +183,24 @@ class Trainer:
         self.shape = (B, T, L, C, vdt)
         self._ensure_outputs(B, T)
         self.ws = m._workspace(B, T, L, C)
-        p = lib.ptr
-        lp = self._loop
-        key = (B, T, L, C, vdt, self.ws.data_ptr(), self._out_flat.data_ptr(), self.loss_terms.data_ptr(), self.spans.data_ptr(),
-               0 if lp is None else (lp['ids'].data_ptr(), lp['cursor'].data_ptr(), lp['bank'].data_ptr())) + tuple(
-            t.data_ptr() for t in (self.video, self.lens, self.word_ids, self.char_ids, self.y1, self.y2, self.match, self.inner))
-        e = self._cache.get(key)
-        if e is None:
-            if len(self._cache) >= self.cache_limit:            # bounded: drop the least recently used shape
-                self._cache.pop(next(iter(self._cache)))
-                self.stats['evicted'] += 1
-            # table: the shape's OWN job table of the weight-gradient launch - the workspace is shared between shapes, the table is
-            # not, so from the shape's second step on nothing rewrites it (five launches fewer per step, eager or replayed)
-            e = dict(seen=0, graph=None, drop=None, nograph=False, tables_ready=False,
-                     table=torch.empty(self._table_bytes, dtype=torch.uint8, device=dev),
-                     bt=lib.hual_batch(p(self.video).value, p(self.lens).value, p(self.word_ids).value, p(self.char_ids).value,
-                                       B, T, L, C, 1 if vdt == torch.bfloat16 else 0),
-                     lab=lib.hual_labels(p(self.y1).value, p(self.y2).value, p(self.match).value, p(self.inner).value))
-        else:
-            self._cache.pop(key)                                 # re-insert: most recently used last
-        self._cache[key] = e
-        self._entry = e
-        self.bt, self.lab = e['bt'], e['lab']
         self.start_logits = self._out_flat[:B * T].view(B, T)
         self.end_logits = self._out_flat[self._out_cap[0] * self._out_cap[1]:][:B * T].view(B, T)
         self.match_scores = self._out_flat[2 * self._out_cap[0] * self._out_cap[1]:][:B * T * 4].view(B, T, 4)
         self.start_index, self.end_index = self.spans[0, :B], self.spans[1, :B]
-        self.out = lib.hual_outputs(p(self.start_logits).value, p(self.end_logits).value, p(self.match_scores).value,
-                                    p(self.start_index).value, p(self.end_index).value, p(self.loss_terms).value)
-        self._dw_table = e['table']
-        self._tables_ready = e['tables_ready']
-        if self.dp and (self._dp_B != B):
+        lp = self._loop
+        key = (B, T, L, C, vdt, self.ws.data_ptr(), self._out_flat.data_ptr(), self.loss_terms.data_ptr(), self.spans.data_ptr(),
+               0 if lp is None else (lp['ids'].data_ptr(), lp['cursor'].data_ptr(), lp['bank'].data_ptr())) + tuple(
+            t.data_ptr() for t in (self.video, self.lens, self.word_ids, self.char_ids, self.y1, self.y2, self.match, self.inner))
+        s = self._cache.pop(key, None)                           # (re-)inserted below: most recently used last
+        if s is None:
+            if len(self._cache) >= self.cache_limit:            # bounded: drop the least recently used shape
+                self._cache.pop(next(iter(self._cache)))
+                self.stats['evicted'] += 1
+            s = self._new_step()
+        self._cache[key] = s
+        self._cur = s
+        if self.dp:
             self._alloc_dp(B)
-            self._dp_B = B
         self._update_match_denominator()
 
     def _ensure_outputs(self, B, T):
@@ -222,33 +227,34 @@ class Trainer:
     def _opts(self, drop_rate, align_external, defer_loss=True):
         """defer_loss: the forward leaves the closing of the loss to the backward's matching-head launch (one launch fewer per step,
         hual_run_opts.deferred_loss_terms) - for a forward that IS followed by its backward; False for a forward on its own"""
-        # static_tables: all buffers of this trainer are static per shape, so after one backward on them the job tables
-        # in the workspace stay valid (hual_run_opts.static_tables)
+        # static_tables: all buffers of a step are static, so after one backward on them its job table stays valid
+        # (hual_run_opts.static_tables)
+        s = self._cur
         return lib.hual_run_opts(float(drop_rate), lib.ptr(self.m.rng_state).value, float(self.match_denom),
                                  int(align_external),
-                                 1 if (self._tables_ready and not os.environ.get('HUAL_NO_STATIC_TABLES')) else 0,
+                                 1 if (s.tables_ready and not os.environ.get('HUAL_NO_STATIC_TABLES')) else 0,
                                  lib.ptr(self.denom_dev).value if self.dp else None, 0,
                                  # the forward's first launch zeroes the gradient bucket (one launch fewer in backward); the
                                  # host word is the receipt the backward call checks and clears (hual_run_opts.prezero_token)
                                  lib.ptr(self.m.grads).value, ctypes.addressof(self._prezero_token),
                                  lib.ptr(self.loss_terms).value if defer_loss else None,
-                                 lib.ptr(self._dw_table).value if self._dw_table is not None else None,
-                                 self._table_bytes if self._dw_table is not None else 0)
+                                 lib.ptr(s.table).value, self._table_bytes)
 
     def _forward(self, opts):
-        m = self.m
+        m, s = self.m, self._cur
         lib.check(self._lib.hual_seqpan_forward(
-            ctypes.byref(m.cfg), lib.ptr(m.params), lib.ptr(m.word_table), ctypes.byref(self.bt), ctypes.byref(self.lab),
-            ctypes.byref(self.out), ctypes.byref(opts), lib.ptr(self.ws), self.ws.numel(), lib.stream_ptr()))
+            ctypes.byref(m.cfg), lib.ptr(m.params), lib.ptr(m.word_table), ctypes.byref(s.bt), ctypes.byref(s.lab),
+            ctypes.byref(s.out), ctypes.byref(opts), lib.ptr(self.ws), self.ws.numel(), lib.stream_ptr()))
 
     def _backward(self, opts):
-        m = self.m
-        self._tables_ready = True
-        if self.dynamic and self._entry is not None:
-            self._entry['tables_ready'] = True
+        m, s = self.m, self._cur
         lib.check(self._lib.hual_seqpan_backward(
-            ctypes.byref(m.cfg), lib.ptr(m.params), lib.ptr(m.word_table), ctypes.byref(self.bt), ctypes.byref(self.lab),
+            ctypes.byref(m.cfg), lib.ptr(m.params), lib.ptr(m.word_table), ctypes.byref(s.bt), ctypes.byref(s.lab),
             ctypes.byref(opts), lib.ptr(m.grads), lib.ptr(self.ws), self.ws.numel(), lib.stream_ptr()))
+        # the launches that write the job table are enqueued - unless this call only recorded them: then the graph's first replay
+        # runs them (_replay)
+        if not s.tables_ready and not torch.cuda.is_current_stream_capturing():
+            s.tables_ready = True
 
     def _adam(self, prescale):
         m = self.m
@@ -314,124 +320,39 @@ class Trainer:
         self._dp_reduce()
         self._dp_part_c()
 
-    def _capture_dp_segments(self, drop_rate):
-        """The three runs of OUR launches as three hipGraphs (records only, nothing executes); the collectives stay OUTSIDE and are
-        issued eagerly between the replays - no RCCL call inside a graph (that form, _step_dp's full capture, has never run on two
-        devices and stays opt-in), but 57 of the step's 59 host launches collapse into three.  Ranks need not agree on it: a rank on
-        segment graphs and a rank on eager launches issue the same two collectives in the same order.  Returns None if a capture is
-        refused."""
-        if self._cap_stream is None:
-            self._cap_stream = torch.cuda.Stream(device=self.m.device)
-        cs, cur = self._cap_stream, torch.cuda.current_stream()
-        opts = self._opts(drop_rate, 1)
-        segs = []
-        for part in (lambda: self._dp_part_a(opts), lambda: self._dp_part_b(opts), self._dp_part_c):
-            g = torch.cuda.CUDAGraph()
-            cs.wait_stream(cur)
-            err = None
-            with torch.cuda.stream(cs):
-                # thread_local: the process group's watchdog thread may touch the device while this thread captures
-                g.capture_begin(capture_error_mode='thread_local')
-                try:
-                    part()
-                except BaseException as ex:
-                    err = ex
-                try:
-                    g.capture_end()
-                except RuntimeError as ex:
-                    err = err or ex
-            cur.wait_stream(cs)
-            if err is not None:
-                if isinstance(err, lib.HualError) or not isinstance(err, RuntimeError):
-                    raise err
-                print('[hual] data-parallel step: segment capture refused (%s) - eager launches' % str(err).splitlines()[0], file=sys.stderr)
-                return None
-            segs.append(g)
-        return segs
-
-    def _replay_dp_segments(self, segs):
-        segs[0].replay()
-        self._dp_gather()
-        segs[1].replay()
-        self._dp_reduce()
-        segs[2].replay()
-
-    def step(self, lr, drop_rate):
+    # ------------------------------------------------------------------ capture
+    def _warm_up(self, enqueue):
+        """one eager step outside capture (first-use hipFuncSetAttribute etc., RCCL channel setup) on a snapshot of the training
+        state: the first replay of the graph captured next is the first real step"""
         m = self.m
-        if m.lr_value != float(lr):               # the fed scalar changes once per epoch (main.py:61): no fill launch otherwise
-            m.lr.fill_(float(lr))
-            m.lr_value = float(lr)
-        if self.dynamic:
-            self._step_dynamic(drop_rate)
-        elif self.dp:
-            self._step_dp(drop_rate)
-        elif not self.use_graph:
-            self._enqueue_single(drop_rate)
-        else:
-            if self.graph is None or self.graph_drop != drop_rate:
-                # warm-up outside capture (first-use hipFuncSetAttribute etc.) on a snapshot of the training state,
-                # then capture the whole step; the first replay below is the first real step
-                snap = [t.clone() for t in (m.params, m.adam_m, m.adam_v, m.rng_state)]
-                self._enqueue_single(drop_rate)
-                torch.cuda.synchronize()
-                for t, s in zip((m.params, m.adam_m, m.adam_v, m.rng_state), snap):
-                    t.copy_(s)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                # thread_local: a capture must not make other threads' HIP calls illegal (a loader thread that synchronises its own stream
-                # would fail AND invalidate the capture in the default global mode); the capturing thread itself only launches kernels
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    self._enqueue_single(drop_rate)
-                self.graph, self.graph_drop = g, drop_rate
-            self.graph.replay()
-        m.global_step += 1
+        state = (m.params, m.adam_m, m.adam_v, m.rng_state)
+        snap = [t.clone() for t in state]
+        enqueue()
+        torch.cuda.synchronize()
+        for t, s in zip(state, snap):
+            t.copy_(s)
+        torch.cuda.synchronize()
 
-    def _step_dynamic(self, drop_rate):
-        """device-fed mode: eager on the first `capture_after` sightings of a (shape, addresses) key, then captured, replayed after.
-        Data parallel: eager launches (the collectives inside a step graph are opt-in, _step_dp)."""
-        e = self._entry
-        if self.dp:
-            # segment graphs per shape (the collectives between them eager): default with world > 1 (HUAL_DP_GRAPH=seg), see _step_dp
-            segmented = self.dp_graph and self._dp_mode() == 'seg' and not e['nograph']
-            if segmented and e.get('segs') is not None and e['drop'] == drop_rate:
-                self._replay_dp_segments(e['segs'])
-                self.stats['replayed'] += 1
-                return
-            if segmented and e['seen'] >= self.capture_after:
-                segs = self._capture_dp_segments(drop_rate)
-                if segs is not None:
-                    e['segs'], e['drop'] = segs, drop_rate
-                    self._replay_dp_segments(segs)
-                    self.stats['captured'] += 1
-                    return
-                e['nograph'] = True
-                self.stats['capture_failed'] += 1
-            self._enqueue_dp(drop_rate)
-            e['seen'] += 1
-            self.stats['eager'] += 1
-            return
-        if e['graph'] is not None and e['drop'] == drop_rate:
-            e['graph'].replay()
-            self.stats['replayed'] += 1
-            return
-        if not self.graph_shapes or e['nograph'] or e['seen'] < self.capture_after:
-            self._enqueue_single(drop_rate)
-            e['seen'] += 1
-            self.stats['eager'] += 1
-            return
-        # capture on a side stream by hand (records, executes nothing: the replay below IS the step).  Not `with torch.cuda.graph(g)`:
-        # that context synchronises the device and runs the garbage collector on entry - tens of milliseconds per shape.  A capture
-        # costs ~1 ms of host time (measured over 250 shapes of the ActivityNet length distribution, scripts/exp/epoch_real.py).
-        g = torch.cuda.CUDAGraph()
+    def _capture(self, enqueue):
+        """Record the launches of `enqueue` as a hipGraph on a side stream, by hand (records, executes nothing).  Not the
+        `torch.cuda.graph` context: it synchronises the device and runs the garbage collector on entry - tens of milliseconds per
+        shape (our launches allocate nothing, so its private memory pool is not needed either).  A capture costs ~1 ms of host time
+        (measured over 250 shapes of the ActivityNet length distribution, scripts/exp/epoch_real.py).
+        Returns (graph, None), or (None, error) if the runtime refused the capture.  An error of one of our own launches (lib.HualError:
+        bad arguments) would fail eagerly too and is raised, as is anything that is not a RuntimeError."""
         if self._cap_stream is None:
             self._cap_stream = torch.cuda.Stream(device=self.m.device)
         cs, cur = self._cap_stream, torch.cuda.current_stream()
+        g = torch.cuda.CUDAGraph()
         cs.wait_stream(cur)
         err = None
         with torch.cuda.stream(cs):
-            g.capture_begin(capture_error_mode='thread_local')      # (other threads stay free to use the GPU: see step())
+            # thread_local: a capture must not make other threads' HIP calls illegal (a loader thread that synchronises its own stream,
+            # the process group's watchdog thread - they would fail AND invalidate the capture in the default global mode); the
+            # capturing thread itself only launches kernels
+            g.capture_begin(capture_error_mode='thread_local')
             try:
-                self._enqueue_single(drop_rate)
+                enqueue()
             except BaseException as ex:          # our own launch failed under capture: end the capture, keep THIS error
                 err = ex
             try:
@@ -439,103 +360,145 @@ class Trainer:
             except RuntimeError as ex:           # the runtime refused the capture
                 err = err or ex
         cur.wait_stream(cs)
-        if err is not None:
-            # nothing was executed.  A refused capture leaves the shape on eager launches for good; an error of one of our own
-            # launches (lib.HualError: bad arguments) would fail eagerly too and is raised
-            self.stats['capture_failed'] += 1
-            e['nograph'] = True
-            if isinstance(err, lib.HualError) or not isinstance(err, RuntimeError):
-                raise err
-            print('[hual] step graph capture refused for shape %s (%s): eager launches' % (self.shape[:4], str(err).splitlines()[0]),
-                  file=sys.stderr)
-            self._enqueue_single(drop_rate)
-            e['seen'] += 1
-            self.stats['eager'] += 1
-            return
-        e['graph'], e['drop'] = g, drop_rate
-        g.replay()
-        self.stats['captured'] += 1
+        if err is None:
+            return g, None
+        if isinstance(err, lib.HualError) or not isinstance(err, RuntimeError):
+            raise err
+        return None, err
+
+    def _capture_dp_segments(self, drop_rate):
+        """The three runs of OUR launches as three hipGraphs; the collectives stay OUTSIDE and are issued eagerly between the replays -
+        no RCCL call inside a graph (that form, _capture_dp_collective, has never run on two devices and stays opt-in), but 57 of the
+        step's 59 host launches collapse into three.  Ranks need not agree on it: a rank on segment graphs and a rank on eager
+        launches issue the same two collectives in the same order.  Returns None if a capture is refused."""
+        opts = self._opts(drop_rate, 1)
+        segs = []
+        for part in (lambda: self._dp_part_a(opts), lambda: self._dp_part_b(opts), self._dp_part_c):
+            g, err = self._capture(part)
+            if g is None:
+                print('[hual] data-parallel step: segment capture refused (%s) - eager launches' % str(err).splitlines()[0], file=sys.stderr)
+                return None
+            segs.append(g)
+        return segs
+
+    def _capture_dp_collective(self, drop_rate):
+        """The data-parallel step WITH its RCCL collectives as ONE hipGraph (nccl backend: its collectives are stream operations).
+        The second capture site of this file: torch / RCCL calls run under this capture, so it keeps `torch.cuda.graph` (device
+        synchronised on entry, private memory pool) instead of _capture, and the graph-or-eager decision is COLLECTIVE: after the
+        attempt the ranks all-reduce(MIN) an ok flag, so either every rank replays or every rank launches eagerly.  Only a refused
+        capture (a RuntimeError from torch / HIP) is treated as "no graph" (returns None); an error raised by one of our own launches
+        (lib.HualError) propagates."""
+        g, err, fatal = None, None, None
+        try:
+            g = torch.cuda.CUDAGraph()
+            # thread_local: the process group's watchdog thread may touch the device while this thread captures
+            with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                self._enqueue_dp(drop_rate)
+        except lib.HualError as e:               # one of our launches failed: not a capture refusal - but the peers are about to
+            g, fatal = None, e                   # enter the collective below, so it is raised only after this rank has joined it
+        except RuntimeError as e:                # capture of the collectives refused
+            g, err = None, e
+            torch.cuda.synchronize()
+        except BaseException as e:               # anything else: same rule - join the collective first
+            g, fatal = None, e
+        # the same decision on every rank: 2 = captured, 1 = capture refused (eager launches), 0 = a launch failed (everybody raises)
+        state = hdist.global_min(2 if g is not None else (0 if fatal is not None else 1))
+        if fatal is not None:
+            raise fatal
+        if state == 0:
+            raise lib.HualError('data-parallel step: a launch failed on another rank during graph capture')
+        if state == 1:
+            print('[hual] data-parallel step: graph capture %s - eager launches on every rank'
+                  % ('refused here (%s)' % str(err).splitlines()[0] if err is not None else 'refused on another rank'), file=sys.stderr)
+            return None
+        return g
 
     def _dp_mode(self):
         """HUAL_DP_GRAPH: '1' = the whole step incl. its RCCL collectives as ONE hipGraph (default on a one-rank group: the rehearsal the
-        GPU suite runs; opt-in with more ranks - never validated on two devices), 'seg' = three graphs of our own launches with the two
-        collectives eager between them (default with more than one rank), '0' = eager launches"""
+        GPU suite runs; opt-in with more ranks - never validated on two devices), 'seg' = three graphs of our own launches
+        with the two collectives eager between them (default with more than one rank; a rank whose capture is refused simply launches
+        eagerly), '0' = eager launches.  Measured on a one-rank RCCL group: eager 1.253 ms/step, one graph with the collectives inside
+        1.210, the single-GPU graph 1.195."""
         return os.environ.get('HUAL_DP_GRAPH', '1' if self.world == 1 else 'seg')
 
-    def _step_dp(self, drop_rate):
-        """Three launch modes (_dp_mode).  With more than one rank the default is SEGMENT graphs: forward | backward | optimizer as three
-        hipGraphs of our own launches, the all-gather and the all-reduce issued eagerly between the replays - no collective inside a
-        graph, and a rank whose capture is refused simply launches eagerly (same collective sequence).  Measured on a one-rank RCCL
-        group: eager 1.253 ms/step, one graph with the collectives inside 1.210, the single-GPU graph 1.195.
-        With the nccl backend (RCCL: its collectives are stream operations) the data-parallel step, collectives included, CAN also be
-        captured into ONE hipGraph and replayed.  That is the default only on ONE rank (the forced-collectives rehearsal the GPU
-        suite runs); with more than one rank it is opt-in (HUAL_DP_GRAPH=1) until a multi-GPU run has validated capture and replay
-        of the all-gather / all-reduce pair - no such run exists yet.  There the graph-or-eager decision is COLLECTIVE: after
-        the capture attempt the ranks all-reduce(MIN) an ok flag, so either every rank replays or every rank launches eagerly.  Only a
-        refused capture (a RuntimeError from torch / HIP) is treated as "no graph"; an error raised by one of our own launches
-        (lib.HualError) propagates.  Other backends (gloo: host collectives) always launch eagerly."""
+    def _launcher_kind(self):
+        """what a step may be captured as: 'graph' (single GPU: the whole step), 'seg' / 'collective' (data parallel, _dp_mode),
+        None (eager launches only)"""
+        if not self.dp:
+            return 'graph' if self.use_graph else None
+        if not self.dp_graph:
+            return None
         mode = self._dp_mode()
-        if mode == 'seg' and self.dp_graph and not self._dp_graph_failed:
-            m = self.m
-            if self.graph is None or self.graph_drop != drop_rate:
-                snap = [t.clone() for t in (m.params, m.adam_m, m.adam_v, m.rng_state)]
-                self._enqueue_dp(drop_rate)          # warm-up outside capture (first-use attributes, RCCL channel setup)
-                torch.cuda.synchronize()
-                for t, sn in zip((m.params, m.adam_m, m.adam_v, m.rng_state), snap):
-                    t.copy_(sn)
-                torch.cuda.synchronize()
-                segs = self._capture_dp_segments(drop_rate)
-                if segs is None:
-                    self._dp_graph_failed = True
-                    self._enqueue_dp(drop_rate)
-                    return
-                self.graph, self.graph_drop = segs, drop_rate
-            self._replay_dp_segments(self.graph)
-            self.dp_launch = 'three hipGraphs of the launches, the two collectives eager between them'
-            return
-        want_graph = (mode == '1' and self.dp_graph and not self._dp_graph_failed and hdist.backend() == 'nccl')
-        if not want_graph:
-            self._enqueue_dp(drop_rate)
-            self.dp_launch = 'eager'
-            return
-        self.dp_launch = 'hipGraph with the collectives captured'
+        if mode == 'seg':
+            return 'seg'
+        # collectives inside a graph: static batches only, and only where they are stream operations (gloo: host collectives)
+        if mode == '1' and not self.dynamic and hdist.backend() == 'nccl':
+            return 'collective'
+        return None
+
+    def _record(self, kind, enqueue, drop_rate):
+        """the step's launches as a launcher of `kind`; None, after a line on stderr, if the runtime refused the capture"""
+        if kind == 'seg':
+            return self._capture_dp_segments(drop_rate)
+        if kind == 'collective':
+            return self._capture_dp_collective(drop_rate)
+        g, err = self._capture(lambda: enqueue(drop_rate))
+        if g is None:
+            if not self.dynamic:
+                raise err
+            print('[hual] step graph capture refused for shape %s (%s): eager launches' % (self.shape[:4], str(err).splitlines()[0]),
+                  file=sys.stderr)
+        return g
+
+    def _replay(self, s):
+        g = s.graph
+        if type(g) is list:
+            g[0].replay()
+            self._dp_gather()
+            g[1].replay()
+            self._dp_reduce()
+            g[2].replay()
+        else:
+            g.replay()
+        s.tables_ready = True     # (a graph recorded before the job table was written holds the launches that write it)
+
+    def step(self, lr, drop_rate):
         m = self.m
-        if self.graph is None or self.graph_drop != drop_rate:
-            snap = [t.clone() for t in (m.params, m.adam_m, m.adam_v, m.rng_state)]
-            self._enqueue_dp(drop_rate)              # warm-up outside capture (first-use attributes, RCCL channel setup)
-            torch.cuda.synchronize()
-            for t, sn in zip((m.params, m.adam_m, m.adam_v, m.rng_state), snap):
-                t.copy_(sn)
-            torch.cuda.synchronize()
-            g, err, fatal = None, None, None
-            try:
-                g = torch.cuda.CUDAGraph()
-                # thread_local: the process group's watchdog thread may touch the device while this thread captures
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    self._enqueue_dp(drop_rate)
-            except lib.HualError as e:               # one of our launches failed: not a capture refusal - but the peers are about to
-                g, fatal = None, e                   # enter the collective below, so it is raised only after this rank has joined it
-            except RuntimeError as e:                # capture of the collectives refused
-                g, err = None, e
-                torch.cuda.synchronize()
-            except BaseException as e:               # anything else: same rule - join the collective first
-                g, fatal = None, e
-            # the same decision on every rank: 2 = captured, 1 = capture refused (eager launches), 0 = a launch failed (everybody raises)
-            state = hdist.global_min(2 if g is not None else (0 if fatal is not None else 1))
-            if fatal is not None:
-                raise fatal
-            if state == 0:
-                raise lib.HualError('data-parallel step: a launch failed on another rank during graph capture')
-            if state == 1:
-                self._dp_graph_failed = True
-                self.graph = None
-                print('[hual] data-parallel step: graph capture %s - eager launches on every rank'
-                      % ('refused here (%s)' % str(err).splitlines()[0] if err is not None else 'refused on another rank'), file=sys.stderr)
-                self._enqueue_dp(drop_rate)
-                self.dp_launch = 'eager'
-                return
-            self.graph, self.graph_drop = g, drop_rate
-        self.graph.replay()
+        if m.lr_value != float(lr):               # the fed scalar changes once per epoch (main.py:61): no fill launch otherwise
+            m.lr.fill_(float(lr))
+            m.lr_value = float(lr)
+        self._launch(self._enqueue_dp if self.dp else self._enqueue_single, self._launcher_kind(), drop_rate)
+        m.global_step += 1
+
+    def _launch(self, enqueue, kind, drop_rate):
+        """Replay the current step if it is captured for this drop rate; else capture it if it may be (kind, no earlier refusal) and
+        is due, and replay - nothing executes while recording, the replay IS the step; else launch eagerly.
+        The two modes differ in when a step is due.  A static step (set_batch) is due at once and is warmed up first.  A device-fed
+        one (set_batch_device) is due after `capture_after` eager sightings of its (shape, addresses) key, which are its warm-up (first-use
+        attribute calls happen outside any capture); `stats` counts these steps only."""
+        s, dyn = self._cur, self.dynamic
+        how = 'replayed'
+        if s.graph is None or s.drop != drop_rate:
+            how = 'eager'
+            if kind is not None and not s.nograph and (s.seen >= self.capture_after or not dyn):
+                if not dyn:
+                    self._warm_up(lambda: enqueue(drop_rate))
+                g = self._record(kind, enqueue, drop_rate)
+                if g is not None:
+                    s.graph, s.drop, how = g, drop_rate, 'captured'
+                else:                             # refused: this step stays on eager launches for good
+                    s.nograph = True
+                    if dyn:
+                        self.stats['capture_failed'] += 1
+        if how == 'eager':
+            enqueue(drop_rate)
+            s.seen += 1
+        else:
+            self._replay(s)
+        if dyn:
+            self.stats[how] += 1
+        if self.dp:
+            self.dp_launch = 'eager' if how == 'eager' else _DP_LAUNCH[type(s.graph) is list]
 
     # ------------------------------------------------------------------ one epoch on a device-resident training set
     def run_epoch(self, dataset, order, batch_size, lr, drop_rate, min_chars=4, want_spans=True):
@@ -569,7 +532,7 @@ class Trainer:
         if nsteps == 0:
             return (order[:0].astype(np.int64),) * 2 if want_spans else (None, None)
         Bmax = max(st['B'] for st in steps)
-        if getattr(self, '_feed_owner', None) is not dataset or self._feeds['shape'][0] < Bmax:
+        if self._feed_owner is not dataset or self._feeds['shape'][0] < Bmax:
             self._feeds = dataset.feed_buffers(Bmax, min_chars=min_chars)
             self._feed_owner = dataset
         Bm, Tm, Lm, Cm = self._feeds['shape']
@@ -610,7 +573,7 @@ class Trainer:
     def _ensure_loop(self, dataset, n_ids, nsteps):
         """device state of the epoch loop: the rank's id list, the cursor {ids consumed, bank words written} and the span bank
         [steps, 2, B capacity].  Allocated once per (dataset size, fetch capacity) - the step graphs hold these addresses."""
-        lp = getattr(self, '_loop_state', None)
+        lp = self._loop_state
         Bcap = self.spans.shape[1]
         if lp is None or lp['ds'] is not dataset or lp['ids'].numel() < n_ids or lp['bank'].numel() < nsteps * 2 * Bcap or lp['Bcap'] != Bcap:
             dev = self.m.device

@@ -102,7 +102,7 @@ def _shape_worker(rank, world, port, q):
 
 def test_shape_check_and_graph_decision_are_collective():
     """hual_amd/dist.py check_padded_length / global_min with 2 gloo ranks: a shape mismatch raises on BOTH ranks (neither is left
-    waiting in the next collective), and the graph-or-eager decision of Trainer._step_dp is the minimum over ranks"""
+    waiting in the next collective), and the graph-or-eager decision of Trainer._capture_dp_collective is the minimum over ranks"""
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = 29100 + (os.getpid() % 300)

@@ -60,7 +60,7 @@ def test_two_ranks_on_one_gpu_match_single_process(lens, seg):
     """lens (18, 11, 9, 7): the second shard holds no full-length clip; it is padded to the GLOBAL T = 18 (Trainer.set_batch,
     data-parallel mode), which is what keeps the decomposition exact - with a shard-local T the reference's unmasked
     conv_block (modules.py:59-70) would see different rows behind each clip's end.
-    seg: the step as three hipGraphs of the launches with the two collectives eager between them (Trainer._step_dp, the default launch
+    seg: the step as three hipGraphs of the launches with the two collectives eager between them (Trainer._dp_mode, the default launch
     mode with more than one rank)"""
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import parity_util as pu

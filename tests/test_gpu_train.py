@@ -249,3 +249,41 @@ def test_static_step_graph_survives_other_users_of_the_workspace():
     assert torch.isfinite(m1.grads).all()
     scale = max(1.0, float(want.abs().max()))
     assert float((m1.grads - want).abs().max()) <= 1e-5 * scale   # (float atomics: not bit-reproducible)
+
+
+@pytest.mark.parametrize('device_fed', [False, True])
+def test_static_tables_are_claimed_only_after_the_job_table_was_written(device_fed, monkeypatch):
+    """hual_run_opts.static_tables tells the library that an earlier backward on the same buffers wrote the step's job table.  A
+    backward that fails before its weight-gradient launch has written nothing: here the options declare a table that is too small
+    (a host-side check while enqueuing, HUAL_ERR_INVALID; the tensor itself keeps its full size), so the options of the next step
+    must still carry static_tables = 0 - and 1 only after a step that succeeded."""
+    from hual_amd import lib
+    from hual_amd.train import Trainer
+    monkeypatch.delenv('HUAL_NO_STATIC_TABLES', raising=False)
+    cfg, p, wv, b, labels = pu.make_case(B=3, T=20, L=6, C=5, seed=5)
+    feeds = (b['video'].numpy(), b['lens'].numpy(), b['word_ids'].numpy(), b['char_ids'].numpy(), *[x.numpy() for x in labels])
+    m = pu.hip_model(cfg, p, wv)
+    m.set_rng(3, 1)
+    tr = Trainer(m, world=1, use_graph=False)
+    tr.set_batch(*feeds)
+    if device_fed:
+        dev = dict(video=tr.video, video_seq_len=tr.lens, word_ids=tr.word_ids, char_ids=tr.char_ids, y1=tr.y1, y2=tr.y2,
+                   match_labels=tr.match, inner_labels=tr.inner)
+        tr = Trainer(m, world=1, use_graph=False)
+        tr.set_batch_device(dev)
+    opts = tr._opts(0.1, 0)
+    assert opts.static_tables == 0
+    full = int(opts.dw_table_bytes)
+    assert full == lib.load().hual_seqpan_dw_table_bytes()
+    opts.dw_table_bytes = 16
+    tr._forward(opts)
+    with pytest.raises(lib.HualError):
+        tr._backward(opts)
+    assert tr._opts(0.1, 0).static_tables == 0
+    opts.dw_table_bytes = full
+    if device_fed:
+        tr.set_batch_device(dev)
+    tr.step(lr=0.0, drop_rate=0.1)
+    torch.cuda.synchronize()
+    assert tr._opts(0.1, 0).static_tables == 1
+    assert torch.isfinite(m.grads).all()
