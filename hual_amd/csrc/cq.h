@@ -51,11 +51,12 @@ int tri_bwd_blocks_v(const RowSpace& rs);
 int tri_bwd_blocks_q(const RowSpace& rs);
 int launch_tri_bwd_impl(const CqBufs& b, const CqBwdBufs& g, const CqParams& p, float* part, const RowSpace& rs,
                         const DropCfg& drop, const float* dXa, const float* dXb, hipStream_t s);
-// long clips (cqwide.hip): 128 < T <= 256, L <= 32
+// wide kernels (cqwide.hip): L <= T and either L <= 32, T <= 256 (32 short rows) or 33 <= L <= 64, T <= 128 (64 short rows)
 bool cq_wide_ok(const RowSpace& rs);
 int launch_cq_fwd_wide(const CqBufs& b, const CqParams& p, const RowSpace& rs, const DropCfg& drop, hipStream_t s);
 int launch_cq_bwd_wide(const CqBufs& b, const CqBwdBufs& g, const RowSpace& rs, float* dXa, float* dXb, hipStream_t s);
-// shapes whose score matrices fit none of the LDS forms (long clips with queries of more than 32 words): the global-operand kernels keep
+// shapes whose score matrices fit none of the LDS forms (queries of more than 64 words, or of more than 32 words against clips of more
+// than 128 frames, when the staged kernels do not fit either): the global-operand kernels keep
 // the matrices in global memory too - slow, but every T, L <= 256 runs.  The orchestrator sizes GS / GD by these.
 bool cq_fwd_global(int B, int T, int L);
 bool cq_bwd_global(int B, int T, int L);

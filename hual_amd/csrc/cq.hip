@@ -1043,7 +1043,8 @@ static double cq_bwd_bytes(const RowSpace& rs) { return 4.0 * (13.0 * rs.R * HUA
 // tri_prep (dropout on both roles of every row, rank-1 terms) + the attention itself: one launch when the clip fits the staged
 // kernel (it prepares the rows as it stages them), else two
 // Which kernels serve a shape: queries of at most 32 words against clips of L <= T <= 256 frames - every shape of the YAML configs and of
-// BASELINE.json - run the kernels of cqwide.hip (round 5: at the bench shape 20.8 + 26.1 us against 26.3 + 33.6 us for the staged kernels
+// BASELINE.json - and queries of 33-64 words against clips of L <= T <= 128 frames (the 64-short-row instantiations: at B16 T100 L45
+// 24.6 + 26.6 us against 46.5 + 69.7 us for the global-operand kernels) run the kernels of cqwide.hip (round 5: at the bench shape 20.8 + 26.1 us against 26.3 + 33.6 us for the staged kernels
 // below, at B32 T256 33 + 47 us against 65 + 6 + 109 us for the global-operand kernels); longer queries (or queries longer than the clip)
 // the staged kernels when everything fits LDS, else the global-operand kernels.  HUAL_CQ_NO_WIDE=1 takes cqwide.hip out (A/B timings, tests).
 static bool cq_use_wide(const RowSpace& rs) {

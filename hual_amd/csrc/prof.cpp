@@ -101,6 +101,7 @@ int hual_prof_kernel_pipe(const char* kernel, int* pipe, int* passes) {
       {"da_mid_bwd", HUAL_PIPE_MATRIX16, 3},  {"mproj_", HUAL_PIPE_MATRIX16, 3},
       {"feature_", HUAL_PIPE_MATRIX16, 3},    {"dw_f16_", HUAL_PIPE_MATRIX16, 3},
       {"attn_", HUAL_PIPE_MATRIX16, 3},      {"cq_fwd_staged", HUAL_PIPE_MATRIX16, 3}, {"cq_bwd_staged", HUAL_PIPE_MATRIX16, 3},
+      {"cq_fwd_wide", HUAL_PIPE_MATRIX16, 3}, {"cq_bwd_wide", HUAL_PIPE_MATRIX16, 3},      // (every instantiation: <NW> and <NW, SQ>)
       // exact fp32: v_mfma_f32_16x16x4_f32 (context-query attention of clips beyond the staged kernels' LDS budget)
       {"cq_", HUAL_PIPE_MATRIX32, 1},
   };
