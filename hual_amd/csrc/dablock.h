@@ -106,5 +106,9 @@ struct DaMidBwdArgs {
   int R; int MT; int Nv;   // (Nv: video rows of a unified row space, 0: one row space - XCD order, common.h)
 };
 int launch_da_mid_bwd(const DaMidBwdArgs& a, hipStream_t s);
+// the one-product ln_proj_bwd (dense_2^T + layer_norm_2 backward) and the gated middle behind it as ONE launch: the same stores, the
+// same arithmetic; the middle takes dZ1 from the chip.  fits(): one product, one layer norm, a.dz == m.dz1, equal rows and row tiles
+bool ln2_mid_bwd_fits(const LnProjBwdArgs& a, const DaMidBwdArgs& m);
+int launch_ln2_mid_bwd(const LnProjBwdArgs& a, const DaMidBwdArgs& m, const DropCfg& drop, hipStream_t s);
 
 }  // namespace hual

@@ -355,9 +355,16 @@ __global__ __launch_bounds__(CB_THREADS) void da_post_lnproj_kernel(DaPostArgs a
 // SIX: the dual attention's shape - six products, the last two into the second layer norm, no dropout' on an operand, add_dy1, both
 // layer norms, a residual addend - as compile-time facts (ln_proj_bwd_six() on the host): per product ~100 of ~575 instructions of a
 // wave were selects and compares on those uniform options, and a pair of waves saturates its SIMD's issue in these phases
-template <bool PRE, int NT, bool SIX = false>
-__global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a, DropCfg drop) {
-  extern __shared__ __attribute__((aligned(16))) char lb_lds[];
+// The first two operand tiles of the gated middle's backward (da_mid_bwd_body) and its first weight fragments: requested by the launch
+// in front of it when the two run as one kernel (MID below)
+template <int NT> struct DaMidPre { TfW wa, wb; float4 gate[NT], val[NT]; };
+// MID (ln2_mid_bwd_kernel): the one-product shape with da_mid_bwd_body behind it in the same launch - that body's first loads (pre) go out
+// in front of the row phase's barrier, ahead of this body's stores in the in-order vector-memory pipe, and the rows of dz stay in
+// registers (zv, the row layout: rows grp + 16 u) besides being stored.  false: the workgroup has no tile
+#define LB_LDS ((size_t)4 * LB_ROWS * 256 + 8 * 4 * 32 * 16 + 2 * LB_ROWS * sizeof(float))
+template <bool PRE, int NT, bool SIX, bool MID>
+__device__ __forceinline__ bool ln_proj_bwd_body(const LnProjBwdArgs& a, const DropCfg& drop, char* lb_lds, const DaMidBwdArgs* m,
+                                                 DaMidPre<NT>* mp, float4 (&zv)[LB_U]) {
   char* S0 = lb_lds;                                   // operand slot 0: hi | lo planes [48][256 B]; later dy_0 as fp32 rows
   char* S1 = S0 + 2 * LB_ROWS * 256;                   // operand slot 1; later dy_1
   char* Ps = S1 + 2 * LB_ROWS * 256;                   // the per-wave parameter sums [8][4][32] float4
@@ -368,7 +375,7 @@ __global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a
   const int col = 4 * l32;
   const int MT = a.MT, R = a.R;
   const int tile_ = xcd_tile_clip(blockIdx.x, R, a.Nv, MT);
-  if (tile_ < 0) return;
+  if (tile_ < 0) return false;
   const int r0 = tile_ * MT;                        // (grid rounded up to whole XCD rounds)
   const int RE = min(R, r0 + MT);             // rows [r0, RE) belong to this workgroup (MT need not be a multiple of 16)
   const int j = lane & 15, g = lane >> 4, ecol = 16 * wave + 4 * g;
@@ -386,10 +393,11 @@ __global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a
   const float* a0p = pre ? a.pre_dy : a.A[0];
   const int lda0 = pre ? HUAL_D : a.lda[0];
   uint32_t nkb[LB_U];                                  // keep-bit bytes of the operand rows in flight
-  const int nsteps = SIX ? 6 : a.nsteps;
+  const int nsteps = SIX ? 6 : (MID ? 1 : a.nsteps);
   auto has_bits = [&](int k) { return !SIX && a.a_bits[k] != nullptr; };
   auto to_second = [&](int k) { return SIX ? k >= 4 : a.dst[k] != 0; };
-  const bool has_g2 = SIX || a.g2 != nullptr, has_add_dy1 = SIX || a.add_dy1 != nullptr, has_dy1_bits = !SIX && a.dy1_bits != nullptr;
+  // (MID: one layer norm, nothing added to dy_0 - ln2_mid_bwd_fits() on the host)
+  const bool has_g2 = SIX || (!MID && a.g2 != nullptr), has_add_dy1 = SIX || (!MID && a.add_dy1 != nullptr), has_dy1_bits = !SIX && a.dy1_bits != nullptr;
   const uint8_t* kb0p = has_bits(0) ? a.a_bits[0] : reinterpret_cast<const uint8_t*>(a.x);
   float4 pxv[LB_U];                                    // prologue: rows / statistics of the layer norm in front
   float pmu[LB_U], prs[LB_U];
@@ -430,7 +438,7 @@ __global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a
   float4 addt[NT];                                     // add_dy1 in the accumulator layout
   const float* addp = has_add_dy1 ? a.add_dy1 : a.x;
 #pragma unroll
-  for (int rt = 0; rt < NT; ++rt) addt[rt] = SIX ? f4zero() : ld4(addp + (uint32_t)min(r0 + 16 * rt + j, R - 1) * (uint32_t)HUAL_D + (uint32_t)ecol);      // (SIX: requested in front of the last product - 12 registers less across the loop)
+  for (int rt = 0; rt < NT; ++rt) addt[rt] = (SIX || MID) ? f4zero() : ld4(addp + (uint32_t)min(r0 + 16 * rt + j, R - 1) * (uint32_t)HUAL_D + (uint32_t)ecol);      // (SIX: requested in front of the last product - 12 registers less across the loop)
   // rows -> operand planes of slot `k & 1` (with the operand's dropout', saved for the weight-gradient job)
   auto fill = [&](int k) {
     char* S = (k & 1) ? S1 : S0;
@@ -527,6 +535,18 @@ __global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a
       kbz[u] = bzp[row * 16 + (l32 >> 1)];
     }
   }
+  if (MID) {
+    tf_load_w(mp->wa, m->w[0], wave, lane);
+    tf_load_w(mp->wb, m->w[1], wave, lane);
+#pragma unroll
+    for (int rt = 0; rt < NT; ++rt) {
+      const uint32_t eo = (uint32_t)min(r0 + 16 * rt + j, R - 1) * (uint32_t)HUAL_D + (uint32_t)ecol;
+      mp->gate[rt] = ld4(m->gate + eo);
+      mp->val[rt] = ld4(m->val + eo);
+    }
+#pragma unroll
+    for (int u = 0; u < LB_U; ++u) zv[u] = f4zero();
+  }
   cb_barrier();
   HUAL_STAMP_K(4, 21);
   // ---- row phase: layer norm(s) backward.  dy = dy*g ; dx = rstd * (gv - mean(gv) - xhat * mean(gv * xhat))   (ln_bwd_kernel)
@@ -559,6 +579,7 @@ __global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a
     if (a.dz) {
       if (a.dz_bits && dr.enabled) dx = f4_select((kbz[u] >> (4 * (l32 & 1))) & 15u, make_float4(dx.x * dr.scale, dx.y * dr.scale, dx.z * dr.scale, dx.w * dr.scale));
       st4(a.dz + off, dx);
+      if (MID) zv[u] = dx;
     }
   }
   HUAL_STAMP_K(4, 22);
@@ -585,6 +606,13 @@ __global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a
     a.part[(size_t)tile_ * 4 * HUAL_D + e] = s;
   }
   HUAL_STAMP_K(4, 23);
+  return true;
+}
+template <bool PRE, int NT, bool SIX = false>
+__global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a, DropCfg drop) {
+  extern __shared__ __attribute__((aligned(16))) char lb_lds[];
+  float4 zv[LB_U];
+  ln_proj_bwd_body<PRE, NT, SIX, false>(a, drop, lb_lds, nullptr, nullptr, zv);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -594,9 +622,11 @@ __global__ __launch_bounds__(CB_THREADS) void ln_proj_bwd_kernel(LnProjBwdArgs a
 // two of the four SIMDs) - and reads its weight fragments straight from the L2-resident N images into registers, a step ahead:
 // no weight buffer in LDS, no DMA wait, no barrier for weights.  Accumulator rt of lane (j, g) = row 16 rt + j, columns
 // 16 wave + 4 g .. + 3.
-template <int NT>
-__global__ __launch_bounds__(CB_THREADS) void da_mid_bwd_kernel(DaMidBwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char dm_lds[];
+// FUSED (ln2_mid_bwd_kernel): behind ln_proj_bwd_body<MID> in the same launch - the rows of dZ1 arrive in registers (zv: what that body
+// stored to a.dz1, bit for bit), the first two weight images and the gate / value tiles have been requested there (mp)
+#define DM_LDS ((size_t)3 * DP_SLOT + (3 * DP_ROWS + 16 * DP_ROWS) * sizeof(float))
+template <int NT, bool FUSED>
+__device__ __forceinline__ void da_mid_bwd_body(const DaMidBwdArgs& a, char* dm_lds, DaMidPre<NT>* mp, const float4 (&zin)[3]) {
   char* P0 = dm_lds;
   char* P1 = P0 + DP_SLOT;
   char* P2 = P1 + DP_SLOT;
@@ -616,11 +646,12 @@ __global__ __launch_bounds__(CB_THREADS) void da_mid_bwd_kernel(DaMidBwdArgs a) 
   const int j = lane & 15, g = lane >> 4, ecol = 16 * wave + 4 * g;
 
   TfW wa, wb;
-  tf_load_w(wa, a.w[0], wave, lane);
+  if (FUSED) wa = mp->wa;
+  else tf_load_w(wa, a.w[0], wave, lane);
   {
     float4 zv[3];
 #pragma unroll
-    for (int u = 0; u < 3; ++u) zv[u] = ld4(a.dz1 + (size_t)min(r0 + grp + 16 * u, R - 1) * HUAL_D + col);
+    for (int u = 0; u < 3; ++u) zv[u] = FUSED ? zin[u] : ld4(a.dz1 + (size_t)min(r0 + grp + 16 * u, R - 1) * HUAL_D + col);
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
       const int lr = grp + 16 * u;
@@ -683,9 +714,15 @@ __global__ __launch_bounds__(CB_THREADS) void da_mid_bwd_kernel(DaMidBwdArgs a) 
 
   float4 T1[NT], T2[NT], U1[NT], U2[NT], U3[NT], U4[NT];
   // ---- d mha = dZ1 . Wd1^T ; bilinear backward (layers.py:110): d scores = d mha * val * gate * (1 - gate), d values = d mha * gate
-  tf_load_w(wb, a.w[1], wave, lane);
-  tile_ld(a.gate, U1);
-  tile_ld(a.val, U2);
+  if (FUSED) {
+    wb = mp->wb;
+#pragma unroll
+    for (int rt = 0; rt < NT; ++rt) { U1[rt] = mp->gate[rt]; U2[rt] = mp->val[rt]; }
+  } else {
+    tf_load_w(wb, a.w[1], wave, lane);
+    tile_ld(a.gate, U1);
+    tile_ld(a.val, U2);
+  }
   cb_barrier();
   tf_mma_lean<NT, DP_PLANE>(P1, wa, lane, accp);
   tf_load_w(wa, a.w[2], wave, lane);                   // (requests go in front of the epilogue's stores, here and below)
@@ -790,6 +827,27 @@ __global__ __launch_bounds__(CB_THREADS) void da_mid_bwd_kernel(DaMidBwdArgs a) 
   fold(T2, ainv0, true);
 #pragma unroll
   for (int rt = 0; rt < NT; ++rt) save(a.d_xatt, rt, T2[rt]);
+}
+template <int NT>
+__global__ __launch_bounds__(CB_THREADS) void da_mid_bwd_kernel(DaMidBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char dm_lds[];
+  const float4 zin[3] = {};
+  da_mid_bwd_body<NT, false>(a, dm_lds, nullptr, zin);
+}
+// dense_2^T + layer_norm_2 backward (one product) and the gated middle behind it, one launch: both are row-local on the same tiles of the
+// same grid.  dZ1 and d res are stored as before (the weight-gradient launch and the six-product launch read them); the middle's copy
+// of dZ1 stays on the chip, its first loads fly under the row phase.  Both bodies work from the LDS base (operand slots beyond 64 KB
+// are out of reach of a ds instruction's immediate offset: every fragment address took a register, and the kernel spilled).  The
+// middle fills its slot 1 first - the first body's slot 1, which its one product never touches - so the middle's own first barrier is
+// the only one between the two: when a wave passes it every wave is through the first body's parameter sums (LDS beyond slot 1)
+template <int NT>
+__global__ __launch_bounds__(CB_THREADS) void ln2_mid_bwd_kernel(LnProjBwdArgs a, DaMidBwdArgs m, DropCfg drop) {
+  extern __shared__ __attribute__((aligned(16))) char lm_lds[];
+  DaMidPre<NT> mp;
+  float4 zv[LB_U];
+  if (!ln_proj_bwd_body<false, NT, false, true>(a, drop, lm_lds, &m, &mp, zv)) return;
+  static_assert(DP_SLOT == 2 * LB_ROWS * 256, "the middle's slot 1 must be the first body's slot 1");
+  da_mid_bwd_body<NT, true>(m, lm_lds, &mp, zv);
 }
 
 #if defined(HUAL_STAMPS) && (HUAL_STAMPS == 1 || (HUAL_STAMPS >= 4 && HUAL_STAMPS <= 6))
@@ -937,7 +995,7 @@ static bool ln_proj_bwd_six(const LnProjBwdArgs& a) {
   return true;
 }
 
-int launch_ln_proj_bwd(const LnProjBwdArgs& a, const DropCfg& drop, hipStream_t s) {
+static int check_ln_proj_bwd(const LnProjBwdArgs& a) {
   HUAL_REQUIRE(a.nsteps >= 1 && a.nsteps <= HUAL_LNBWD_MAX && a.R > 0, "ln_proj_bwd: step count / rows");
   HUAL_REQUIRE(a.MT >= 1 && a.MT <= LB_ROWS, "ln_proj_bwd: MT must be 1..48");
   HUAL_REQUIRE(a.x && a.mean && a.rstd && a.g1 && a.dx && a.part, "ln_proj_bwd: null tensor");
@@ -949,10 +1007,20 @@ int launch_ln_proj_bwd(const LnProjBwdArgs& a, const DropCfg& drop, hipStream_t 
   }
   HUAL_REQUIRE(!a.g2 || any1, "ln_proj_bwd: second layer norm without a product");
   HUAL_REQUIRE(!a.pre_x || (!a.g2 && !a.add1 && a.pre_mean && a.pre_rstd && a.pre_g && a.pre_dy), "ln_proj_bwd: layer-norm prologue");
-  const size_t lds = (size_t)4 * LB_ROWS * 256 + 8 * 4 * 32 * 16 + 2 * LB_ROWS * sizeof(float);
+  return 0;
+}
+static void ln_proj_bwd_work(const LnProjBwdArgs& a, double& flops, double& bytes) {
   const double rows = (double)a.R;
-  const double flops = 2.0 * rows * HUAL_D * HUAL_D * a.nsteps;
-  const double bytes = 4.0 * (rows * HUAL_D * ((a.pre_x ? 7.0 : 4.0) + a.nsteps) + (double)a.nsteps * HUAL_D * HUAL_D);
+  flops += 2.0 * rows * HUAL_D * HUAL_D * a.nsteps;
+  bytes += 4.0 * (rows * HUAL_D * ((a.pre_x ? 7.0 : 4.0) + a.nsteps) + (double)a.nsteps * HUAL_D * HUAL_D);
+}
+
+int launch_ln_proj_bwd(const LnProjBwdArgs& a, const DropCfg& drop, hipStream_t s) {
+  int rc = check_ln_proj_bwd(a);
+  if (rc) return rc;
+  const size_t lds = LB_LDS;
+  double flops = 0.0, bytes = 0.0;
+  ln_proj_bwd_work(a, flops, bytes);
   const dim3 grid(xcd_clip_grid(a.R, a.Nv, a.MT));
   const bool six = ln_proj_bwd_six(a);
 #define LN_BWD_NT(NT)                                                                                                   \
@@ -972,19 +1040,55 @@ int launch_ln_proj_bwd(const LnProjBwdArgs& a, const DropCfg& drop, hipStream_t 
   return 0;
 }
 
-int launch_da_mid_bwd(const DaMidBwdArgs& a, hipStream_t s) {
+static int check_da_mid_bwd(const DaMidBwdArgs& a) {
   HUAL_REQUIRE(a.dz1 && a.gate && a.val && a.sg && a.xg && a.sv && a.xv && a.R > 0, "da_mid_bwd: null / empty");
   HUAL_REQUIRE(a.MT >= 1 && a.MT <= DP_ROWS, "da_mid_bwd: MT must be 1..48");
   for (int k = 0; k < 10; ++k) HUAL_REQUIRE(a.w[k] != nullptr, "da_mid_bwd: null weight image");
   HUAL_REQUIRE(a.d_sc && a.d_val && a.d_ln1a && a.d_g && a.dz_sg && a.dz_xg && a.d_sv && a.d_xv && a.d_satt && a.d_xatt, "da_mid_bwd: null output");
-  const size_t lds = (size_t)3 * DP_SLOT + (3 * DP_ROWS + 16 * DP_ROWS) * sizeof(float);
+  return 0;
+}
+static void da_mid_bwd_work(const DaMidBwdArgs& a, double& flops, double& bytes) {
   const double rows = (double)a.R;
-  const double flops = 10.0 * 2.0 * rows * HUAL_D * HUAL_D, bytes = 4.0 * (rows * HUAL_D * 17.0 + 10.0 * HUAL_D * HUAL_D);
+  flops += 10.0 * 2.0 * rows * HUAL_D * HUAL_D;
+  bytes += 4.0 * (rows * HUAL_D * 17.0 + 10.0 * HUAL_D * HUAL_D);
+}
+
+int launch_da_mid_bwd(const DaMidBwdArgs& a, hipStream_t s) {
+  int rc = check_da_mid_bwd(a);
+  if (rc) return rc;
+  const size_t lds = DM_LDS;
+  double flops = 0.0, bytes = 0.0;
+  da_mid_bwd_work(a, flops, bytes);
   const dim3 grid(xcd_clip_grid(a.R, a.Nv, a.MT));
   switch (cdiv(a.MT, 16)) {      // row tiles per workgroup
     case 1: { HUAL_DYN_LDS(da_mid_bwd_kernel<1>, 160 * 1024); HUAL_LAUNCH(flops, bytes, da_mid_bwd_kernel<1>, grid, dim3(CB_THREADS), lds, s, a); break; }
     case 2: { HUAL_DYN_LDS(da_mid_bwd_kernel<2>, 160 * 1024); HUAL_LAUNCH(flops, bytes, da_mid_bwd_kernel<2>, grid, dim3(CB_THREADS), lds, s, a); break; }
     default: { HUAL_DYN_LDS(da_mid_bwd_kernel<3>, 160 * 1024); HUAL_LAUNCH(flops, bytes, da_mid_bwd_kernel<3>, grid, dim3(CB_THREADS), lds, s, a); break; }
+  }
+  HUAL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+bool ln2_mid_bwd_fits(const LnProjBwdArgs& a, const DaMidBwdArgs& m) {
+  return a.nsteps == 1 && !a.pre_x && !a.g2 && !a.add_dy1 && a.dst[0] == 0 && a.dz && a.dz == m.dz1 && a.R == m.R && a.Nv == m.Nv && a.MT == m.MT;
+}
+
+int launch_ln2_mid_bwd(const LnProjBwdArgs& a, const DaMidBwdArgs& m, const DropCfg& drop, hipStream_t s) {
+  int rc = check_ln_proj_bwd(a);
+  if (rc) return rc;
+  if ((rc = check_da_mid_bwd(m))) return rc;
+  HUAL_REQUIRE(ln2_mid_bwd_fits(a, m), "ln2_mid_bwd: one product into one layer norm whose dz is the middle's dz1, on the same row tiles");
+  static_assert(LB_ROWS == DP_ROWS, "the two bodies share their row tiles");
+  const size_t lds = LB_LDS > DM_LDS ? LB_LDS : DM_LDS;
+  double flops = 0.0, bytes = 0.0;
+  ln_proj_bwd_work(a, flops, bytes);
+  da_mid_bwd_work(m, flops, bytes);
+  bytes -= 4.0 * (double)a.R * HUAL_D;      // dz1 is not read back
+  const dim3 grid(xcd_clip_grid(a.R, a.Nv, a.MT));
+  switch (cdiv(a.MT, 16)) {      // row tiles per workgroup
+    case 1: { HUAL_DYN_LDS(ln2_mid_bwd_kernel<1>, 160 * 1024); HUAL_LAUNCH(flops, bytes, ln2_mid_bwd_kernel<1>, grid, dim3(CB_THREADS), lds, s, a, m, drop); break; }
+    case 2: { HUAL_DYN_LDS(ln2_mid_bwd_kernel<2>, 160 * 1024); HUAL_LAUNCH(flops, bytes, ln2_mid_bwd_kernel<2>, grid, dim3(CB_THREADS), lds, s, a, m, drop); break; }
+    default: { HUAL_DYN_LDS(ln2_mid_bwd_kernel<3>, 160 * 1024); HUAL_LAUNCH(flops, bytes, ln2_mid_bwd_kernel<3>, grid, dim3(CB_THREADS), lds, s, a, m, drop); break; }
   }
   HUAL_CHECK_HIP(hipGetLastError());
   return 0;

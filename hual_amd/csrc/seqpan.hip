@@ -141,6 +141,26 @@ struct Ctx {
     if (active) colsum.push_back(cj);
     if (live()) chk(launch_ln_proj_bwd(a, drop, stream));
   }
+  // the one-product form with the dual attention's gated middle behind it (dablock.h): one launch when the whole step runs and the two
+  // work on the same row tiles, else the two launches.  Same scratch buffer, same reduction job either way
+  void ln2_mid_bwd(const LnProjBwdArgs& a0, const DaMidBwdArgs& m0, float* dg1, float* db1) {
+    LnProjBwdArgs a = a0;
+    DaMidBwdArgs m = m0;
+    a.MT = ln_proj_bwd_rows(a.R, a.Nv);
+    m.MT = da_post_rows(m.R, m.Nv);
+    const int nblk = ln_proj_bwd_blocks(a.R, a.Nv);
+    a.part = buf("part." + std::to_string(part_seq++), (size_t)nblk * 4, HUAL_D);
+    ColsumJob cj{};
+    cj.src = a.part; cj.nblk = nblk; cj.nvec = 4;
+    cj.dst[0] = dg1; cj.dst[1] = db1;
+    if (active) colsum.push_back(cj);
+    if (!live()) return;
+#ifndef HUAL_NO_DA_BWD_FUSE      // (A/B builds of the unfused launch sequence: build.py --define)
+    if (sel_stage < 0 && ln2_mid_bwd_fits(a, m)) { chk(launch_ln2_mid_bwd(a, m, drop, stream)); return; }
+#endif
+    chk(launch_ln_proj_bwd(a, drop, stream));
+    if (ok()) chk(launch_da_mid_bwd(m, stream));
+  }
   // (unpack: the char-CNN filter-gradient unpack rides in the last of these launches - it has to follow the weight-gradient launch)
   void flush_colsum(const EmbedUnpack* unpack = nullptr) {
     for (size_t i = 0; i < colsum.size() && !dry && ok(); i += HUAL_COLSUM_MAX_JOBS) {   // (whatever stages ran)
@@ -1096,14 +1116,13 @@ int backward_graph(Ctx& c, const hual_batch* bt, const hual_labels* lab, const h
       else { lb.A[0] = dx; lb.a_bits[0] = c.bits(t + ".kb4", R); lb.a_save[0] = dz2; }
       lb.dy1_bits = c.bits(t + ".kb3", R); lb.x = res; lb.mean = mean2; lb.rstd = rstd2; lb.g1 = c.p(d.ln2.g); lb.add1 = dx;
       lb.dx = d_res; lb.dz = dz1; lb.dz_bits = c.bits(t + ".kb2", R); lb.R = R; lb.Nv = Nv; lb.drop_row0 = 0;
-      c.ln_proj_bwd(lb, c.g(d.ln2.g), c.g(d.ln2.b), nullptr, nullptr);
       DaMidBwdArgs mb{};
       mb.dz1 = dz1; mb.gate = gate; mb.val = val; mb.sg = sg; mb.xg = xg; mb.sv = sv; mb.xv = xv;
       const size_t wo[10] = {d.dense1.k, d.bl1_d1, d.bl2_d1, d.bl1_d2, d.bl2_d2, d.guided.k, d.s_gate.k, d.x_gate.k, d.s_dense.k, d.x_dense.k};
       for (int k = 0; k < 10; ++k) mb.w[k] = c.nimg(wo[k]);      // register-resident weights (N images)
       mb.d_sc = d_sc; mb.d_val = d_val; mb.d_ln1a = d_ln1a; mb.d_g = d_g; mb.dz_sg = dz_sg; mb.dz_xg = dz_xg; mb.d_sv = d_sv; mb.d_xv = d_xv;
-      mb.d_satt = d_satt; mb.d_xatt = d_xatt; mb.R = R; mb.Nv = Nv; mb.MT = da_post_rows(R, Nv);
-      if (c.live()) c.chk(launch_da_mid_bwd(mb, c.stream));
+      mb.d_satt = d_satt; mb.d_xatt = d_xatt; mb.R = R; mb.Nv = Nv;
+      c.ln2_mid_bwd(lb, mb, c.g(d.ln2.g), c.g(d.ln2.b));
     }
     // the four attentions
     float* dq_self = c.act(dt + ".q_self");
