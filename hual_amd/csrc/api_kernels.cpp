@@ -5,6 +5,7 @@
 #include "mproj.h"
 #include "attn.h"
 #include "heads.h"
+#include "optim.h"
 #include "rowops.h"
 
 namespace hual {
@@ -133,6 +134,19 @@ int hual_span_argmax(const float* start_logits, const float* end_logits, const f
   a.logit[0] = const_cast<float*>(start_logits); a.logit[1] = const_cast<float*>(end_logits); a.vmask = vmask;
   a.start_index = start_index; a.end_index = end_index; a.inv_batch = 1.0f / (float)B;
   return launch_heads(a, B, T, (hipStream_t)stream);
+}
+
+int hual_adamw_clip_step_ema(float* params, const float* grads, float* adam_m, float* adam_v, const float* decay,
+                             uint64_t n_padded, const float* lr, float clip_norm, float grad_prescale, float* sqnorm,
+                             uint32_t* rng_state, int64_t* cursor, const int64_t* spans, int64_t* bank, int span_words, int sel_inc,
+                             int bank_inc, float* ema, uint32_t* ema_count, float ema_decay, int ema_warmup, void* stream) {
+  HUAL_REQUIRE(!(ema == nullptr && ema_count != nullptr), "hual_adamw_clip_step_ema: ema_count without ema");
+  HUAL_REQUIRE(!(ema != nullptr && ema_count == nullptr), "hual_adamw_clip_step_ema: ema without ema_count");
+  HUAL_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "hual_adamw_clip_step_ema: ema_decay must lie in [0, 1)");
+  HUAL_REQUIRE(span_words >= 0 && sel_inc >= 0 && bank_inc >= 0, "hual_adamw_clip_step_ema: negative increments");
+  AdamArgs a{params, const_cast<float*>(grads), adam_m, adam_v, decay, (size_t)n_padded, lr, clip_norm, grad_prescale, sqnorm,
+             rng_state, cursor, spans, bank, span_words, sel_inc, bank_inc, ema, ema_count, ema_decay, ema_warmup != 0};
+  return launch_adamw(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

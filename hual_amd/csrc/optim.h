@@ -18,6 +18,10 @@ struct AdamArgs {
   // optional: the epoch loop's device-side position (hual_loop_step): block 0 copies span_words 8-byte words (the step's predicted
   // spans) to bank + cursor[1], then cursor[0] += sel_inc (ids consumed), cursor[1] += bank_inc
   int64_t* cursor; const int64_t* spans; int64_t* bank; int span_words, sel_inc, bank_inc;
+  // optional (both or neither): the averaged weights.  ema: flat shadow of p (same layout, n floats), updated from the new parameter
+  // values in the same launch: s <- s + (1 - d_k) (p_new - s), d_k = min(ema_decay, (1 + k) / (10 + k)) with ema_warmup, ema_decay
+  // without; ema_count: device u32, the number k of updates so far, bumped by the sqnorm launch and read by the adamw launch
+  float* ema = nullptr; uint32_t* ema_count = nullptr; float ema_decay = 0.f; int ema_warmup = 0;
 };
 int launch_adamw(const AdamArgs& a, hipStream_t s);
 // p[0..n) = 0 with a kernel (no memset node inside captured graphs)

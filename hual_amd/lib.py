@@ -103,6 +103,7 @@ def load():
     lib.hual_adamw_clip_step.argtypes = [vp, vp, vp, vp, vp, u64, vp, f32, f32, vp, vp]
     lib.hual_adamw_clip_step_rng.argtypes = [vp, vp, vp, vp, vp, u64, vp, f32, f32, vp, vp, vp]
     lib.hual_adamw_clip_step_loop.argtypes = [vp, vp, vp, vp, vp, u64, vp, f32, f32, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.hual_adamw_clip_step_ema.argtypes = [vp, vp, vp, vp, vp, u64, vp, f32, f32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, f32, i32, vp]
     lib.hual_assemble_batch_cursor.argtypes = [P(hual_dataset), vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_xgmi_flags_bytes.restype = ctypes.c_uint64
     lib.hual_xgmi_flags_alloc.argtypes = [P(vp)]

@@ -12,10 +12,13 @@ eval_test_save :69-110):
     sess.run(match_scores, feed)                          model.forward(...)['match_scores']
     sess.run([train_op, loss, start_index, end_index])    model.train_step(feeds, lr, drop_rate)
     tf.train.Saver                                        model.state_dict() / load_state_dict()  (TF variable names)
+    tf.train.ExponentialMovingAverage (not in the         train.ema_decay: a shadow of the parameters updated inside the optimizer
+      reference; the QANet family evaluates on it)          launch, model.use_weights('ema') to evaluate on it
 
 All compute runs in libhual_seqpan.so (hand-written HIP for gfx950) through ctypes; PyTorch only owns device
 memory and streams.  There is no CPU fallback: without the library or a GPU this module raises.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -52,8 +55,25 @@ def cfg_from_configs(configs, num_words):
         finetune_word_emb=1 if _get(configs, 'model.finetune_word_emb', False) else 0)
 
 
+EMA_SUFFIX = '/ExponentialMovingAverage'      # TensorFlow's own name of a variable's average: <variable name>/ExponentialMovingAverage
+EMA_COUNT = 'ExponentialMovingAverage/num_updates'
+
+
+def ema_settings(configs, ema_decay=None, ema_warmup=None):
+    """(decay, warmup) of train.ema_decay / train.ema_warmup: decay 0.0 = off (key absent or 0), warm-up on by default.  The keys are not
+    part of hual_cfg: a model built from the struct takes them as keyword arguments."""
+    if ema_decay is None:
+        ema_decay = 0.0 if isinstance(configs, lib.hual_cfg) else (_get(configs, 'train.ema_decay', 0.0) or 0.0)
+    if ema_warmup is None:
+        ema_warmup = True if isinstance(configs, lib.hual_cfg) else _get(configs, 'train.ema_warmup', True)
+    ema_decay = float(ema_decay)
+    if not 0.0 <= ema_decay < 1.0:
+        raise lib.HualError('train.ema_decay must lie in [0, 1) (0 or absent: no averaged weights), got %r' % ema_decay)
+    return ema_decay, bool(ema_warmup)
+
+
 class SeqPAN:
-    def __init__(self, configs, word_vectors, device='cuda:0', seed=12345, rng_seed=12345):
+    def __init__(self, configs, word_vectors, device='cuda:0', seed=12345, rng_seed=12345, ema_decay=None, ema_warmup=None):
         if not torch.cuda.is_available():
             raise lib.HualError('SeqPAN needs a GPU: the HIP path has no CPU fallback')
         lib.load()
@@ -70,6 +90,12 @@ class SeqPAN:
             self.word_table = self.params[e['offset']:e['offset'] + e['size']].view(*e['shape'])
         else:
             self.word_table = torch.from_numpy(wv).to(self.device).contiguous()
+        # train.ema_decay in (0, 1): averaged weights - a shadow of the flat buffer (word table of a fine-tuning model included) that
+        # every optimizer launch updates from the new parameter values, and the device-side count of those updates
+        self.ema_decay, self.ema_warmup = ema_settings(configs, ema_decay, ema_warmup)
+        self.ema = self.params.clone() if self.ema_decay > 0.0 else None
+        self.ema_count = torch.zeros(1, dtype=torch.int32, device=self.device) if self.ema_decay > 0.0 else None
+        self.weights = 'raw'                                      # what forward() reads: use_weights()
         self.grads = torch.zeros_like(self.params)
         self.adam_m = torch.zeros_like(self.params)
         self.adam_v = torch.zeros_like(self.params)
@@ -93,10 +119,49 @@ class SeqPAN:
     def state_dict(self):
         return self.table.unpack(self.params.detach().cpu().numpy())
 
+    def ema_state_dict(self):
+        """the averaged weights as <TF name>/ExponentialMovingAverage -> array, and the update count"""
+        self._need_ema('ema_state_dict')
+        d = {k + EMA_SUFFIX: v for k, v in self.table.unpack(self.ema.detach().cpu().numpy()).items()}
+        d[EMA_COUNT] = self.ema_count.cpu().numpy().view(np.uint32).copy()
+        return d
+
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise lib.HualError('%s: this model keeps no averaged weights (train.ema_decay is absent or 0)' % what)
+
+    @contextlib.contextmanager
+    def use_weights(self, which):
+        """forward() inside the block reads the averaged weights ('ema') or the parameters ('raw'): the pointer handed to the launches
+        changes, nothing is copied; the word table of a fine-tuning model is the matching slice of whichever buffer is read.  The
+        training step (Trainer) always works on the parameters."""
+        if which not in ('ema', 'raw'):
+            raise lib.HualError("use_weights: 'ema' or 'raw', got %r" % (which,))
+        self._need_ema('use_weights')
+        prev, self.weights = self.weights, which
+        try:
+            yield self
+        finally:
+            self.weights = prev
+
+    def _read_weights(self):
+        """(flat buffer, word table) that forward() reads"""
+        if self.weights != 'ema':
+            return self.params, self.word_table
+        if not self.finetune_word_emb:
+            return self.ema, self.word_table
+        e = self.table.by_name[WORD_TABLE]
+        return self.ema, self.ema[e['offset']:e['offset'] + e['size']].view(*e['shape'])
+
     def load_state_dict(self, named):
         """named: TF name -> array.  A fine-tuning model (model.finetune_word_emb) keeps its current word table when `named` has
         none (a frozen model's checkpoint: fine-tuning starts from GloVe); a frozen model refuses a checkpoint that holds a trained
-        table - dropping it would change the predictions."""
+        table - dropping it would change the predictions.  Averaged weights (<name>/ExponentialMovingAverage and the update count) are
+        restored into a model that keeps them and ignored by one that does not; without them the shadow restarts from the loaded
+        parameters with a count of 0."""
+        avg = {k[:-len(EMA_SUFFIX)]: v for k, v in named.items() if k.endswith(EMA_SUFFIX)}
+        count = named.get(EMA_COUNT)
+        named = {k: v for k, v in named.items() if not k.endswith(EMA_SUFFIX) and k != EMA_COUNT}
         if WORD_TABLE in named and not self.finetune_word_emb:
             raise lib.HualError('the checkpoint holds a trained %s: load it into a model with model.finetune_word_emb: true'
                                 % WORD_TABLE)
@@ -104,6 +169,15 @@ class SeqPAN:
             named = dict(named)
             named[WORD_TABLE] = self.word_table.detach().cpu().numpy()
         self.params.copy_(torch.from_numpy(self.table.pack(named)).to(self.device))
+        if self.ema is not None:
+            if avg and count is not None:
+                if self.finetune_word_emb and WORD_TABLE not in avg:      # (a frozen run's averages: the table's starts where the table does)
+                    avg[WORD_TABLE] = self.word_table.detach().cpu().numpy()
+                self.ema.copy_(torch.from_numpy(self.table.pack(avg)).to(self.device))
+                self.ema_count.copy_(torch.from_numpy(np.asarray(count).reshape(1).astype(np.uint32).view(np.int32)))
+            else:
+                self.ema.copy_(self.params)
+                self.ema_count.zero_()
 
     def grads_dict(self):
         return self.table.unpack(self.grads.detach().cpu().numpy())
@@ -211,8 +285,9 @@ class SeqPAN:
         o, lt, ost = self._outputs(B, T, labels is not None)
         lab_st, lab_keep = (None, None) if labels is None else self._labels(*labels)
         opts = _opts if _opts is not None else self._opts(drop_rate)
+        flat, table = self._read_weights()
         lib.check(lib.load().hual_seqpan_forward(
-            ctypes.byref(self.cfg), lib.ptr(self.params), lib.ptr(self.word_table), ctypes.byref(bt),
+            ctypes.byref(self.cfg), lib.ptr(flat), lib.ptr(table), ctypes.byref(bt),
             None if lab_st is None else ctypes.byref(lab_st), ctypes.byref(ost), ctypes.byref(opts), lib.ptr(ws),
             ws.numel(), lib.stream_ptr()))
         if lt is not None:
@@ -230,8 +305,9 @@ class SeqPAN:
         bt, keep, lab_st, lab_keep, opts = self._last
         assert lab_st is not None, 'backward() needs forward(labels=...)'
         ws = self._ws
+        flat, table = self._read_weights()      # (inside use_weights('ema'): the gradient at the averaged weights, like the forward)
         lib.check(lib.load().hual_seqpan_backward(
-            ctypes.byref(self.cfg), lib.ptr(self.params), lib.ptr(self.word_table), ctypes.byref(bt),
+            ctypes.byref(self.cfg), lib.ptr(flat), lib.ptr(table), ctypes.byref(bt),
             ctypes.byref(lab_st), ctypes.byref(opts), lib.ptr(self.grads), lib.ptr(ws), ws.numel(), lib.stream_ptr()))
         return self.grads
 
@@ -243,11 +319,31 @@ class SeqPAN:
         elif self.lr_value != float(lr):
             self.lr.fill_(float(lr))
             self.lr_value = float(lr)
-        lib.check(lib.load().hual_adamw_clip_step(
-            lib.ptr(self.params), lib.ptr(self.grads), lib.ptr(self.adam_m), lib.ptr(self.adam_v), lib.ptr(self.decay),
-            self.params.numel(), lib.ptr(self.lr), float(self.cfg.clip_norm), float(grad_prescale), lib.ptr(self.sqnorm),
-            lib.stream_ptr()))
+        self.optimizer_launch(grad_prescale, rng=False)
         self.global_step += 1
+
+    def optimizer_launch(self, grad_prescale, rng=True, loop=None):
+        """the two optimizer launches of a step on the current stream.  rng: the Philox offset of the dropout stream advances in the same
+        launch (rng_state[2] += 1); loop = (cursor, spans, bank, span_words, sel_inc, bank_inc): the epoch loop's device-side position
+        does too.  A model with averaged weights goes through hual_adamw_clip_step_ema whatever else rides along: the shadow and its
+        counter are arguments of the same two launches, so eager steps, captured steps and every loop update it alike."""
+        l = lib.load()
+        head = (lib.ptr(self.params), lib.ptr(self.grads), lib.ptr(self.adam_m), lib.ptr(self.adam_v), lib.ptr(self.decay),
+                self.params.numel(), lib.ptr(self.lr), float(self.cfg.clip_norm), float(grad_prescale), lib.ptr(self.sqnorm))
+        rs = lib.ptr(self.rng_state) if rng else None
+        if self.ema is not None:
+            cursor, spans, bank, nsp, sel_inc, bank_inc = loop if loop is not None else (None, None, None, 0, 0, 0)
+            lib.check(l.hual_adamw_clip_step_ema(*head, rs, lib.ptr(cursor), lib.ptr(spans), lib.ptr(bank), nsp, sel_inc, bank_inc,
+                                                 lib.ptr(self.ema), lib.ptr(self.ema_count), self.ema_decay, int(self.ema_warmup),
+                                                 lib.stream_ptr()))
+        elif loop is not None:
+            cursor, spans, bank, nsp, sel_inc, bank_inc = loop
+            lib.check(l.hual_adamw_clip_step_loop(*head, rs, lib.ptr(cursor), lib.ptr(spans), lib.ptr(bank), nsp, sel_inc, bank_inc,
+                                                  lib.stream_ptr()))
+        elif rng:
+            lib.check(l.hual_adamw_clip_step_rng(*head, rs, lib.stream_ptr()))
+        else:
+            lib.check(l.hual_adamw_clip_step(*head, lib.stream_ptr()))
 
     def train_step(self, video_inputs, video_seq_len, word_ids, char_ids, y1, y2, match_labels, inner_labels, lr,
                    drop_rate):

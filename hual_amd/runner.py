@@ -8,11 +8,14 @@
     main.py --mode infer_trainset -> results/<task>/<suffix>.pkl   Runner.infer_trainset(path)
     runner_utils.train_epoch / test_epoch (IoU bookkeeping)  Runner.train_epoch / Runner.test_epoch
     tf.train.Saver                                           numpy .npz keyed by the TF variable names
+    (neither has)                                            train.ema_decay: evaluation and best-epoch selection on averaged weights;
+                                                             Runner.save_state / load_state / train(resume=...): a run split across visits
 
 Data: the records the reference's dataset_gen leaves (utils/data_gen.py:98-125: vid, duration, v_len, words, w_ids, c_ids,
 s_ind, e_ind) + {vid: float32 [n, vdim]} features; both go to HBM once (hual_amd/dataset.py).  Python `random` is seeded here
 (the reference leaves the epoch order unseeded).  There is no CPU fallback.
 """
+import contextlib
 import logging
 import os
 import pickle
@@ -27,6 +30,8 @@ from . import dist as hdist
 from .dataset import DeviceDataset
 from .model import SeqPAN
 from .params import WORD_TABLE
+
+STATE_FORMAT = 1      # Runner.save_state
 from .train import Trainer
 
 
@@ -57,6 +62,17 @@ class Runner:
         self.world, self.rank = hdist.world_size(), hdist.rank()
         self.trainer = Trainer(self.model, world=self.world, use_graph=True)     # per-shape step graphs (Trainer.set_batch_device)
         self.clips_per_s = 0.0
+        # where train() stands: the next epoch, the epoch count its lr schedule runs over (main.py:61), the best R1@0.7 so far and
+        # its log lines - part of save_state
+        self.progress = dict(epoch=0, epochs=int(configs['train'].get('epochs', 1)), best=-1.0, best_lines=None)
+
+    def _weights(self, weights):
+        """context of an evaluation pass: the averaged weights by default where the model keeps them (train.ema_decay), else the raw ones"""
+        if self.model.ema is None:
+            if weights not in (None, 'raw'):
+                raise lib.HualError("weights=%r: this run keeps no averaged weights (train.ema_decay is absent or 0)" % (weights,))
+            return contextlib.nullcontext()
+        return self.model.use_weights(weights or 'ema')
 
     # ------------------------------------------------------------------ runner_utils.train_epoch (:139-159)
     @staticmethod
@@ -116,7 +132,12 @@ class Runner:
         return al.iou_metrics(ious)
 
     # ------------------------------------------------------------------ runner_utils.test_epoch (:161-176)
-    def test_epoch(self, dataset=None):
+    def test_epoch(self, dataset=None, weights=None):
+        """weights: 'ema' (the default with train.ema_decay) or 'raw'"""
+        with self._weights(weights):
+            return self._test_epoch(dataset)
+
+    def _test_epoch(self, dataset):
         ds = dataset or self.test_set
         ious = []
         for k, lo in enumerate(range(0, len(ds), self.batch_size)):
@@ -132,7 +153,12 @@ class Runner:
         return al.iou_metrics(ious)
 
     # ------------------------------------------------------------------ R@k evaluation (top-k proposals after temporal NMS)
-    def evaluate(self, dataset=None, k=5, nms_iou=0.5, max_len=0, return_proposals=False):
+    def evaluate(self, dataset=None, k=5, nms_iou=0.5, max_len=0, return_proposals=False, weights=None):
+        """weights: 'ema' (the default with train.ema_decay) or 'raw'; everything else: _evaluate"""
+        with self._weights(weights):
+            return self._evaluate(dataset, k, nms_iou, max_len, return_proposals)
+
+    def _evaluate(self, dataset, k, nms_iou, max_len, return_proposals):
         """R1 and R<k> at IoU 0.3 / 0.5 / 0.7 and mIoU (percent) of the k best spans per clip after greedy temporal NMS
         (hual_span_topk).  Batches and ranks as test_epoch; the proposals of all batches collect on the device and come back in one
         transfer.  R1 and mIoU are those of the first proposal, which is the span test_epoch scores.  return_proposals: also a list
@@ -186,30 +212,51 @@ class Runner:
         return res, props
 
     # ------------------------------------------------------------------ main.py --mode train (:50-78)
-    def train(self, epochs=None):
-        epochs = int(epochs if epochs is not None else self.configs['train']['epochs'])
-        best, best_lines = -1.0, None
-        for epoch in range(epochs):
-            self.log.info('Epoch {}|{}:'.format(epoch, epochs))
-            cur_lr = self.lr * (1.0 - epoch / epochs)             # main.py:61
-            r = self.train_epoch(cur_lr)
-            train_line = 'TRAIN:\t{:.2f}\t{:.2f}\t{:.2f}\t{:.2f}\t'.format(*r)
-            self.log.info(train_line + '({:.0f} clips/s)'.format(self.clips_per_s))
-            test_line = ''
-            r1i7 = r[2]
-            if self.test_set is not None:
-                t = self.test_epoch()
-                test_line = 'TEST:\t{:.2f}\t{:.2f}\t{:.2f}\t{:.2f}\t'.format(*t)
-                self.log.info(test_line)
-                r1i7 = t[2]
-            if r1i7 > best:                                       # main.py:71-75
-                best = r1i7
-                if self.rank == 0:
-                    self.save(os.path.join(self.ckpt_dir, 'best_SeqPAN.npz'))
-                best_lines = '\n' + train_line + '\n' + test_line
+    def cur_lr(self):
+        """the learning rate of the next epoch (main.py:61)"""
+        pr = self.progress
+        return self.lr * (1.0 - pr['epoch'] / pr['epochs'])
+
+    def run_one_epoch(self, state_path=None):
+        """the body of main.py's epoch loop at self.progress: train, test, keep the best R1@0.7 (on the averaged weights where the run
+        keeps them), move on; with state_path, rank 0 then writes the training state"""
+        pr = self.progress
+        self.log.info('Epoch {}|{}:'.format(pr['epoch'], pr['epochs']))
+        r = self.train_epoch(self.cur_lr())
+        train_line = 'TRAIN:\t{:.2f}\t{:.2f}\t{:.2f}\t{:.2f}\t'.format(*r)
+        self.log.info(train_line + '({:.0f} clips/s)'.format(self.clips_per_s))
+        test_line = ''
+        r1i7 = r[2]
+        if self.test_set is not None:
+            t = self.test_epoch()
+            test_line = 'TEST:\t{:.2f}\t{:.2f}\t{:.2f}\t{:.2f}\t'.format(*t)
+            self.log.info(test_line)
+            r1i7 = t[2]
+        if r1i7 > pr['best']:                                     # main.py:71-75
+            pr['best'] = r1i7
+            if self.rank == 0:
+                self.save(os.path.join(self.ckpt_dir, 'best_SeqPAN.npz'))
+            pr['best_lines'] = '\n' + train_line + '\n' + test_line
+        pr['epoch'] += 1
+        if state_path is not None and self.rank == 0:
+            self.save_state(state_path)
+
+    def train(self, epochs=None, resume=None, state_path=None):
+        """resume: a file of save_state to continue from (read by every rank); state_path: where rank 0 writes the state after every
+        epoch (may be the same file)"""
+        pr = self.progress
+        if resume is not None:
+            self.load_state(resume)
+            if epochs is not None and int(epochs) != pr['epochs']:
+                raise lib.HualError('%s was written by a run over %d epochs: continuing it over %d would change the learning rate '
+                                    'schedule' % (resume, pr['epochs'], int(epochs)))
+        else:
+            pr.update(epoch=0, epochs=int(epochs if epochs is not None else self.configs['train']['epochs']), best=-1.0, best_lines=None)
+        while pr['epoch'] < pr['epochs']:
+            self.run_one_epoch(state_path)
         self.log.info('\n\nHighest R1i7 epoch\n')
-        self.log.info(best_lines)
-        return best
+        self.log.info(pr['best_lines'])
+        return pr['best']
 
     def test(self):
         hdist.barrier()                                            # rank 0 wrote the checkpoint
@@ -219,14 +266,16 @@ class Runner:
         return t
 
     # ------------------------------------------------------------------ main.py --mode infer_trainset (:99-111)
-    def infer_trainset(self, path=None, mc_dropout=None, load_best=True):
-        """results/<task>/<suffix>.pkl of runner_utils.py:103-104.  mc_dropout=None: as the reference runs."""
+    def infer_trainset(self, path=None, mc_dropout=None, load_best=True, weights=None):
+        """results/<task>/<suffix>.pkl of runner_utils.py:103-104.  mc_dropout=None: as the reference runs.
+        weights: 'ema' (the default with train.ema_decay) or 'raw'."""
         if load_best:
             hdist.barrier()
             self.load(os.path.join(self.ckpt_dir, 'best_SeqPAN.npz'))
         if self.train_set is None:          # feed='host': the inference pass works on a device-resident set, built on first use
             self.train_set = DeviceDataset(*self._host_train, device=self.model.device)
-        records, ious = al.infer_trainset_sharded(self.model, self.train_set, self.batch_size, mc_dropout=mc_dropout, min_chars=4)
+        with self._weights(weights):
+            records, ious = al.infer_trainset_sharded(self.model, self.train_set, self.batch_size, mc_dropout=mc_dropout, min_chars=4)
         if self.rank != 0:
             return None, hdist.broadcast_object(None)
         if path:
@@ -239,8 +288,13 @@ class Runner:
 
     # ------------------------------------------------------------------ checkpoints by TF variable name
     def save(self, path):
+        """the parameters by TF variable name; a run with averaged weights adds <name>/ExponentialMovingAverage for every variable
+        (TensorFlow's own naming) and the update count"""
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        np.savez(path, **{k.replace('/', '|'): v for k, v in self.model.state_dict().items()})
+        named = self.model.state_dict()
+        if self.model.ema is not None:
+            named.update(self.model.ema_state_dict())
+        np.savez(path, **{k.replace('/', '|'): v for k, v in named.items()})
 
     def load(self, path):
         with np.load(path) as z:
@@ -248,3 +302,59 @@ class Runner:
         if self.model.finetune_word_emb and WORD_TABLE not in named:
             self.log.info('%s holds no %s: fine-tuning starts from the GloVe table' % (path, WORD_TABLE))
         self.model.load_state_dict(named)
+
+    # ------------------------------------------------------------------ the whole training state: a run continued on another visit
+    def save_state(self, path):
+        """Everything that determines how the run goes on: parameters, Adam moments, averaged weights and their count, the Philox
+        state, the step count, train()'s position and best epoch, and the shuffle stream.  Written under a temporary name and renamed
+        into place: a kill during the write leaves the previous file whole."""
+        m, pr = self.model, self.progress
+        ver, words, gauss = self.rand.getstate()
+        d = dict(format=np.int64(STATE_FORMAT), flat_floats=np.int64(m.params.numel()), params=m.params.cpu().numpy(),
+                 adam_m=m.adam_m.cpu().numpy(), adam_v=m.adam_v.cpu().numpy(), rng_state=m.rng_state.cpu().numpy(),
+                 global_step=np.int64(m.global_step), epoch=np.int64(pr['epoch']), epochs=np.int64(pr['epochs']),
+                 best=np.float64(pr['best']), best_lines=np.array('' if pr['best_lines'] is None else pr['best_lines']),
+                 has_best=np.int64(pr['best_lines'] is not None), rand_version=np.int64(ver),
+                 rand_words=np.array(words, dtype=np.uint64), rand_gauss=np.float64(np.nan if gauss is None else gauss),
+                 ema_decay=np.float64(m.ema_decay))
+        if m.ema is not None:
+            d.update(ema=m.ema.cpu().numpy(), ema_count=m.ema_count.cpu().numpy())
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        tmp = '%s.tmp.%d' % (path, os.getpid())
+        try:
+            with open(tmp, 'wb') as f:
+                np.savez(f, **d)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+
+    def load_state(self, path):
+        """the inverse of save_state, on every rank (ranks other than 0 keep the seed words of their own dropout stream and take its
+        offset).  The file and the run must agree on whether averaged weights are kept."""
+        m, pr = self.model, self.progress
+        with np.load(path) as z:
+            d = {k: z[k] for k in z.files}
+        if int(d.get('format', -1)) != STATE_FORMAT:
+            raise lib.HualError('%s is not a training state of this version (Runner.save_state)' % path)
+        if ('ema' in d) != (m.ema is not None):
+            raise lib.HualError('%s was written %s averaged weights and this run is configured %s them: set train.ema_decay %s'
+                                % ((path, 'with', 'without', 'to %g to continue it' % float(d['ema_decay'])) if 'ema' in d else
+                                   (path, 'without', 'with', 'to 0 (or drop it) to continue it')))
+        if int(d['flat_floats']) != m.params.numel():
+            raise lib.HualError('%s holds %d parameters, this model %d: another model configuration' % (path, int(d['flat_floats']), m.params.numel()))
+        dev = m.device
+        for name in ('params', 'adam_m', 'adam_v') + (('ema', 'ema_count') if m.ema is not None else ()):
+            getattr(m, name).copy_(torch.from_numpy(d[name]).to(dev))
+        rs = torch.from_numpy(d['rng_state']).to(dev)
+        if self.rank == 0:
+            m.rng_state.copy_(rs)
+        else:
+            m.rng_state[2:].copy_(rs[2:])
+        m.global_step = int(d['global_step'])
+        pr.update(epoch=int(d['epoch']), epochs=int(d['epochs']), best=float(d['best']),
+                  best_lines=str(d['best_lines']) if int(d['has_best']) else None)
+        g = float(d['rand_gauss'])
+        self.rand.setstate((int(d['rand_version']), tuple(int(x) for x in d['rand_words']), None if np.isnan(g) else g))

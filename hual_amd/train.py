@@ -257,22 +257,15 @@ class Trainer:
             s.tables_ready = True
 
     def _adam(self, prescale):
-        m = self.m
-        # the Philox offset of the dropout stream advances in the same launch (rng_state[2] += 1)
+        # the Philox offset of the dropout stream advances in the same launch (rng_state[2] += 1) ...
         lp = self._loop
+        loop = None
         if lp is not None:
             # ... and so does the epoch loop's device-side position: the step's spans go to their place in the bank, the cursor moves on
             nsp = self.spans.numel()
-            lib.check(self._lib.hual_adamw_clip_step_loop(
-                lib.ptr(m.params), lib.ptr(m.grads), lib.ptr(m.adam_m), lib.ptr(m.adam_v), lib.ptr(m.decay),
-                m.params.numel(), lib.ptr(m.lr), float(m.cfg.clip_norm), float(prescale), lib.ptr(m.sqnorm),
-                lib.ptr(m.rng_state), lib.ptr(lp['cursor']), lib.ptr(self.spans), lib.ptr(lp['bank']), nsp, int(self.shape[0]), nsp,
-                lib.stream_ptr()))
-            return
-        lib.check(self._lib.hual_adamw_clip_step_rng(
-            lib.ptr(m.params), lib.ptr(m.grads), lib.ptr(m.adam_m), lib.ptr(m.adam_v), lib.ptr(m.decay),
-            m.params.numel(), lib.ptr(m.lr), float(m.cfg.clip_norm), float(prescale), lib.ptr(m.sqnorm),
-            lib.ptr(m.rng_state), lib.stream_ptr()))
+            loop = (lp['cursor'], self.spans, lp['bank'], nsp, int(self.shape[0]), nsp)
+        # ... and so do the averaged weights of a model that keeps them (train.ema_decay): SeqPAN.optimizer_launch picks the entry point
+        self.m.optimizer_launch(prescale, rng=True, loop=loop)
 
     def _enqueue_assembly(self):
         """epoch loop: the batch-assembly launch is the first launch of the step (and of the step's graph)"""
@@ -325,7 +318,7 @@ class Trainer:
         """one eager step outside capture (first-use hipFuncSetAttribute etc., RCCL channel setup) on a snapshot of the training
         state: the first replay of the graph captured next is the first real step"""
         m = self.m
-        state = (m.params, m.adam_m, m.adam_v, m.rng_state)
+        state = (m.params, m.adam_m, m.adam_v, m.rng_state) + ((m.ema, m.ema_count) if m.ema is not None else ())
         snap = [t.clone() for t in state]
         enqueue()
         torch.cuda.synchronize()

@@ -228,6 +228,22 @@ int hual_adamw_clip_step_loop(float* params, const float* grads, float* adam_m, 
                               uint32_t* rng_state, int64_t* cursor, const int64_t* spans, int64_t* bank, int span_words, int sel_inc,
                               int bank_inc, void* stream);
 
+/* the same with AVERAGED WEIGHTS riding in the optimizer launch (an exponential moving average of the parameters, as the QANet family
+ * of span predictors is evaluated on; HUAL_ABI_VERSION unchanged: a new symbol, nothing else moved).  rng_state, cursor, spans and bank
+ * may be null as above (a null cursor: no loop position).  ema: flat shadow of `params` (same layout, n_padded floats, 16-byte aligned,
+ * the word table of a fine-tuning model included), ema_count: device u32, the number of updates so far, zero at start.  Update k
+ * (1-based) is
+ *     ema <- ema + (1 - d_k) * (params_new - ema),   d_k = min(ema_decay, (1 + k) / (10 + k))  with ema_warmup,  d_k = ema_decay  without,
+ * taken from the new parameter value while it is in registers (one 16-byte load and store more per four elements, no further launch).
+ * k lives on the device because a step replayed from a hipGraph has frozen arguments: the call's FIRST launch (the gradient's square
+ * norm) adds one to ema_count, its second launch (the update) only reads it - every block sees the same k, graph replays included.
+ * ema and ema_count go together: one without the other is refused; both null is hual_adamw_clip_step_loop without its cursor
+ * requirement.  ema_decay must lie in [0, 1). */
+int hual_adamw_clip_step_ema(float* params, const float* grads, float* adam_m, float* adam_v, const float* decay,
+                             uint64_t n_padded, const float* lr, float clip_norm, float grad_prescale, float* sqnorm,
+                             uint32_t* rng_state, int64_t* cursor, const int64_t* spans, int64_t* bank, int span_words, int sel_inc,
+                             int bank_inc, float* ema, uint32_t* ema_count, float ema_decay, int ema_warmup, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * One-shot all-reduce of the flat gradient bucket over peer mappings (csrc/xgmi.hip; absent in the reference, which
  * pins one GPU: utils/runner_utils.py:11).  ONE launch per rank: flag barrier, reduce-scatter read straight from the peers' buckets
