@@ -15,6 +15,11 @@ host.  There is no CPU fallback: without the library or a GPU this module raises
 Reference quirk kept selectable: eval-mode get_feed_dict (runner_utils.py:61-65) drops drop_rate, so the
 reference's two "dropout 0.5" passes run WITHOUT dropout and prop_logits1 == prop_logits2 == prop_logits;
 mc_dropout=None reproduces that, mc_dropout=0.5 is what the code intends.
+
+K-pass uncertainty (neither has): infer_trainset(mc_dropout=0.5, mc_samples=K, bank=McBank) runs K >= 2 stochastic forwards per batch
+and folds each into a device-resident bank of per-frame statistics (hual_al_mc_fold); no stochastic logit reaches the host, the records
+carry 'prop_uncert' instead of 'prop_logits1/2', and LabelUpdater.from_bank / update_labels(bank=) score straight from the bank
+(hual_al_score_mc).  Without mc_samples every launch, record and result is what it was.
 """
 import ctypes
 import math
@@ -46,8 +51,120 @@ def get_coff(task, I):
             t['neg']['distance'][I], t['neg']['model'][I], t['neg']['old'][I], t['uncert'][I])
 
 
+# ---------------------------------------------------------------- K-pass uncertainty bank ---------
+class McBank:
+    """Per-sample statistics of K stochastic forwards over a training set of N samples, resident on the device (hual_al_bank):
+    tlen i32 [N]; the deterministic logits s0 / e0 f32 [N, ld]; per head (0 = start, 1 = end) the minimum, maximum, Welford mean and
+    sum of squared deviations of the per-frame probabilities, stats f32 [2, 4, N, ld] = [head, (lo, hi, mean, m2)].
+    K: the number of stochastic passes folded so far (the largest k seen since the last k = 1)."""
+    FIELDS = ('lo', 'hi', 'mean', 'm2')
+
+    def __init__(self, N, ld, device='cuda:0'):
+        if not torch.cuda.is_available():
+            raise lib.HualError('McBank needs a GPU: the HIP path has no CPU fallback')
+        if N < 1 or not 2 <= ld <= 1024:
+            raise ValueError('McBank: need N >= 1 and 2 <= ld <= 1024')
+        self._lib = lib.load()
+        self.dev = torch.device(device)
+        self.N, self.ld, self.K = int(N), int(ld), 0
+        self.tlen = torch.zeros(N, dtype=torch.int32, device=self.dev)
+        self.s0 = torch.zeros(N, ld, device=self.dev)
+        self.e0 = torch.zeros(N, ld, device=self.dev)
+        self.stats = torch.zeros(2, 4, N, ld, device=self.dev)
+        self._bind()
+
+    @classmethod
+    def for_dataset(cls, dataset, device='cuda:0'):
+        """a bank over a DeviceDataset: one row per sample, as wide as its longest clip"""
+        return cls(len(dataset), max(2, int(np.max(dataset.vlen_h))), device=device)
+
+    def _bind(self):
+        a, st = lib._addr, self.stats
+        self.c = lib.hual_al_bank(self.N, self.ld, a(self.tlen), a(self.s0), a(self.e0), a(st[0, 0]), a(st[0, 1]), a(st[0, 2]), a(st[0, 3]),
+                                  a(st[1, 0]), a(st[1, 1]), a(st[1, 2]), a(st[1, 3]))
+
+    def stat(self, head, name):
+        """[N, ld] view: head 0 = start / 1 = end, name in ('lo', 'hi', 'mean', 'm2')"""
+        return self.stats[head, self.FIELDS.index(name)]
+
+    def rows(self, ids):
+        """device i32 row ids of one fold, checked on the host: inside the bank, none twice (the rows of a launch must be disjoint)"""
+        ids = np.ascontiguousarray(ids.cpu().numpy() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
+        if ids.size == 0 or ids.min() < 0 or ids.max() >= self.N:
+            raise lib.HualError('McBank.fold: row ids must lie in [0, %d)' % self.N)
+        if np.unique(ids).size != ids.size:
+            raise lib.HualError('McBank.fold: a row id is repeated - the rows of one fold must be disjoint')
+        return torch.from_numpy(ids.astype(np.int32)).to(self.dev)
+
+    def fold(self, ids, v_len, start_logits, end_logits, k, _checked=False):
+        """one forward's logits f32 [B, T_b] (device) into the rows `ids` (host array, list or tensor); k = 0: the deterministic pass,
+        k = 1..K: the stochastic ones, in order.  Enqueued on the current stream."""
+        if not _checked:
+            ids = self.rows(ids)
+        s, e = start_logits, end_logits
+        if s.dtype != torch.float32 or e.dtype != torch.float32 or s.dim() != 2 or e.shape != s.shape:
+            raise lib.HualError('McBank.fold: start / end logits must both be float32 [B, T_b]')
+        s, e = s.contiguous(), e.contiguous()
+        B, T = s.shape
+        vl = v_len.to(device=self.dev, dtype=torch.int32).contiguous()
+        if ids.numel() != B or vl.numel() != B:
+            raise lib.HualError('McBank.fold: ids and v_len must hold B = %d entries' % B)
+        lib.check(self._lib.hual_al_mc_fold(ctypes.byref(self.c), lib.ptr(ids), lib.ptr(vl), lib.ptr(s), lib.ptr(e), B, T, int(k),
+                                            lib.stream_ptr()))
+        if k >= 1:
+            self.K = int(k) if k == 1 else max(self.K, int(k))
+
+    def uncert(self, K=None, stat='range'):
+        """the model-uncertainty term f32 [N, ld] of every frame as hual_al_score_mc computes it (by that launch itself, so a value read
+        here is the value a later score uses, bit for bit); columns beyond a row's tlen are 0"""
+        K = self.K if K is None else int(K)
+        N, ld = self.N, self.ld
+        tl = self.tlen.cpu().numpy()
+        if tl.min() < 0 or tl.max() > ld:
+            raise lib.HualError('McBank.uncert: a row length outside [0, ld] - the bank is not initialised')
+        z = torch.zeros(N + 1, dtype=torch.int32, device=self.dev)
+        one = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        aset = lib.hual_al_set(N, ld, lib._addr(self.tlen), lib._addr(self.tlen), lib._addr(z), lib._addr(one),
+                               lib._addr(torch.zeros(1, dtype=torch.int8, device=self.dev)))
+        um = torch.zeros(N, ld, device=self.dev)
+        scratch = torch.empty(2, N, ld, device=self.dev)
+        uf = torch.empty(N, ld, device=self.dev, dtype=torch.float64)
+        uv = torch.empty(N, device=self.dev)
+        ob = torch.empty(N, device=self.dev, dtype=torch.int32)
+        p = lib.ptr
+        lib.check(self._lib.hual_al_score_mc(ctypes.byref(aset), p(self.s0), p(self.e0), ctypes.byref(self.c), K, lib.AL_STAT[stat], 0.0,
+                                             p(scratch[0]), p(scratch[1]), p(uf), p(uv), p(ob), p(um), lib.stream_ptr()))
+        torch.cuda.current_stream().synchronize()          # (the launch's inputs above are locals)
+        return um
+
+    # rows as host arrays and back: how the ranks of a sharded pass hand their (disjoint) rows to rank 0 - copied, never reduced
+    def export_rows(self, ids):
+        i = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).to(self.dev)
+        return dict(ids=np.ascontiguousarray(ids, dtype=np.int64), tlen=self.tlen[i].cpu().numpy(), s0=self.s0[i].cpu().numpy(),
+                    e0=self.e0[i].cpu().numpy(), stats=self.stats[:, :, i].cpu().numpy(), K=self.K)
+
+    def import_rows(self, part):
+        if len(part['ids']) == 0:
+            return
+        i = torch.from_numpy(part['ids']).to(self.dev)
+        self.tlen[i] = torch.from_numpy(part['tlen']).to(self.dev)
+        self.s0[i] = torch.from_numpy(part['s0']).to(self.dev)
+        self.e0[i] = torch.from_numpy(part['e0']).to(self.dev)
+        self.stats[:, :, i] = torch.from_numpy(part['stats']).to(self.dev)
+        self.K = max(self.K, int(part['K']))
+
+
+def attach_uncert(records, rows, bank, K, stat):
+    """records[j]['prop_uncert'] = the model-uncertainty term f32 [T_b] of bank row rows[j], read from the bank once"""
+    um = bank.uncert(K, stat).cpu().numpy()
+    tl = bank.tlen.cpu().numpy()
+    for r, n in zip(records, rows):
+        r['prop_uncert'] = um[n, :tl[n]].copy()
+
+
 # ---------------------------------------------------------------- infer_trainset ----------------
-def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None):
+def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc_samples=None, bank=None, sample_ids=None,
+                   mc_stat='range', _attach=True):
     """eval_test_save (runner_utils.py:69-110) without the file write: returns (records, ious).
 
     batches: iterable of (raw_records, video, video_seq_len, word_ids, char_ids) as TestLoader.test_iter yields them
@@ -56,9 +173,27 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None):
     batch_ids (with mc_dropout): the position of each yielded batch in the whole pass - the two stochastic forwards of batch i use the
     Philox offsets base + 2 i and base + 2 i + 1, whichever rank runs the batch and whatever ran before it (infer_trainset_sharded);
     rng = (seed, base) of that stream (default: the model's own state).
+    mc_samples=K (>= 2, with mc_dropout and a McBank `bank` over the whole set): the deterministic forward plus K stochastic ones, each
+    followed by one fold into the bank rows sample_ids[i] (one array of row ids per yielded batch; default: the samples in the order
+    they arrive).  Only the five deterministic fetches go to the host.  Pass k of batch i uses the Philox offset base + K i + (k - 1) -
+    today's two at K = 2.  The records lose prop_logits1/2 and gain 'prop_uncert' (f32 [T_b], the statistic `mc_stat` = 'range' or
+    'std' of hual_al_score_mc, read from the bank once at the end).
     """
     from . import data
     records, ious = [], []
+    K = None
+    if mc_samples is not None:
+        K = int(mc_samples)
+        if K < 2:
+            raise ValueError('mc_samples: K >= 2 stochastic passes (one sample has no spread)')
+        if mc_dropout is None:
+            raise ValueError('mc_samples needs mc_dropout: K passes without dropout are K copies of one')
+        if bank is None:
+            raise ValueError('mc_samples needs a McBank (bank=) over the whole training set')
+        if mc_stat not in lib.AL_STAT:
+            raise ValueError("mc_stat is 'range' or 'std'")
+    sample_ids = iter(sample_ids) if sample_ids is not None else None
+    rows_seen = []
     batch_ids = iter(batch_ids) if batch_ids is not None else None
     rng_base = rng_seed = None
     if batch_ids is not None and mc_dropout is not None:
@@ -74,7 +209,19 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None):
         raw, video, lens, word_ids, char_ids = batch
         o = model.forward(video, lens, word_ids, char_ids, drop_rate=0.0)
         dev = [o['start_logits'], o['end_logits'], o['match_scores'], o['start_index'], o['end_index']]
-        if mc_dropout is not None:
+        if K is not None:
+            n0 = sum(len(x) for x in rows_seen)
+            ids = np.asarray(next(sample_ids)) if sample_ids is not None else np.arange(n0, n0 + len(raw))
+            rows_seen.append(ids)
+            rows = bank.rows(ids)
+            bank.fold(rows, lens, o['start_logits'], o['end_logits'], 0, _checked=True)
+            if rng_base is not None:
+                model.set_rng(rng_seed, rng_base + K * int(next(batch_ids)))
+            for k in range(1, K + 1):
+                ok = model.forward(video, lens, word_ids, char_ids, drop_rate=mc_dropout)
+                model.rng_state[2] += 1                          # a fresh Philox offset for the next stochastic pass
+                bank.fold(rows, lens, ok['start_logits'], ok['end_logits'], k, _checked=True)
+        elif mc_dropout is not None:
             if rng_base is not None:
                 model.set_rng(rng_seed, rng_base + 2 * int(next(batch_ids)))
             o1 = model.forward(video, lens, word_ids, char_ids, drop_rate=mc_dropout)
@@ -95,16 +242,22 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None):
         ev.synchronize()
         # (copies: the records outlive the loop, the pinned staging buffers should not)
         s0, e0, ms, si, ei = (h.numpy().copy() for h in host[:5])
-        if mc_dropout is None:
-            s1, e1, s2, e2 = s0, e0, s0, e0                     # as written: drop_rate never reaches the graph (F8)
+        if K is not None:
+            stoch = None                                        # folded on the device: the records carry prop_uncert instead
+        elif mc_dropout is None:
+            stoch = (s0, e0, s0, e0)                            # as written: drop_rate never reaches the graph (F8)
         else:
-            s1, e1, s2, e2 = (h.numpy().copy() for h in host[5:9])
+            stoch = tuple(h.numpy().copy() for h in host[5:9])
         ious.extend(ious_of_spans(raw, si, ei))
         for i, r in enumerate(raw):
-            records.append({'vid': r['vid'], 'duration': r['duration'], 'psuedo_idx': [r['s_ind'], r['e_ind']],
-                            'sentence': ' '.join(r['words']), 'v_len': int(r['v_len']),
-                            'prop_idx': [int(si[i]), int(ei[i])], 'prop_logits': [s0[i], e0[i]],
-                            'prop_logits1': [s1[i], e1[i]], 'prop_logits2': [s2[i], e2[i]], 'm_score': ms[i]})
+            rec = {'vid': r['vid'], 'duration': r['duration'], 'psuedo_idx': [r['s_ind'], r['e_ind']],
+                   'sentence': ' '.join(r['words']), 'v_len': int(r['v_len']),
+                   'prop_idx': [int(si[i]), int(ei[i])], 'prop_logits': [s0[i], e0[i]]}
+            if stoch is not None:
+                s1, e1, s2, e2 = stoch
+                rec['prop_logits1'], rec['prop_logits2'] = [s1[i], e1[i]], [s2[i], e2[i]]
+            rec['m_score'] = ms[i]
+            records.append(rec)
 
     pending = None
     for batch in batches:
@@ -114,15 +267,20 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None):
         pending = job
     if pending is not None:
         emit(pending)
+    if K is not None and _attach and records:
+        attach_uncert(records, np.concatenate(rows_seen), bank, K, mc_stat)
     return records, ious
 
 
-def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_chars=4):
+def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_chars=4, mc_samples=None, bank=None, mc_stat='range'):
     """infer_trainset over a DeviceDataset in the reference's order (TrainNoSuffleLoader.test_iter, data_loader.py:167-206), the
     batches dealt round-robin to the ranks of the process group (batch i -> rank i % world; every rank holds the whole set):
     rank 0 returns (records, ious) of the WHOLE set in sample order, the other ranks (None, None).  One rank: the plain pass.
     The batches are the single-process ones (own padded shape each), so the records equal a single-process pass; the Philox offsets
-    of the stochastic forwards depend on the batch index only."""
+    of the stochastic forwards depend on the batch index only.
+    mc_samples=K: every rank folds its own batches into its own bank (`bank`; default: a McBank.for_dataset of this call only); the
+    rows of the other ranks reach rank 0's bank with the records (disjoint rows: copied, never reduced), and rank 0 reads
+    'prop_uncert' from the gathered bank.  Every rank's own stream advances by K * n_batches."""
     from . import dist as hdist
     world, rank = hdist.world_size(), hdist.rank()
     N = len(dataset)
@@ -137,20 +295,32 @@ def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_char
     st0 = model.rng_state.cpu().numpy().view(np.uint32).copy()
     own_rng = (int(st0[0]) | (int(st0[1]) << 32), int(st0[2]))
     rng = hdist.broadcast_object(own_rng)                       # rank 0's stream for the stochastic passes: the records do not depend on `world`
-    records, ious = infer_trainset(model, batches(), mc_dropout=mc_dropout, batch_ids=own, rng=rng)
+    K = int(mc_samples) if mc_samples is not None else None
+    own_rows = [np.arange(los[i], min(N, los[i] + batch_size)) for i in own]
+    if K is not None and bank is None:
+        bank = McBank.for_dataset(dataset, device=model.device)
+    records, ious = infer_trainset(model, batches(), mc_dropout=mc_dropout, batch_ids=own, rng=rng, mc_samples=mc_samples, bank=bank,
+                                   sample_ids=own_rows if K is not None else None, mc_stat=mc_stat, _attach=False)
     # every rank returns to its OWN dropout stream, behind the whole pass
-    model.set_rng(own_rng[0], own_rng[1] + (2 * len(los) if mc_dropout is not None else 0))
-    parts = hdist.gather_objects((own, records, ious))
+    model.set_rng(own_rng[0], own_rng[1] + ((2 if K is None else K) * len(los) if mc_dropout is not None else 0))
+    part = None
+    if K is not None and world > 1 and rank != 0:
+        part = bank.export_rows(np.concatenate(own_rows) if own_rows else np.zeros(0, dtype=np.int64))
+    parts = hdist.gather_objects((own, records, ious, part))
     if parts is None:
         return None, None
     out_r, out_i = [None] * N, [None] * N
-    for own_r, recs_r, ious_r in parts:
+    for own_r, recs_r, ious_r, part_r in parts:
+        if part_r is not None:
+            bank.import_rows(part_r)
         k = 0
         for i in own_r:
             n = min(N, los[i] + batch_size) - los[i]
             out_r[los[i]:los[i] + n] = recs_r[k:k + n]
             out_i[los[i]:los[i] + n] = ious_r[k:k + n]
             k += n
+    if K is not None:
+        attach_uncert(out_r, np.arange(N), bank, K, mc_stat)
     return out_r, out_i
 
 
@@ -224,7 +394,9 @@ def _round_half_even_index(t, duration, vlen):
 
 class LabelUpdater:
     """Device-side state of one update_label round: the logits of the results pkl as [N, ld] matrices, the active
-    points as CSR.  score() and renew() are one launch each."""
+    points as CSR.  score() and renew() are one launch each.
+    Bank form (from_bank, or records that hold 'prop_uncert'): the model-uncertainty term comes from a McBank of K folded passes
+    (hual_al_score_mc) instead of the two stochastic passes' logits; there is no [6, N, ld] matrix then."""
 
     def __init__(self, last_prop, aps, device='cuda:0'):
         if not torch.cuda.is_available():
@@ -237,15 +409,61 @@ class LabelUpdater:
         ld = int(tlen.max())
         if int(tlen.min()) < 2 or ld > 1024 or (vlen < 1).any() or (vlen > tlen).any():
             raise ValueError('need 2 <= len(logits) <= 1024 and 1 <= v_len <= len(logits)')
-        lg = np.zeros((6, N, ld), dtype=np.float32)
-        for n, p in enumerate(last_prop):
-            for k, key in enumerate(('prop_logits', 'prop_logits1', 'prop_logits2')):
-                lg[2 * k, n, :tlen[n]] = p[key][0]
-                lg[2 * k + 1, n, :tlen[n]] = p[key][1]
+        with_uncert = ['prop_uncert' in p for p in last_prop]
+        if any(with_uncert):
+            # a round resumed from records of a K-pass inference: the recorded term itself is the whole state.  As the start head's
+            # maximum over a minimum of 0 (end head all 0) the RANGE statistic returns it bit for bit: (u - 0) + (0 - 0)
+            if not all(with_uncert):
+                raise ValueError("some records hold 'prop_uncert' and some do not")
+            lg = np.zeros((2, N, ld), dtype=np.float32)
+            um = np.zeros((N, ld), dtype=np.float32)
+            for n, p in enumerate(last_prop):
+                if len(p['prop_uncert']) != tlen[n]:
+                    raise ValueError("'prop_uncert' and 'prop_logits' differ in length")
+                lg[0, n, :tlen[n]], lg[1, n, :tlen[n]] = p['prop_logits']
+                um[n, :tlen[n]] = p['prop_uncert']
+            lg_d = torch.from_numpy(lg).to(self.dev)
+            self._s0, self._e0 = lg_d[0], lg_d[1]
+            self._um, self._zero = torch.from_numpy(um).to(self.dev), torch.zeros(N, ld, device=self.dev)
+            a = lib._addr
+            self.bank_c = lib.hual_al_bank(N, ld, None, a(self._s0), a(self._e0), a(self._zero), a(self._um), a(self._zero), a(self._zero),
+                                           a(self._zero), a(self._zero), a(self._zero), a(self._zero))
+            self.bank, self.K, self.stat, self.logits = None, 2, 'range', None
+        else:
+            lg = np.zeros((6, N, ld), dtype=np.float32)
+            for n, p in enumerate(last_prop):
+                for k, key in enumerate(('prop_logits', 'prop_logits1', 'prop_logits2')):
+                    lg[2 * k, n, :tlen[n]] = p[key][0]
+                    lg[2 * k + 1, n, :tlen[n]] = p[key][1]
+            self.logits = torch.from_numpy(lg).to(self.dev)
+            self.bank_c = None
+        self._finish(N, ld, tlen, vlen, torch.from_numpy(tlen).to(self.dev), aps)
+
+    @classmethod
+    def from_bank(cls, bank, vlen, aps, K=None, stat='range'):
+        """score straight from a McBank (no upload, no logits matrix).  vlen: host [N] valid frames; K: the stochastic passes the bank
+        holds (default: bank.K); stat: 'range' or 'std' (hual_al_score_mc)."""
+        if stat not in lib.AL_STAT:
+            raise ValueError("stat is 'range' or 'std'")
+        self = cls.__new__(cls)
+        self._lib = lib.load()
+        self.dev = bank.dev
+        tlen = bank.tlen.cpu().numpy()
+        vlen = np.ascontiguousarray(vlen, dtype=np.int32)
+        if len(vlen) != bank.N or int(tlen.min()) < 2 or int(tlen.max()) > bank.ld or (vlen < 1).any() or (vlen > tlen).any():
+            raise ValueError('need one v_len per bank row, every row folded (tlen >= 2) and 1 <= v_len <= tlen')
+        self.bank, self.bank_c, self.logits = bank, bank.c, None
+        self._s0, self._e0 = bank.s0, bank.e0
+        self.K, self.stat = int(bank.K if K is None else K), stat
+        if self.K < 2:
+            raise ValueError('the bank holds K = %d stochastic passes: a spread needs two' % self.K)
+        self._finish(bank.N, bank.ld, tlen, vlen, bank.tlen, aps)
+        return self
+
+    def _finish(self, N, ld, tlen, vlen, tlen_d, aps):
         self.N, self.ld = N, ld
         self.tlen_h, self.vlen_h = tlen, vlen
-        self.logits = torch.from_numpy(lg).to(self.dev)
-        self.tlen = torch.from_numpy(tlen).to(self.dev)
+        self.tlen = tlen_d
         self.vlen = torch.from_numpy(vlen).to(self.dev)
         self.sprob = torch.zeros(N, ld, device=self.dev)
         self.eprob = torch.zeros(N, ld, device=self.dev)
@@ -269,6 +487,11 @@ class LabelUpdater:
 
     def score(self, coff_uncert):
         p, lg = lib.ptr, self.logits
+        if self.bank_c is not None:
+            lib.check(self._lib.hual_al_score_mc(ctypes.byref(self.set), p(self._s0), p(self._e0), ctypes.byref(self.bank_c), self.K,
+                                                 lib.AL_STAT[self.stat], float(coff_uncert), p(self.sprob), p(self.eprob),
+                                                 p(self.uncert_frame), p(self.uncert_video), p(self.observe), None, lib.stream_ptr()))
+            return
         lib.check(self._lib.hual_al_score(ctypes.byref(self.set), p(lg[0]), p(lg[1]), p(lg[2]), p(lg[3]), p(lg[4]), p(lg[5]),
                                           float(coff_uncert), p(self.sprob), p(self.eprob), p(self.uncert_frame),
                                           p(self.uncert_video), p(self.observe), lib.stream_ptr()))
@@ -284,12 +507,15 @@ class LabelUpdater:
         return new_d.cpu().numpy()
 
 
-def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False):
+def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range'):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
     data/<task>_re<I>/train.json; last_prop: the records of results/<task>/re<I-1>.pkl; coff: get_coff(task, I).
     Mutates and returns data_old exactly as the reference writes it to data/<task>_re<I>/train.json.
+    bank: the McBank the K-pass inference that made last_prop folded into - the model uncertainty is then read from it on the device
+    (mc_samples = its K, default bank.K; mc_stat 'range' or 'std'); last_prop then only names the samples ('vid', 'v_len').  Without
+    a bank, records that hold 'prop_uncert' are scored from that recorded term.
     """
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -300,7 +526,10 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     # active points in one list per sample; the reference keeps two lists and only ever asks for min / max / membership
     # of each, so the relative order between the two kinds does not matter
     aps = [[(f, True) for f in r[4]['pos_idx']] + [(f, False) for f in r[4]['neg_idx']] for r in data_old]
-    up = LabelUpdater(last_prop, aps, device=device)
+    if bank is not None:
+        up = LabelUpdater.from_bank(bank, [p['v_len'] for p in last_prop], aps, K=mc_samples, stat=mc_stat)
+    else:
+        up = LabelUpdater(last_prop, aps, device=device)
     up.score(coff[6])
     uv = up.uncert_video.cpu().numpy()
     observe = up.observe.cpu().numpy()
@@ -341,7 +570,7 @@ def labels_from_times(data, vlens):
 
 
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
-              shuffle_seed=0, log=None, trainer=None):
+              shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -349,13 +578,18 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     `last_prop` is needed on rank 0 only (the other ranks may pass None).  Rank 0 renews the labels and broadcasts the new train
     list, the epochs run data parallel (`batch_size` clips per rank, Trainer.run_epoch), infer_trainset is sharded by batch and its
     records are gathered on rank 0.
+    mc_samples=K: the round's inference runs K stochastic passes folded into a McBank (metrics['mc_bank']; `bank` if given, else a new
+    one).  A `bank` that already holds the passes behind last_prop (the previous round's metrics['mc_bank']) feeds this round's label
+    update on the device before it is refilled; otherwise last_prop's own 'prop_uncert' or 'prop_logits1/2' do.
     Returns (new train list, new results records - rank 0 only, else None -, metrics dict)."""
     import time
     from . import dist as hdist
     from .train import Trainer
     world, rank = hdist.world_size(), hdist.rank()
     t0 = time.perf_counter()
-    new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device) if rank == 0 else None
+    prev = bank if bank is not None and bank.K >= 2 else None
+    new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
+                             mc_stat=mc_stat) if rank == 0 else None
     new_data = hdist.broadcast_object(new_data)
     torch.cuda.synchronize()
     t1a = time.perf_counter()
@@ -377,7 +611,10 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         steps += (N + batch_size * world - 1) // (batch_size * world)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    records, ious = infer_trainset_sharded(model, dataset, batch_size, mc_dropout=mc_dropout, min_chars=4)
+    if mc_samples is not None and bank is None:
+        bank = McBank.for_dataset(dataset, device=model.device)
+    records, ious = infer_trainset_sharded(model, dataset, batch_size, mc_dropout=mc_dropout, min_chars=4, mc_samples=mc_samples,
+                                           bank=bank if mc_samples is not None else None, mc_stat=mc_stat)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     met = hdist.broadcast_object(iou_metrics(ious) if rank == 0 else None)
@@ -385,6 +622,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     m = dict(update_s=t1a - t0, relabel_s=t1 - t1a, train_s=t2 - t1, infer_s=t3 - t2, train_steps=steps, clips_per_s=N * epochs / max(t2 - t1, 1e-9),
              step_launch_modes=dict(tr.stats), world=world,
              r1i3=r3, r1i5=r5, r1i7=r7, miou=mi)
+    if mc_samples is not None:
+        m['mc_bank'] = bank
     if log and rank == 0:
         log('round %d: update_label %.3f s | train %d steps %.3f s (%.0f clips/s) | infer_trainset %.3f s | pseudo-label '
             'R1@0.5 %.2f mIoU %.2f' % (I, m['update_s'], steps, m['train_s'], m['clips_per_s'], m['infer_s'], r5, mi))

@@ -22,6 +22,41 @@ struct AlScoreArgs {
   int32_t* observe;                           // [N] argmax of uncert_frame
 };
 
+// hual_al_score_mc: the same scoring with the model-uncertainty term read from the per-sample bank of K folded passes
+// (the fields al_score_body reads carry the names of AlScoreArgs)
+struct AlScoreMcArgs {
+  const float *s0, *e0;                       // [N, ld] deterministic logits
+  const float *lo_s, *hi_s, *m2_s;            // [N, ld] start head: min / max probability, sum of squared deviations
+  const float *lo_e, *hi_e, *m2_e;            // [N, ld] end head
+  int ld, N;
+  const int32_t* vlen;
+  const int32_t* tlen;
+  const int32_t* ap_off;
+  const int32_t* ap_idx;
+  const int8_t* ap_pos;
+  float coff_uncert;
+  int stat;                                   // HUAL_AL_STAT_RANGE / HUAL_AL_STAT_STD
+  float km1;                                  // (float)(K - 1)
+  float* sprob;
+  float* eprob;
+  double* uncert_frame;
+  float* uncert_video;
+  int32_t* observe;
+  float* uncert_model;                        // [N, ld] the model-uncertainty term itself (NULL: not written)
+};
+
+// hual_al_mc_fold: one forward's logits [B, T] folded into the rows ids[b] of the bank
+struct AlFoldArgs {
+  const int32_t* ids;                         // [B] bank rows
+  const int32_t* vlen;                        // [B] valid frames of each clip
+  const float *s, *e;                         // [B, T] start / end logits
+  int B, T, k;                                // k = 0: deterministic pass, 1..K: stochastic passes
+  int ld, N;
+  int32_t* tlen;                              // [N]
+  float *s0, *e0;                             // [N, ld]
+  float *lo[2], *hi[2], *mean[2], *m2[2];     // [N, ld] per head (0 = start, 1 = end)
+};
+
 struct AlRenewArgs {
   const int32_t* sel;                         // [nsel] sample ids to update (NULL: all)
   const float* sprob;
@@ -38,6 +73,8 @@ struct AlRenewArgs {
 };
 
 int launch_al_score(const AlScoreArgs& a, hipStream_t s);
+int launch_al_score_mc(const AlScoreMcArgs& a, hipStream_t s);
+int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);
 
 }  // namespace hual

@@ -133,7 +133,31 @@ __device__ __forceinline__ float sigmoid_np(float x) { return 1.0f / (1.0f + exp
 // ------------------------------------------------------------------------------------------------------
 // get_uncert_rank body (update_label.py:125-169) for one sample per block
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(AL_THREADS) void al_score_kernel(AlScoreArgs a) {
+namespace {
+
+// the model-uncertainty term of frame i = row + t, by its source: the two stochastic passes' logits (get_uncert_model,
+// utils_hual.py:144-161) ...
+__device__ __forceinline__ float model_uncert(const AlScoreArgs& a, size_t i) {
+  return fabsf(sigmoid_np(a.s1[i]) - sigmoid_np(a.s2[i])) + fabsf(sigmoid_np(a.e1[i]) - sigmoid_np(a.e2[i]));
+}
+__device__ __forceinline__ void keep_uncert(const AlScoreArgs&, size_t, float) {}
+
+// ... or the bank of K folded passes.  RANGE at K = 2 is the expression above bit for bit: hi - lo = fmaxf(p1, p2) - fminf(p1, p2)
+// is the same subtraction as |p1 - p2| up to its sign.  STD is sqrt(2) times the sample deviation (ddof = 1): |p1 - p2| at K = 2 up to
+// rounding, and of an expectation that does not grow with K.
+__device__ __forceinline__ float model_uncert(const AlScoreMcArgs& a, size_t i) {
+  if (a.stat == HUAL_AL_STAT_RANGE) return (a.hi_s[i] - a.lo_s[i]) + (a.hi_e[i] - a.lo_e[i]);
+  return sqrtf(2.0f) * (sqrtf(a.m2_s[i] / a.km1) + sqrtf(a.m2_e[i] / a.km1));
+}
+__device__ __forceinline__ void keep_uncert(const AlScoreMcArgs& a, size_t i, float um) {
+  if (a.uncert_model) a.uncert_model[i] = um;
+}
+
+}  // namespace
+
+// Args = AlScoreArgs: hual_al_score, the code it always was; Args = AlScoreMcArgs: hual_al_score_mc
+template <class Args>
+__global__ __launch_bounds__(AL_THREADS) void al_score_kernel(Args a) {
   extern __shared__ float lds[];            // dist[T] | tmp[T]
   __shared__ float red[AL_THREADS / 64];
   __shared__ double redd[AL_THREADS / 64];
@@ -161,7 +185,8 @@ __global__ __launch_bounds__(AL_THREADS) void al_score_kernel(AlScoreArgs a) {
     a.eprob[row + t] = sigmoid_np(a.e0[row + t]);
     float um = 0.0f;
     if (t < V)
-      um = fabsf(sigmoid_np(a.s1[row + t]) - sigmoid_np(a.s2[row + t])) + fabsf(sigmoid_np(a.e1[row + t]) - sigmoid_np(a.e2[row + t]));
+      um = model_uncert(a, row + t);
+    keep_uncert(a, row + t, um);
     vsum += (double)um;
     const double uf = (double)dist[t] + (double)(um * a.coff_uncert);
     a.uncert_frame[row + t] = uf;
@@ -184,6 +209,59 @@ __global__ __launch_bounds__(AL_THREADS) void al_score_kernel(AlScoreArgs a) {
     }
     a.uncert_video[n] = (float)s;
     a.observe[n] = besti;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// One forward's logits folded into the bank: min / max / Welford mean and sum of squared deviations of the per-frame
+// probabilities, one workgroup per clip, rows disjoint (no atomics).  Only columns [0, T) of the rows ids[b] are written.
+// ------------------------------------------------------------------------------------------------------
+namespace {
+
+// Welford's update with every operation rounded on its own: tests/mc_uncert_ref.py restates it in numpy, which never fuses.  What must
+// stay unfused: `mean + d / k` (a division, then an add) and above all `m2 + d * (p - mean)` - as an fma the product would enter the sum
+// unrounded, and at K = 2 m2 would no longer be the float32 product d * (d / 2) whose root times sqrt(2) is |p1 - p2| to an ulp.
+__device__ __forceinline__ void welford_step(float p, float k, float& mean, float& m2) {
+#pragma clang fp contract(off)
+  const float d = p - mean;
+  mean = mean + d / k;
+  const float r = p - mean;
+  const float q = d * r;
+  m2 = m2 + q;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(AL_THREADS) void al_mc_fold_kernel(AlFoldArgs a) {
+  const int b = blockIdx.x;
+  const int n = a.ids[b];
+  if (n < 0 || n >= a.N) return;                      // an id outside the bank writes nothing
+  const int V = a.vlen[b];
+  const size_t row = (size_t)n * a.ld, src = (size_t)b * a.T;
+  if (a.k == 0) {
+    for (int t = threadIdx.x; t < a.T; t += AL_THREADS) {
+      a.s0[row + t] = a.s[src + t];
+      a.e0[row + t] = a.e[src + t];
+    }
+    if (threadIdx.x == 0) a.tlen[n] = a.T;
+    return;
+  }
+  const float kf = (float)a.k;
+  for (int t = threadIdx.x; t < a.T; t += AL_THREADS) {
+    const float p[2] = {t < V ? sigmoid_np(a.s[src + t]) : 0.0f, t < V ? sigmoid_np(a.e[src + t]) : 0.0f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (a.k == 1) {
+        a.lo[h][row + t] = p[h]; a.hi[h][row + t] = p[h]; a.mean[h][row + t] = p[h]; a.m2[h][row + t] = 0.0f;
+      } else {
+        float mean = a.mean[h][row + t], m2 = a.m2[h][row + t];
+        welford_step(p[h], kf, mean, m2);
+        a.lo[h][row + t] = fminf(a.lo[h][row + t], p[h]);
+        a.hi[h][row + t] = fmaxf(a.hi[h][row + t], p[h]);
+        a.mean[h][row + t] = mean;
+        a.m2[h][row + t] = m2;
+      }
+    }
   }
 }
 
@@ -297,7 +375,29 @@ int launch_al_score(const AlScoreArgs& a, hipStream_t s) {
   HUAL_REQUIRE(a.s0 && a.e0 && a.s1 && a.e1 && a.s2 && a.e2 && a.vlen && a.tlen && a.ap_off, "al_score: null input");
   HUAL_REQUIRE(a.sprob && a.eprob && a.uncert_frame && a.uncert_video && a.observe, "al_score: null output");
   HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_score: need N > 0 and 2 <= ld <= 1024");
-  HUAL_LAUNCH(0.0, 40.0 * a.N * a.ld, al_score_kernel, dim3(a.N), dim3(AL_THREADS), 2 * a.ld * sizeof(float), s, a);
+  HUAL_LAUNCH(0.0, 40.0 * a.N * a.ld, al_score_kernel<AlScoreArgs>, dim3(a.N), dim3(AL_THREADS), 2 * a.ld * sizeof(float), s, a);
+  HUAL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_al_score_mc(const AlScoreMcArgs& a, hipStream_t s) {
+  HUAL_REQUIRE(a.s0 && a.e0 && a.lo_s && a.hi_s && a.m2_s && a.lo_e && a.hi_e && a.m2_e && a.vlen && a.tlen && a.ap_off,
+               "al_score_mc: null input");
+  HUAL_REQUIRE(a.sprob && a.eprob && a.uncert_frame && a.uncert_video && a.observe, "al_score_mc: null output");
+  HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_score_mc: need N > 0 and 2 <= ld <= 1024");
+  HUAL_LAUNCH(0.0, 44.0 * a.N * a.ld, al_score_kernel<AlScoreMcArgs>, dim3(a.N), dim3(AL_THREADS), 2 * a.ld * sizeof(float), s, a);
+  HUAL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s) {
+  HUAL_REQUIRE(a.ids && a.vlen && a.s && a.e, "al_mc_fold: null input");
+  HUAL_REQUIRE(a.tlen && a.s0 && a.e0, "al_mc_fold: null bank");
+  for (int h = 0; h < 2; ++h) HUAL_REQUIRE(a.lo[h] && a.hi[h] && a.mean[h] && a.m2[h], "al_mc_fold: null bank");
+  HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_mc_fold: need N > 0 and 2 <= ld <= 1024");
+  HUAL_REQUIRE(a.B > 0 && a.T >= 2 && a.T <= a.ld, "al_mc_fold: need B > 0 and 2 <= T_b <= ld");
+  HUAL_REQUIRE(a.k >= 0, "al_mc_fold: pass index k >= 0");
+  HUAL_LAUNCH(0.0, (a.k == 0 ? 16.0 : a.k == 1 ? 40.0 : 72.0) * a.B * a.T, al_mc_fold_kernel, dim3(a.B), dim3(AL_THREADS), 0, s, a);
   HUAL_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -328,6 +428,35 @@ int hual_al_score(const hual_al_set* set, const float* s0, const float* e0, cons
   a.coff_uncert = coff_uncert;
   a.sprob = sprob; a.eprob = eprob; a.uncert_frame = uncert_frame; a.uncert_video = uncert_video; a.observe = observe_point;
   return launch_al_score(a, (hipStream_t)stream);
+}
+
+int hual_al_score_mc(const hual_al_set* set, const float* s0, const float* e0, const hual_al_bank* bank, int K, int stat,
+                     float coff_uncert, float* sprob, float* eprob, double* uncert_frame, float* uncert_video,
+                     int32_t* observe_point, float* uncert_model, void* stream) {
+  HUAL_REQUIRE(set && bank, "hual_al_score_mc: null pointer");
+  HUAL_REQUIRE(K >= 2, "hual_al_score_mc: K >= 2 stochastic passes (one sample has no spread)");
+  HUAL_REQUIRE(stat == HUAL_AL_STAT_RANGE || stat == HUAL_AL_STAT_STD, "hual_al_score_mc: stat is HUAL_AL_STAT_RANGE or HUAL_AL_STAT_STD");
+  HUAL_REQUIRE(bank->N == set->N && bank->ld == set->ld, "hual_al_score_mc: bank and set differ in N or ld");
+  AlScoreMcArgs a{};
+  a.s0 = s0; a.e0 = e0;
+  a.lo_s = bank->lo_s; a.hi_s = bank->hi_s; a.m2_s = bank->m2_s; a.lo_e = bank->lo_e; a.hi_e = bank->hi_e; a.m2_e = bank->m2_e;
+  a.ld = set->ld; a.N = set->N; a.vlen = set->vlen; a.tlen = set->tlen;
+  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos;
+  a.coff_uncert = coff_uncert; a.stat = stat; a.km1 = (float)(K - 1);
+  a.sprob = sprob; a.eprob = eprob; a.uncert_frame = uncert_frame; a.uncert_video = uncert_video; a.observe = observe_point;
+  a.uncert_model = uncert_model;
+  return launch_al_score_mc(a, (hipStream_t)stream);
+}
+
+int hual_al_mc_fold(const hual_al_bank* bank, const int32_t* ids, const int32_t* v_len, const float* start_logits,
+                    const float* end_logits, int B, int T_b, int k, void* stream) {
+  HUAL_REQUIRE(bank, "hual_al_mc_fold: null bank");
+  AlFoldArgs a{};
+  a.ids = ids; a.vlen = v_len; a.s = start_logits; a.e = end_logits; a.B = B; a.T = T_b; a.k = k;
+  a.ld = bank->ld; a.N = bank->N; a.tlen = bank->tlen; a.s0 = bank->s0; a.e0 = bank->e0;
+  a.lo[0] = bank->lo_s; a.hi[0] = bank->hi_s; a.mean[0] = bank->mean_s; a.m2[0] = bank->m2_s;
+  a.lo[1] = bank->lo_e; a.hi[1] = bank->hi_e; a.mean[1] = bank->mean_e; a.m2[1] = bank->m2_e;
+  return launch_al_mc_fold(a, (hipStream_t)stream);
 }
 
 int hual_al_renew(const hual_al_set* set, const int32_t* sel, int nsel, const float* sprob, const float* eprob,

@@ -57,6 +57,15 @@ class hual_al_set(ctypes.Structure):
                 ('ap_off', ctypes.c_void_p), ('ap_idx', ctypes.c_void_p), ('ap_pos', ctypes.c_void_p)]
 
 
+class hual_al_bank(ctypes.Structure):
+    _fields_ = [('N', ctypes.c_int32), ('ld', ctypes.c_int32), ('tlen', ctypes.c_void_p), ('s0', ctypes.c_void_p), ('e0', ctypes.c_void_p),
+                ('lo_s', ctypes.c_void_p), ('hi_s', ctypes.c_void_p), ('mean_s', ctypes.c_void_p), ('m2_s', ctypes.c_void_p),
+                ('lo_e', ctypes.c_void_p), ('hi_e', ctypes.c_void_p), ('mean_e', ctypes.c_void_p), ('m2_e', ctypes.c_void_p)]
+
+
+AL_STAT = {'range': 0, 'std': 1}      # HUAL_AL_STAT_RANGE / HUAL_AL_STAT_STD
+
+
 class hual_dataset(ctypes.Structure):
     _fields_ = [('feat_bank', ctypes.c_void_p), ('feat_off', ctypes.c_void_p), ('vdim', ctypes.c_int32),
                 ('sample_vid', ctypes.c_void_p), ('word_off', ctypes.c_void_p), ('word_bank', ctypes.c_void_p),
@@ -138,6 +147,8 @@ def load():
     lib.hual_span_topk.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]
     lib.hual_linear_dw.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, u64, vp]
     lib.hual_al_score.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
+    lib.hual_al_mc_fold.argtypes = [P(hual_al_bank), vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.hual_al_score_mc.argtypes = [P(hual_al_set), vp, vp, P(hual_al_bank), i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_al_renew.argtypes = [P(hual_al_set), vp, i32, vp, vp, vp, P(ctypes.c_double), vp, vp]
     lib.hual_assemble_batch.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_carry.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]

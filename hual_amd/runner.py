@@ -266,16 +266,18 @@ class Runner:
         return t
 
     # ------------------------------------------------------------------ main.py --mode infer_trainset (:99-111)
-    def infer_trainset(self, path=None, mc_dropout=None, load_best=True, weights=None):
+    def infer_trainset(self, path=None, mc_dropout=None, load_best=True, weights=None, mc_samples=None, mc_stat='range', bank=None):
         """results/<task>/<suffix>.pkl of runner_utils.py:103-104.  mc_dropout=None: as the reference runs.
-        weights: 'ema' (the default with train.ema_decay) or 'raw'."""
+        weights: 'ema' (the default with train.ema_decay) or 'raw'.  mc_samples=K (with mc_dropout): K stochastic passes folded into
+        `bank` (al.McBank; default: one of this call only) - the records then hold 'prop_uncert' instead of prop_logits1/2."""
         if load_best:
             hdist.barrier()
             self.load(os.path.join(self.ckpt_dir, 'best_SeqPAN.npz'))
         if self.train_set is None:          # feed='host': the inference pass works on a device-resident set, built on first use
             self.train_set = DeviceDataset(*self._host_train, device=self.model.device)
         with self._weights(weights):
-            records, ious = al.infer_trainset_sharded(self.model, self.train_set, self.batch_size, mc_dropout=mc_dropout, min_chars=4)
+            records, ious = al.infer_trainset_sharded(self.model, self.train_set, self.batch_size, mc_dropout=mc_dropout, min_chars=4,
+                                                      mc_samples=mc_samples, bank=bank, mc_stat=mc_stat)
         if self.rank != 0:
             return None, hdist.broadcast_object(None)
         if path:

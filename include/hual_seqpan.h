@@ -464,6 +464,42 @@ int hual_al_renew(const hual_al_set* set, const int32_t* sel, int nsel, const fl
                   const int32_t* old_idx, const double* coff6, int32_t* new_idx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K-pass MC-dropout uncertainty, folded on the device (HUAL_ABI_VERSION unchanged: new symbols, nothing else moved).
+ * Replaces, for K >= 2 stochastic passes, the two fixed slots prop_logits1 / prop_logits2 of the results records
+ * (utils/runner_utils.py:90-100) and the two-sample spread of get_uncert_model (utils/utils_hual.py:144-161): instead of
+ * keeping every pass's logits, each pass is folded into per-frame statistics of the probabilities p = 1/(1+expf(-logit)) (float32;
+ * p = 0 at t >= v_len, as get_uncert_model zeroes them).  The bank belongs to the caller, lives in device memory and covers
+ * the whole training set: row n = sample n, each array [N, ld] row major, 2 <= ld <= 1024.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hual_al_bank {
+  int32_t N, ld;
+  int32_t* tlen;                       /* [N] length of the sample's logits (padded length of its batch), written by the k = 0 fold */
+  float *s0, *e0;                      /* deterministic start / end logits (prop_logits) */
+  float *lo_s, *hi_s, *mean_s, *m2_s;  /* start head: min, max, running mean, sum of squared deviations (Welford) of p */
+  float *lo_e, *hi_e, *mean_e, *m2_e;  /* end head */
+} hual_al_bank;
+
+/* One launch folds one forward's start_logits / end_logits f32 [B, T_b] into the rows ids[b] (device i32 [B]: any rows in any order,
+ * each at most once - the rows of a launch must be disjoint; an id outside [0, N) writes nothing).  v_len: device i32 [B].
+ *   k = 0 (the deterministic pass): s0 / e0 <- the raw logits, tlen[ids[b]] <- T_b
+ *   k = 1: lo = hi = mean = p, m2 = 0
+ *   k >= 2: lo = fminf(lo, p), hi = fmaxf(hi, p), d = p - mean, mean += d / k, m2 += d * (p - mean), every operation rounded on its own
+ * Writes columns [0, T_b) of the listed rows only; 2 <= T_b <= ld.  Allocates nothing, does not synchronise. */
+int hual_al_mc_fold(const hual_al_bank* bank, const int32_t* ids, const int32_t* v_len, const float* start_logits,
+                    const float* end_logits, int B, int T_b, int k, void* stream);
+
+#define HUAL_AL_STAT_RANGE 0   /* (hi_s - lo_s) + (hi_e - lo_e): at K = 2 get_uncert_model's value bit for bit; grows with K */
+#define HUAL_AL_STAT_STD 1     /* sqrtf(2) * (sqrtf(m2_s / (K-1)) + sqrtf(m2_e / (K-1))): |p1 - p2| sums at K = 2 up to rounding; its
+                                  expectation does not grow with K, so coff_uncert keeps its meaning */
+/* hual_al_score with the model-uncertainty term read from a bank of K >= 2 folded passes instead of from s1 .. e2 (the fold has
+ * zeroed p at t >= v_len); s0 / e0 may be the bank's own.  Everything else - distance score, float64 mixture, uncert_video, the first
+ * maximal frame - is hual_al_score's, in the same arithmetic types.  uncert_model (may be NULL): f32 [N, ld], the term itself, columns
+ * [0, tlen[n]) of every row. */
+int hual_al_score_mc(const hual_al_set* set, const float* s0, const float* e0, const hual_al_bank* bank, int K, int stat,
+                     float coff_uncert, float* sprob, float* eprob, double* uncert_frame, float* uncert_video,
+                     int32_t* observe_point, float* uncert_model, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
