@@ -56,7 +56,7 @@ __device__ __forceinline__ int isactive_at(const ApInfo& a, const int32_t* idx, 
 }
 
 __device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max64(v);
+  v = wave_max64_bperm(v);
   __syncthreads();                                    // protects `red` against the previous use
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();

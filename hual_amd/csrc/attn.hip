@@ -116,19 +116,7 @@ __device__ __forceinline__ void panel_store_h(char* dst, int row, int c4, const 
   *reinterpret_cast<uint2*>(dst + row * 64 + 8 * c4) = h;
   *reinterpret_cast<uint2*>(dst + row * 64 + 32 + 8 * c4) = l;
 }
-// power-of-two scale that brings amax >= 0 into [2^13, 2^14) and its exact inverse (amax = 0: 2^113, finite)
-__device__ __forceinline__ float att_pow2_scale(float amax, float& inv) {
-  uint32_t eb = (__float_as_uint(amax) >> 23) & 0xffu;
-  eb = eb < 27u ? 27u : (eb > 240u ? 240u : eb);
-  inv = __uint_as_float((eb - 13u) << 23);
-  return __uint_as_float((267u - eb) << 23);
-}
-// workgroup barrier that waits for the wave's LDS operations only (__syncthreads() also drains the global stores of the job before)
-__device__ __forceinline__ void att_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// (the backward's operand scales are pow2_scale<240u, 267u>, bf16x3.h: amax >= 0 into [2^13, 2^14) and the exact inverse; amax = 0: 2^113)
 
 // ======================================================================================================
 // forward: ONE workgroup per (clip, head) for ALL jobs of the launch
@@ -151,7 +139,7 @@ __device__ __forceinline__ void att_lds_barrier() {
 //   longer matches the exact probabilities it recomputes (key-bias gradients, exact zeros by cancellation, came out at 1e-3): the
 //   backward would have to round its probabilities the same way (+2 vector instructions per score there for -3 here) - not taken.
 // NKT = key tiles of 16 of the unit's job (compile time per unit body; tiles beyond Tk hold zero keys with an additive term of -inf).
-__device__ __forceinline__ int nkt_pad(int Tk) {
+__host__ __device__ inline int nkt_pad(int Tk) {
   const int n = (Tk + 15) >> 4;
   return n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : 16;
 }
@@ -227,8 +215,7 @@ __device__ __forceinline__ void attn_fwd_unit(const AttnJob& job, int b, int h, 
     mx = fmaxf(fmaxf(mx, fmaxf(acc[0], acc[1])), fmaxf(acc[2], acc[3]));
     s[kt] = acc;
   }
-  mx = fmaxf(mx, lane_xor16_partner(mx));      // (v_permlane16_swap / v_permlane32_swap: no LDS round trip)
-  mx = fmaxf(mx, lane_xor32_partner(mx));
+  mx = slice16_max(mx);
   // e = 2^10 exp2(s - max): the operand scale of the probabilities rides in the exponent (no multiplication), the row sum and with
   // it 1 / sum carry it too, so the normalisation of the output tile needs no correction for it; the SAVED 1 / sum is the true one
   const float mxs = mx - 10.0f;                     // log2(ATT_SP)
@@ -242,8 +229,7 @@ __device__ __forceinline__ void attn_fwd_unit(const AttnJob& job, int b, int h, 
       sum += e;
     }
   }
-  sum += lane_xor16_partner(sum);
-  sum += lane_xor32_partner(sum);
+  sum = slice16_sum(sum);
   const float inv = 1.0f / sum;                     // = (true 1 / sum) / 2^(mx - mxs)
   const int ql_ = b * Tq + q0 + j;                  // job-local query index
   if (job.stats && g == 0 && qok) {
@@ -444,13 +430,9 @@ __global__ __launch_bounds__(NT, (NT == 512 && MAXNKT <= 8) ? 4 : 2) void attn_f
 // epilogues) except for one v_cndmask and one v_mul per score.
 // largest |dO| and |delta| of the head: every wave leaves its maxima in Red[wave], Red[4 + wave] during the staging (plain stores, no
 // barrier of their own); attn_bwd_compute reads all eight behind the barrier that ends the staging
-__device__ __forceinline__ float att_wave_max(float v) {      // DPP / permlane butterflies only (no LDS round trip)
-  v = fast_max32(v);
-  return fmaxf(v, lane_xor32_partner(v));
-}
 template <int NW = 4>
 __device__ __forceinline__ void att_wave_max2_put(float* Red, float a, float b) {
-  a = att_wave_max(a); b = att_wave_max(b);
+  a = wave_max64(a); b = wave_max64(b);
   if ((threadIdx.x & 63) == 0) { Red[threadIdx.x >> 6] = a; Red[NW + (threadIdx.x >> 6)] = b; }
 }
 
@@ -616,7 +598,7 @@ __device__ __forceinline__ void attn_bwd_stage(const AttnJob& job, int b, int h,
 #ifdef ATT_EXP_DOFIX      // timing experiment: what the per-row scale of the dO panel costs (numerically wrong for small gradients)
       const float rsc = 1024.0f; rinv = 1.0f / 1024.0f; (void)rmax;
 #else
-      const float rsc = att_pow2_scale(rmax, rinv);
+      const float rsc = pow2_scale<240u, 267u>(rmax, rinv);
 #endif
       if (row < Tqp) {
         panel_store_h(Qp, row, c4, qok ? sq[it] : f4zero(), ATT_SX);
@@ -697,7 +679,7 @@ __device__ __forceinline__ void attn_bwd_compute(const AttnJob& job, int b, int 
   }
   // the dO panel holds dO_q * s_q with the row's own scale s_q >= sg = the scale of the head's largest |dO|; St[6] = 1 / s_q
   float sg_inv;
-  const float sg = att_pow2_scale(gmax, sg_inv);
+  const float sg = pow2_scale<240u, 267u>(gmax, sg_inv);
   const float c_s = ATT_C1 / (ATT_SX * ATT_SX);     // scores: (16 Q) . (16 K)
   const float m_dp0 = (dodrop ? scale8 : 1.0f) / ATT_SX;      // dP = dO . V^T: (s_q dO) . (16 V) -> x 1 / (16 s_q) per row
   const float c_dv = sg_inv / ATT_SP;               // dV = Pd^T . dO with Pd_q x (sg / s_q) <= 1: sum_q (2^10 Pd sg / s_q) . (s_q dO)
@@ -729,12 +711,12 @@ __device__ __forceinline__ void attn_bwd_compute(const AttnJob& job, int b, int 
 #ifdef ATT_EXP_NOVMAX     // timing experiment
     vmax = 1.0f;
 #else
-    vmax = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wave_max64(vmax))));
+    vmax = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wave_max64_bperm(vmax))));
 #endif
     float s_ds_inv;
     // (the bound itself goes to [2^14, 2^15): p <= 1 + 1e-4 keeps p |t| below fp16's 65504, and every binade the scale gives away is a binade
     //  of small dS elements whose residual falls below fp16's normal range and is lost)
-    float s_ds = att_pow2_scale(16.0f * gmax * vmax * (dodrop ? scale8 : 1.0f) + dmax, s_ds_inv);
+    float s_ds = pow2_scale<240u, 267u>(16.0f * gmax * vmax * (dodrop ? scale8 : 1.0f) + dmax, s_ds_inv);
     s_ds *= 2.0f; s_ds_inv *= 0.5f;
     c_dk = s_ds_inv / ATT_SX;
     const float m_pd0 = (dodrop ? scale8 : 1.0f) * ATT_SP * s_ds_inv * sg;      // pd = (p s_ds) m_pd0 / s_q = 2^10 (sg / s_q) x dropped probability
@@ -833,7 +815,7 @@ __device__ __forceinline__ void attn_bwd_compute(const AttnJob& job, int b, int 
 #pragma unroll
         for (int r = 0; r < 4; ++r) dst[16 * r] = fst ? dq[r] * c_dk : fmaf(dq[r], c_dk, dst[16 * r]);
       }
-      if (NW == 8) att_lds_barrier();          // the slot's rows of this step are written before the other wave comes to them
+      if (NW == 8) lds_barrier();          // the slot's rows of this step are written before the other wave comes to them
     }
     first = false;
     if (qsplit) {      // partial dK / dV of this wave's queries -> slots 1 .. 3 as [wave][dk | dv][t][r][lane]; summed below
@@ -859,7 +841,7 @@ __device__ __forceinline__ void attn_bwd_compute(const AttnJob& job, int b, int 
       }
   }
   if (NW == 8 && !(wave < nkp)) {               // a wave without a key block (Tk <= 224) keeps the others' step barriers company
-    for (int qi = 0; qi < nqp; ++qi) att_lds_barrier();
+    for (int qi = 0; qi < nqp; ++qi) lds_barrier();
   }
   ATT_STAMP(3);
   __syncthreads();
@@ -955,7 +937,7 @@ __device__ __forceinline__ void attn_bwd_pre_store(const AttnJob& job, char* lds
 #ifdef ATT_EXP_DOFIX
   const float rsc = 1024.0f; rinv = 1.0f / 1024.0f;
 #else
-  const float rsc = att_pow2_scale(rmax, rinv);          // the row's own scale (attn_bwd_stage)
+  const float rsc = pow2_scale<240u, 267u>(rmax, rinv);          // the row's own scale (attn_bwd_stage)
 #endif
   if (row < Tqp) {
     panel_store_h(Qp, row, c4, qok ? s.q : f4zero(), ATT_SX);
@@ -1005,6 +987,29 @@ __device__ __forceinline__ void attn_bwd_chain(const AttnJob& j1, const AttnJob&
   attn_bwd_compute<DROP>(j3, b, h, lds, drop, bv, false);
 }
 
+// the call with DROP = true / false as `dd` (block-uniform: the job draws dropout) says; the call names the template argument DROP.
+// (A macro: the same call through a generic lambda compiles to another block order)
+#define ATT_BY_DROP(dd, ...)                                   \
+  do {                                                         \
+    if (dd) { constexpr bool DROP = true; __VA_ARGS__; }       \
+    else { constexpr bool DROP = false; __VA_ARGS__; }         \
+  } while (0)
+// (job, clip) = (x, y) of a workgroup of attn_bwd_kernel / attn_bwd_big_kernel from lid = its logical id / 8 heads.  An XCD holds a
+// contiguous run of logical ids = whole clips; inside the run the LARGEST job of every clip goes first (launch_attn_bwd sorts the jobs
+// by cost): the 64 resident slots of an XCD start on the 128 x 128 self-attention jobs together and the short jobs fill in behind
+// them - with the jobs of a clip interleaved the four-job launches ended on long jobs (44.5 -> 42.2 us each, A/B on one box).  Clip
+// counts that do not give every XCD whole clips keep the interleaved order
+__device__ __forceinline__ int2 attn_bwd_job_clip(int lid, int njobs) {
+  int jb = lid % njobs, b = lid / njobs;
+  const int per = (int)(gridDim.x >> 6);      // (job, clip) pairs per XCD
+  if ((gridDim.x & 63) == 0 && per % njobs == 0) {
+    const int cpx = per / njobs, x = lid / per, w = lid - x * per;
+    jb = w / cpx;
+    b = x * cpx + (w - jb * cpx);
+  }
+  return make_int2(jb, b);
+}
+
 // four jobs = two kinds of workgroup per (clip, head): kind 0 the largest job, kind 1 the chain of the other three
 __global__ __launch_bounds__(256, 2) void attn_bwd_chain_kernel(AttnBatch batch, DropCfg drop) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -1025,66 +1030,39 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_chain_kernel(AttnBatch batch,
   }
   if (b >= batch.j[0].B) return;   // block-uniform
   const bool dd = batch.j[0].drop_site >= 0 && drop.enabled;
-  if (kind == 0) {
-    if (dd) attn_bwd_body<true>(batch.j[0], b, h, lds, drop);
-    else attn_bwd_body<false>(batch.j[0], b, h, lds, drop);
-  } else {
-    if (dd) attn_bwd_chain<true>(batch.j[1], batch.j[2], batch.j[3], b, h, lds, drop);
-    else attn_bwd_chain<false>(batch.j[1], batch.j[2], batch.j[3], b, h, lds, drop);
-  }
+  if (kind == 0) ATT_BY_DROP(dd, attn_bwd_body<DROP>(batch.j[0], b, h, lds, drop));
+  else ATT_BY_DROP(dd, attn_bwd_chain<DROP>(batch.j[1], batch.j[2], batch.j[3], b, h, lds, drop));
 }
 
 __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnBatch batch, int njobs, DropCfg drop) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   int lid = xcd_logical_id();
   const int h = lid & 7; lid >>= 3;
-  // (job, clip) of this workgroup.  An XCD holds a contiguous run of logical ids = whole clips; inside the run the LARGEST job of
-  // every clip goes first (launch_attn_bwd sorts the jobs by cost): the 64 resident slots of an XCD start on the 128 x 128
-  // self-attention jobs together and the short jobs fill in behind them - with the jobs of a clip interleaved the four-job launches
-  // ended on long jobs (44.5 -> 42.2 us each, A/B on one box).  Clip counts that do not give every XCD whole clips keep the
-  // interleaved order
-  int jb = lid % njobs, b = lid / njobs;
-  {
-    const int per = (int)(gridDim.x >> 6);      // (job, clip) pairs per XCD
-    if ((gridDim.x & 63) == 0 && per % njobs == 0) {
-      const int cpx = per / njobs, x = lid / per, w = lid - x * per;
-      jb = w / cpx;
-      b = x * cpx + (w - jb * cpx);
-    }
-  }
-  const AttnJob& job = batch.j[jb];
+  const int2 jc = attn_bwd_job_clip(lid, njobs);
+  const int b = jc.y;
+  const AttnJob& job = batch.j[jc.x];
   if (b >= job.B) return;   // block-uniform
-  if (job.drop_site >= 0 && drop.enabled) attn_bwd_body<true>(job, b, h, lds, drop);
-  else attn_bwd_body<false>(job, b, h, lds, drop);
+  ATT_BY_DROP(job.drop_site >= 0 && drop.enabled, attn_bwd_body<DROP>(job, b, h, lds, drop));
 }
 
 // A launch whose LARGEST job has more than 128 queries and keys (dual attention at T = 256): that job on eight waves
 // (attn_bwd_compute NW = 8); the other jobs of the launch as before on the first four waves of their workgroups - the other four
-// end at once (s_barrier waits for the surviving waves of a workgroup only).  Workgroup -> (job, clip) as in attn_bwd_kernel.
+// end at once (s_barrier waits for the surviving waves of a workgroup only).
 __global__ __launch_bounds__(512) void attn_bwd_big_kernel(AttnBatch batch, int njobs, DropCfg drop) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   int lid = xcd_logical_id();
   const int h = lid & 7; lid >>= 3;
-  int jb = lid % njobs, b = lid / njobs;
-  {
-    const int per = (int)(gridDim.x >> 6);      // (job, clip) pairs per XCD
-    if ((gridDim.x & 63) == 0 && per % njobs == 0) {
-      const int cpx = per / njobs, x = lid / per, w = lid - x * per;
-      jb = w / cpx;
-      b = x * cpx + (w - jb * cpx);
-    }
-  }
-  const AttnJob& job = batch.j[jb];
+  const int2 jc = attn_bwd_job_clip(lid, njobs);
+  const int b = jc.y;
+  const AttnJob& job = batch.j[jc.x];
   if (b >= job.B) return;   // block-uniform
   const bool dd = job.drop_site >= 0 && drop.enabled;
-  if (jb == 0) {
-    if (dd) attn_bwd_body<true, 8>(job, b, h, lds, drop);
-    else attn_bwd_body<false, 8>(job, b, h, lds, drop);
+  if (jc.x == 0) {
+    ATT_BY_DROP(dd, attn_bwd_body<DROP, 8>(job, b, h, lds, drop));
     return;
   }
   if (threadIdx.x >= 256) return;               // (wave-uniform)
-  if (dd) attn_bwd_body<true>(job, b, h, lds, drop);
-  else attn_bwd_body<false>(job, b, h, lds, drop);
+  ATT_BY_DROP(dd, attn_bwd_body<DROP>(job, b, h, lds, drop));
 }
 
 namespace hual {
@@ -1118,10 +1096,6 @@ static bool getenv_flag(const char* name) {
   const char* v = getenv(name);
   return v != nullptr && atoi(v) != 0;
 }
-static int nkt_pad_host(int Tk) {
-  const int n = cdiv(Tk, 16);
-  return n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : 16;
-}
 // algorithmic HBM bytes of an attention job (forward): Q, K, V rows of a head read once, O written, softmax statistics and keep words
 static double attn_job_bytes(const AttnJob& j, bool drop) {
   return (double)j.B * 8.0 * ((double)j.Tq * 64.0 * 2.0 + (double)j.Tk * 128.0 + (double)j.Tq * 8.0) +
@@ -1144,7 +1118,7 @@ int launch_attn_fwd(const AttnJob* jobs, int n, const DropCfg& drop, hipStream_t
   int RT = 0;
   double flops = 0.0, bytes = 0.0;
   for (int i = 0; i < n; ++i) {
-    const int nktp = nkt_pad_host(jobs[i].Tk);
+    const int nktp = nkt_pad(jobs[i].Tk);
     RT += 16 * nktp;
     for (int qt = 0; qt < cdiv(jobs[i].Tq, 16); ++qt) us.push_back(U{2 * nktp + 3, (i << 4) | qt});
     flops += 4.0 * jobs[i].B * 8.0 * jobs[i].Tq * jobs[i].Tk * 16.0;   // QK^T + PV

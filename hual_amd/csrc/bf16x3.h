@@ -80,14 +80,19 @@ __device__ __forceinline__ void f16_split4(const float4& x, uint2& hi, uint2& lo
   f16_split_pair(x.z, x.w, hi.y, lo.y);
 }
 __device__ __forceinline__ float f4absmax(const float4& v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
-// power-of-two scale that brings a row maximum rmax >= 0 into [2^13, 2^14) (rmax below 2^-100, incl. 0: scale 2^113, still
-// finite); inv = 1 / (scale * 2^HUAL_F16_WSCALE_LOG2), both exact powers of two
-__device__ __forceinline__ float f16_row_scale(float rmax, float& inv) {
-  uint32_t eb = (__float_as_uint(rmax) >> 23) & 0xffu;
-  eb = eb < 27u ? 27u : (eb > 254u ? 254u : eb);
-  inv = __uint_as_float((eb - 13u - (uint32_t)HUAL_F16_WSCALE_LOG2) << 23);
-  return __uint_as_float((267u - eb) << 23);
+// Power-of-two operand scale from a magnitude amax >= 0: with eb = the exponent byte of amax clamped to [27, EB_MAX], the scale is
+// 2^(C - 127 - eb) - amax * scale lands in [2^(C - 254), 2^(C - 253)) - and inv = 1 / (scale * 2^INV_LOG2); both are exact powers of
+// two built in the exponent field.  amax below 2^-100 (0 and denormals included) takes the scale of eb = 27, still finite; amax
+// beyond the clamp (Inf / NaN included) that of eb = EB_MAX.
+template <uint32_t EB_MAX, uint32_t C, uint32_t INV_LOG2 = 0>
+__device__ __forceinline__ float pow2_scale(float amax, float& inv) {
+  uint32_t eb = (__float_as_uint(amax) >> 23) & 0xffu;
+  eb = eb < 27u ? 27u : (eb > EB_MAX ? EB_MAX : eb);
+  inv = __uint_as_float((eb - (C - 254u) - INV_LOG2) << 23);
+  return __uint_as_float((C - eb) << 23);
 }
+// scale of an operand row against the weight images: row maximum into [2^13, 2^14), the inverse takes the weights' fixed scale with it
+__device__ __forceinline__ float f16_row_scale(float rmax, float& inv) { return pow2_scale<254u, 267u, HUAL_F16_WSCALE_LOG2>(rmax, inv); }
 __device__ __forceinline__ float4 f4scale1(const float4& v, float s) { return make_float4(v.x * s, v.y * s, v.z * s, v.w * s); }
 __device__ __forceinline__ f16x8 join_tr_f16(s16x4 a, s16x4 b);
 

@@ -104,7 +104,7 @@ __device__ __forceinline__ void conv_block_fwd_body(const CbFwdArgs& a, const Ro
       if (grp < CB_NPAR) par[(l * CB_NPAR + grp) * 32 + l32] = qv[l];
     if (TAIL && grp < LNP_TP_VECS) TP[grp * 32 + l32] = tq;
   }
-  cb_barrier();
+  lds_barrier();
   HUAL_STAMP_K(2, 1);
 
 #pragma unroll 1
@@ -150,7 +150,7 @@ __device__ __forceinline__ void conv_block_fwd_body(const CbFwdArgs& a, const Ro
         if (t >= r0 && t < r0 + MT) { L.mean[t] = mean; L.rstd[t] = rstd; }
       }
     }
-    cb_barrier();
+    lds_barrier();
     HUAL_STAMP_K(2, 2 + 6 * l);
     // ---------------- P1b: depthwise conv over a sliding window of normalised rows -> operand planes
     if (l + 1 < 4) tf_load_w(wn, a.l[l + 1].wimg, wave, lane);      // the next layer's fragments (requested in front of this phase's stores)
@@ -214,7 +214,7 @@ __device__ __forceinline__ void conv_block_fwd_body(const CbFwdArgs& a, const Ro
       }
     }
     HUAL_STAMP_K(2, 3 + 6 * l);
-    cb_barrier();                                         // operand planes complete
+    lds_barrier();                                         // operand planes complete
     HUAL_STAMP_K(2, 4 + 6 * l);
     // ---------------- P2: pointwise convolution on the matrix cores (three or four row tiles: H = 9, 6 / 3, 0 at 37 .. 46 owned rows)
     f32x4 acc[4];
@@ -269,7 +269,7 @@ __device__ __forceinline__ void conv_block_fwd_body(const CbFwdArgs& a, const Ro
       bits_store2_t(L.relu_bits, orow[2], orow[3], own[2], own[3], ecol >> 2, rb[2], rb[3], lane);
     }
     if (l + 1 < 4) wc = wn;
-    cb_barrier();
+    lds_barrier();
     HUAL_STAMP_K(2, 7 + 6 * l);
   }
   if (TAIL) {      // x_4 of the owned rows is in X (rows r0 - xbase ..); the tail's operand slots take over everything from the operand planes on
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(CB_THREADS) void conv_block_bwd_kernel(CbBwdArgs a,
     }
     if (grp < 9) par[grp * 32 + l32] = pv;
     HUAL_STAMP_K(3, 2 + 7 * (3 - i));
-    cb_barrier();                                          // (1) operand planes + parameters complete
+    lds_barrier();                                          // (1) operand planes + parameters complete
     HUAL_STAMP_K(3, 3 + 7 * (3 - i));
     // ---- G: dC_i = dZ_i . W_i^T (three or four row tiles)
     f32x4 acc[4];
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(CB_THREADS) void conv_block_bwd_kernel(CbBwdArgs a,
     float irv[4];
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt) irv[rt] = ainv[16 * rt + (lane & 15)];
-    cb_barrier();                                          // (2) every wave is through the planes: they become dC
+    lds_barrier();                                          // (2) every wave is through the planes: they become dC
     HUAL_STAMP_K(3, 4 + 7 * (3 - i));
     {
       // accumulator rt of lane (j, g) = row 16 rt + j, columns 16 wave + 4 g .. + 3.  The 16 lanes j of a store are 16 rows of one
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(CB_THREADS) void conv_block_bwd_kernel(CbBwdArgs a,
         DC[lr * 32 + ((4 * wave + g) ^ (2 * j))] = make_float4(acc[rt][0] * ir, acc[rt][1] * ir, acc[rt][2] * ir, acc[rt][3] * ir);
       }
     }
-    cb_barrier();                                          // (3) dC visible
+    lds_barrier();                                          // (3) dC visible
     // keep & relu' of dZ_{i-1}, 4 bits per row (bit c = column col + c), rows packed into one register
     uint32_t zbits = 0;
 #pragma unroll
@@ -499,14 +499,14 @@ __global__ __launch_bounds__(CB_THREADS) void conv_block_bwd_kernel(CbBwdArgs a,
           dst[7 * 32] = sg;
           dst[8 * 32] = sb;
         }
-        cb_barrier();                                      // (4) on the first pass: dC consumed as well
+        lds_barrier();                                      // (4) on the first pass: dC consumed as well
         const float* pf = reinterpret_cast<const float*>(pbuf);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           const int e = threadIdx.x + CB_THREADS * q;
           if (e < 9 * HUAL_D) pacc[q] += (pf[e] + pf[e + 9 * HUAL_D]) + (pf[e + 2 * 9 * HUAL_D] + pf[e + 3 * 9 * HUAL_D]);
         }
-        cb_barrier();
+        lds_barrier();
       }
 #pragma unroll
       for (int q = 0; q < 3; ++q) {

@@ -86,8 +86,8 @@ __global__ __launch_bounds__(256) void tri_prep_kernel(CqBufs b, CqParams p, Row
       c = f4_select(n2, xs);
     }
     float4 w0 = ld4(p.w0[d1] + col), wm = ld4(p.wm[d1] + col), w1 = ld4(p.w1[d2] + col);
-    float s0 = half_sum32(a.x * w0.x + a.y * w0.y + a.z * w0.z + a.w * w0.w);
-    float s1 = half_sum32(c.x * w1.x + c.y * w1.y + c.z * w1.z + c.w * w1.w);
+    float s0 = fast_sum32(a.x * w0.x + a.y * w0.y + a.z * w0.z + a.w * w0.w);
+    float s1 = fast_sum32(c.x * w1.x + c.y * w1.y + c.z * w1.z + c.w * w1.w);
     st4(b.D1W + off, make_float4(a.x * wm.x, a.y * wm.y, a.z * wm.z, a.w * wm.w));
     st4(b.D2 + off, c);
     if (l32 == 0) { b.S0[row] = s0; b.S1[row] = s1; }
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(CQ_MAX_THREADS) void cq_fwd_kernel(CqBufs b, RowSpa
         const float mk = m2[jj];
         mx = fmaxf(mx, S[i * c.ld + jj] * mk + HUAL_MASK_VALUE * (1.0f - mk));
       }
-    mx = wave_max64(mx);
+    mx = wave_max64_bperm(mx);
     float sum = 0.f;
     if (i < c.N1)
       for (int jj = lane; jj < c.N2; jj += 64) {
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(CQ_MAX_THREADS) void cq_fwd_kernel(CqBufs b, RowSpa
         const float mk = m1[i];
         mx = fmaxf(mx, S[i * c.ld + jj] * mk + HUAL_MASK_VALUE * (1.0f - mk));
       }
-    mx = wave_max64(mx);
+    mx = wave_max64_bperm(mx);
     float sum = 0.f;
     if (jj < c.N2)
       for (int i = lane; i < c.N1; i += 64) {
@@ -346,7 +346,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
       float4 x = xrows.v[u];
       if (dr.enabled) x = f4_select(nib[u], make_float4(x.x * dr.scale, x.y * dr.scale, x.z * dr.scale, x.w * dr.scale));
       const float4 w = first ? w0 : w1;
-      const float sv = half_sum32(x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w);
+      const float sv = fast_sum32(x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w);
       const float4 o = first ? make_float4(x.x * wm.x, x.y * wm.y, x.z * wm.z, x.w * wm.w) : x;
       rows.v[u] = o;
       if (row < N1q + N2q && k < (first ? c.N1p : c.N2p)) {
@@ -359,7 +359,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
     }
   }
   cq_rows_store<1>(rows, bufA, N1q, bufB, N2q);
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(1);
   // ---- score = d1w . d2^T + s0 + s1
   for (int tile = wave; tile < ni * nj; tile += CQ_WAVES) {
@@ -368,7 +368,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
 #pragma unroll
     for (int r = 0; r < 4; ++r) S[__mul24(i0 + 4 * g + r, c.ld) + n0 + j] = acc[r] + s0[i0 + 4 * g + r] + s1[n0 + j];
   }
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(2);
   cq_rows_store<1>(xrows, bufA, N1q, bufB, N2q);      // X1, X2
   CQ_STAMP(8);
@@ -383,9 +383,9 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
         const float mk = m2[l32];
         lg = S[__mul24(i, c.ld) + l32] * mk + HUAL_MASK_VALUE * (1.0f - mk);
       }
-      const float mx = half_max32(lg);
+      const float mx = fast_max32(lg);
       const float e = ok ? __expf(lg - mx) : 0.f;
-      const float inv = 1.0f / half_sum32(e);
+      const float inv = 1.0f / fast_sum32(e);
       cq_sc_store<LONG1, 1>(SrI, i, l32, ok ? e * inv : 0.f);
     }
   } else {
@@ -396,7 +396,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
           const float mk = m2[jj];
           mx = fmaxf(mx, S[__mul24(i, c.ld) + jj] * mk + HUAL_MASK_VALUE * (1.0f - mk));
         }
-      mx = wave_max64(mx);
+      mx = wave_max64_bperm(mx);
       float sum = 0.f;
       if (i < c.N1)
         for (int jj = lane; jj < c.N2; jj += 64) {
@@ -426,9 +426,9 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
         const float mk = m1[l32];
         lg = S[__mul24(l32, c.ld) + jj] * mk + HUAL_MASK_VALUE * (1.0f - mk);
       }
-      const float mx = half_max32(lg);
+      const float mx = fast_max32(lg);
       const float e = ok ? __expf(lg - mx) : 0.f;
-      const float inv = 1.0f / half_sum32(e);
+      const float inv = 1.0f / fast_sum32(e);
       cq_sc_store<LONG1, 1>(ScI, l32, jj, ok ? e * inv : 0.f);
     }
   } else {
@@ -439,7 +439,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
           const float mk = m1[i];
           mx = fmaxf(mx, S[__mul24(i, c.ld) + jj] * mk + HUAL_MASK_VALUE * (1.0f - mk));
         }
-      mx = wave_max64(mx);
+      mx = wave_max64_bperm(mx);
       float sum = 0.f;
       if (jj < c.N2)
         for (int i = lane; i < c.N1; i += 64) {
@@ -459,7 +459,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
     }
   }
   CQ_STAMP(10);
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(3);
   // ---- save both softmaxes for the backward pass: the images as they stand (both planes)
   {
@@ -494,7 +494,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
       m2acc[q] = cq_mma<!LONG1, true, 1>(ScI, i0, bufA, n0, N1q, lane, zero);
     }
   }
-  cq_barrier();
+  lds_barrier();
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int tile = wave + CQ_WAVES * q;
@@ -507,7 +507,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
       }
     }
   }
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(6);
   // ---- q2c = Sr . M2          (= (Sr.Sc^T).x1 of layers.py:127, re-associated)
   for (int tile = wave; tile < ni * 8; tile += CQ_WAVES) {
@@ -752,12 +752,12 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
   }
   cq_wgmax_put(mx0, cq_rows_absmax_a(r1, N1q));          // max |dC2Q|, max |dQ2C| of the clip
   cq_wgmax_put(mx1, cq_rows_absmax_a(r2, N1q));
-  cq_barrier();
+  lds_barrier();
   CqImg bufA2 = bufA;                                    // the dQ2C image (same bytes as bufA, its own scale)
   cq_img_autoscale(bufA, cq_wgmax_get(mx0));
   cq_img_autoscale(bufA2, cq_wgmax_get(mx1));
   cq_rows_store<1>(r1, bufA, N1q, bufB, N2q);            // dC2Q, X2
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(17);
   // ---- first half of dSr = dc2q . x2^T (+ dq2c . M2^T below) ;  dXb (x2 rows) = Sr^T . dc2q
   cq_rows_load(r1, b.X + x1off, c.N1, N1q, nullptr, 0, N2q);      // X1, for the dSc product
@@ -779,10 +779,10 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
       if (jj < c.N2) dXb[(size_t)(c.x2base + jj) * HUAL_D + n0 + j] = acc2[r];
     }
   }
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(18);
   cq_rows_store<1>(r2, bufA2, N1q, bufB, N2q);         // dQ2C, M2
-  cq_barrier();
+  lds_barrier();
   cq_rows_load(r2, b.D1W + x1off, c.N1, N1q, b.D2 + x2off, c.N2, N2q);     // for the last two products
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -808,7 +808,7 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
     }
   }
   cq_wgmax_put(mx0, mmax);                               // (mx0 was read behind the first barrier: four barriers ago)
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(19);
   bufA.scale = CQ_SCALE_ACT; bufA.inv = 1.0f / CQ_SCALE_ACT;
   CqImg bufB2 = bufB;                                    // the dM2 image
@@ -826,7 +826,7 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
       }
     }
   }
-  cq_barrier();
+  lds_barrier();
   // ---- dSc = x1 . dM2^T ;  dXa (x1 rows) = Sc . dM2
   for (int tile = wave; tile < ni * nj; tile += CQ_WAVES) {
     const int ti = small_div(tile, nj), i0 = ti * 16, n0 = (tile - ti * nj) * 16;      // (no integer division: common.h)
@@ -843,7 +843,7 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
       if (i < c.N1) dXa[(size_t)(c.x1base + i) * HUAL_D + n0 + j] = acc[r];
     }
   }
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(20);
   cq_rows_store<1>(r2, bufA, N1q, bufB, N2q);          // D1W, D2 (activation scale on both)
   // ---- softmax backward -> dscore (in dSr).  mask_logits is multiplicative, so its derivative is the mask.
@@ -853,7 +853,7 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
     for (int i = 2 * wave + hh; i < c.N1p; i += 2 * CQ_WAVES) {
       const bool ok = i < c.N1 && l32 < c.N2;
       const float sr = ok ? cq_sc_load<LONG1, 1>(SrI, i, l32) : 0.f, ds = ok ? dSr[__mul24(i, c.ld) + l32] : 0.f;
-      const float dot = half_sum32(sr * ds);
+      const float dot = fast_sum32(sr * ds);
       if (ok) dSr[__mul24(i, c.ld) + l32] = sr * (ds - dot) * m2[l32];
     }
   } else {
@@ -865,20 +865,20 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
         dSr[__mul24(i, c.ld) + jj] = cq_sc_load<LONG1, 1>(SrI, i, jj) * (dSr[__mul24(i, c.ld) + jj] - dot) * m2[jj];
     }
   }
-  cq_barrier();
+  lds_barrier();
   float dmax = 0.f;                                       // largest |dscore| this thread produced
   if (c.N1p <= 32) {
     for (int jj = 2 * wave + hh; jj < c.N2p; jj += 2 * CQ_WAVES) {
       const bool ok = jj < c.N2 && l32 < c.N1;
       const float sc = ok ? cq_sc_load<LONG1, 1>(ScI, l32, jj) : 0.f, ds = ok ? dSc[__mul24(l32, c.ld) + jj] : 0.f;
-      const float dot = half_sum32(sc * ds);
+      const float dot = fast_sum32(sc * ds);
       float v = 0.f;
       if (ok) {
         v = dSr[__mul24(l32, c.ld) + jj] + sc * (ds - dot) * m1[l32];
         dSr[__mul24(l32, c.ld) + jj] = v;
       }
       dmax = fmaxf(dmax, fabsf(v));
-      const float colsum = half_sum32(v);
+      const float colsum = fast_sum32(v);
       if (l32 == 0 && jj < c.N2) gb.dS1[c.x2base + jj] = colsum;
     }
   } else {
@@ -898,7 +898,7 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
     }
   }
   cq_wgmax_put(mx1, dmax);
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(21);
   // row sums (d s0) and the dscore image (in place of the Sr image: both softmaxes are done with it)
   CqImg dscI = SrI;
@@ -906,7 +906,7 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
   if (c.N2p <= 32) {
     for (int i = 2 * wave + hh; i < N1q; i += 2 * CQ_WAVES) {
       const float v = (i < c.N1 && l32 < c.N2) ? dSr[__mul24(i, c.ld) + l32] : 0.f;
-      const float rowsum = half_sum32(v);
+      const float rowsum = fast_sum32(v);
       if (l32 == 0 && i < c.N1) gb.dS0[c.x1base + i] = rowsum;
       cq_sc_store<LONG1, 1>(dscI, i, l32, v);
     }
@@ -922,7 +922,7 @@ __device__ __forceinline__ void cq_bwd_staged_body(const CqBufs& b, const CqBwdB
       if (lane == 0 && i < c.N1) gb.dS0[c.x1base + i] = rowsum;
     }
   }
-  cq_barrier();
+  lds_barrier();
   CQ_STAMP(22);
   // ---- dD1W = dscore . d2 ;  dD2 = dscore^T . d1w
   for (int tile = wave; tile < ni * 8; tile += CQ_WAVES) {

@@ -51,13 +51,7 @@ __host__ __device__ inline size_t cq_m2_rows(int T, int L) {
 //   bufA (x1 rows), bufB (x2 rows): row images of the [rows,128] operands of the current phase (rows padded to 32 with zeros);
 //   SrI, ScI (dscore in the backward): the softmax matrices, stored with the LONGER of (N1, N2) along the 128 columns and the
 //   shorter one along the rows (template LONG1: N1 is the column index) - also the layout in which they are saved for the backward.
-// workgroup barrier that waits for the wave's LDS operations only: __syncthreads() also drains every outstanding global STORE of the
-// wave (s_waitcnt vmcnt(0)) - a store round trip in front of every phase; the staged kernels never read back their own global stores
-__device__ __forceinline__ void cq_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// (the phases are separated by lds_barrier(), wave.h: the staged kernels never read back their own global stores)
 // Element format of an image: FMT 0 - bf16 hi + lo (16 significant bits whatever the magnitude: the backward's gradient operands);
 // FMT 1 - fp16 hi + lo of x * scale with a FIXED power-of-two scale (22 significant bits down to |x| scale >= 2^-3, an absolute floor of
 // 2^-25 / scale below: the forward's activations (scale 2^4: |x| < 4096 or the product turns Inf / NaN, loudly) and softmax
@@ -75,15 +69,12 @@ __device__ __forceinline__ CqImg cq_img(char* p, int rows, float scale = 1.0f) {
 // one scale per image, because every image of the backward is read along its rows in one product and along its columns in another
 // (a per-row scale would not be constant along the second contraction).  amax = 0 / denormal: 2^113, still finite.
 __device__ __forceinline__ void cq_img_autoscale(CqImg& im, float amax) {
-  uint32_t eb = (__float_as_uint(amax) >> 23) & 0xffu;
-  eb = eb < 27u ? 27u : (eb > 240u ? 240u : eb);
-  im.scale = __uint_as_float((267u - eb) << 23);
-  im.inv = __uint_as_float((eb - 13u) << 23);
+  im.scale = pow2_scale<240u, 267u>(amax, im.inv);
 }
 // largest value over the workgroup: every wave leaves its maximum in its slot; the caller's next barrier publishes the slots
 // (cq_wgmax_get).  Slots are plain stores - no zeroing pass, no atomics; a slot row is reused only after a later barrier.
 __device__ __forceinline__ void cq_wgmax_put(float* slots, float v) {
-  v = wave_max64(v);
+  v = wave_max64_bperm(v);
   if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
 }
 __device__ __forceinline__ float cq_wgmax_get(const float* slots) {

@@ -77,7 +77,7 @@ extern "C" int hual_debug_cqw_wstamps(unsigned long long* out, int n) {
 #define CQW_STAMP() do { } while (0)
 #define CQW_WSTAMP(s, drain) do { } while (0)
 #endif
-#define CQW_BARRIER() do { CQW_STAMP(); cq_barrier(); CQW_STAMP(); } while (0)
+#define CQW_BARRIER() do { CQW_STAMP(); lds_barrier(); CQW_STAMP(); } while (0)
 
 struct CqwFrag { uint4 h[4], l[4]; };      // 16 rows x 128 columns of a wave as A fragments: k-step s = columns 32 s .. 32 s + 31
 // this lane's 32 columns of a row (rowp = the row's first element): x[2 s], x[2 s + 1] = columns 32 s + 8 g .. + 7
@@ -176,24 +176,6 @@ __device__ __forceinline__ f32x4 cqw_beta(f32x4 acc, const CqImg& Pb, int pk0, i
 // range-checked 16-byte / 4-byte row stores (common.h: a store that is not to happen gets the offset ROW_SKIP - no branch around it)
 __device__ __forceinline__ void cqw_st4(__amdgpu_buffer_rsrc_t r, bool ok, int row, int col, const f32x4& v, float scale) {
   bst4(r, ok ? (uint32_t)(row * HUAL_D + col) * 4u : ROW_SKIP, make_float4(v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale));
-}
-__device__ __forceinline__ float cqw_max16(float v) {      // over the 16 lanes of a row group (same g)
-  v = fmaxf(v, dpp_xor_partner(v, 1)); v = fmaxf(v, dpp_xor_partner(v, 2));
-  v = fmaxf(v, dpp_xor_partner(v, 4)); v = fmaxf(v, dpp_xor_partner(v, 8));
-  return v;
-}
-__device__ __forceinline__ float cqw_sum16(float v) {
-  v += dpp_xor_partner(v, 1); v += dpp_xor_partner(v, 2);
-  v += dpp_xor_partner(v, 4); v += dpp_xor_partner(v, 8);
-  return v;
-}
-__device__ __forceinline__ float cqw_gmax(float v) {       // over the four row groups (same j)
-  v = fmaxf(v, lane_xor16_partner(v));
-  return fmaxf(v, lane_xor32_partner(v));
-}
-__device__ __forceinline__ float cqw_gsum(float v) {
-  v += lane_xor16_partner(v);
-  return v + lane_xor32_partner(v);
 }
 // elements (row, col .. col + 3) of an image, col % 4 == 0
 __device__ __forceinline__ f32x4 cqw_img_load4(const CqImg& im, int row, int col) {
@@ -344,7 +326,7 @@ __device__ __forceinline__ void cqw_fwd_body(const CqBufs& b, const CqParams& p,
       }
       x[2 * s] = a; x[2 * s + 1] = c;
     }
-    term = cqw_gsum(term);
+    term = slice16_sum(term);
     if (g == 0) tlong[q.lrow] = q.lok ? term : 0.f;
     cqw_split(x, CQ_SCALE_ACT, fa);
     const uint32_t ro = (uint32_t)((q.lbase + q.lrow) * HUAL_D + 8 * g) * 4u;      // (ROW_SKIP per store: it must not be offset)
@@ -365,7 +347,7 @@ __device__ __forceinline__ void cqw_fwd_body(const CqBufs& b, const CqParams& p,
       const uint32_t bits = drop_bits8_r(dr, site_short, (uint32_t)(q.sbase + min(k, q.Ns - 1)), (uint32_t)(q.c4 >> 1));
       o = f4_select((bits >> (4 * (q.c4 & 1))) & 15u, f4scale1(xs[u], dr.scale));
     }
-    const float sv = half_sum32(o.x * wS.x + o.y * wS.y + o.z * wS.z + o.w * wS.w);
+    const float sv = fast_sum32(o.x * wS.x + o.y * wS.y + o.z * wS.z + o.w * wS.w);
     if (DIR == 1) o = make_float4(o.x * mS.x, o.y * mS.y, o.z * mS.z, o.w * mS.w);
     if (q.c4 == 0) tshort[k] = sok ? sv : 0.f;
     cq_img_store4<1>(simg, k, 4 * q.c4, o);
@@ -398,19 +380,19 @@ __device__ __forceinline__ void cqw_fwd_body(const CqBufs& b, const CqParams& p,
         mxs[r] = fmaxf(mxs[r], Ps[nt][r]);
         wmax[nt] = fmaxf(wmax[nt], lgl[nt][r]);
       }
-      wmax[nt] = cqw_gmax(wmax[nt]);
+      wmax[nt] = slice16_max(wmax[nt]);
     }
     float sums[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      mxs[r] = cqw_max16(mxs[r]);
+      mxs[r] = fast_max16(mxs[r]);
       float e = 0.f;
 #pragma unroll
       for (int nt = 0; nt < NTS; ++nt) {
         Ps[nt][r] = valid[nt][r] ? __expf(Ps[nt][r] - mxs[r]) : 0.f;
         e += Ps[nt][r];
       }
-      sums[r] = 1.0f / cqw_sum16(e);
+      sums[r] = 1.0f / fast_sum16(e);
     }
 #pragma unroll
     for (int nt = 0; nt < NTS; ++nt) {
@@ -420,7 +402,7 @@ __device__ __forceinline__ void cqw_fwd_body(const CqBufs& b, const CqParams& p,
         Ps[nt][r] = valid[nt][r] ? Ps[nt][r] * sums[r] : 0.f;
         ws += valid[nt][r] ? __expf(lgl[nt][r] - wmax[nt]) : 0.f;
       }
-      ws = cqw_gsum(ws);
+      ws = slice16_sum(ws);
       if (g == 0) { ca[q.wave * SQ + 16 * nt + j] = wmax[nt]; cb[q.wave * SQ + 16 * nt + j] = ws; }
       cq_img_store4<1>(cqw_blk<SQ>(lds, L.ps, q.lblk), 16 * nt + j, q.lc0 + 4 * g, cqw_f4(Ps[nt]));
     }
@@ -668,11 +650,11 @@ __device__ __forceinline__ void cqw_bwd_body(const CqBufs& b, const CqBwdBufs& g
           dots[r] = fmaf(a[r], dps[nt][r], dots[r]);
           part = fmaf(c[r], dpl[nt][r], part);
         }
-        part = cqw_gsum(part);
+        part = slice16_sum(part);
         if (g == 0) ca[q.wave * SQ + 16 * nt + j] = part;
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) dots[r] = cqw_sum16(dots[r]);
+      for (int r = 0; r < 4; ++r) dots[r] = fast_sum16(dots[r]);
     }
   };
   // ... part 2: dscore in registers, its sums along the short axis out, its sums along the long axis and its maximum into LDS
@@ -696,12 +678,12 @@ __device__ __forceinline__ void cqw_bwd_body(const CqBufs& b, const CqBwdBufs& g
           part += v;
           dmax = fmaxf(dmax, fabsf(v));
         }
-        part = cqw_gsum(part);
+        part = slice16_sum(part);
         if (g == 0) cb[q.wave * SQ + col] = part;
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float v = cqw_sum16(rs4[r]);
+        const float v = fast_sum16(rs4[r]);
         const int l = q.l0 + 4 * g + r;
         bst1(rdsl, (j == 0 && l < q.Nl) ? (uint32_t)(q.lbase + l) * 4u : ROW_SKIP, v);
       }

@@ -7,14 +7,6 @@
 
 using namespace hual;
 
-// maximum over the 16 lanes that share lane >> 4 (one DPP row): the lanes holding the 64 columns of a tile row
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, dpp_xor_partner(v, 1));
-  v = fmaxf(v, dpp_xor_partner(v, 2));
-  v = fmaxf(v, dpp_xor_partner(v, 4));
-  v = fmaxf(v, dpp_xor_partner(v, 8));
-  return v;
-}
 __device__ __forceinline__ float4 sig4(float4 v) { return make_float4(sigmoidf_(v.x), sigmoidf_(v.y), sigmoidf_(v.z), sigmoidf_(v.w)); }
 
 #include "lnproj_body.h"      // ln_row(), ln_proj_body<NT>
@@ -181,7 +173,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
 
   float4 SV[NT], XV[NT], T1[NT], T2[NT];
   // ---- s_value = s_att . Ws + b ; x_value = x_att . Wx + b  (layers.py:93-94)
-  cb_barrier();
+  lds_barrier();
   tf_mma_lean<NT, DP_PLANE>(P0, wa, lane, accp);
   fold(SV, ainv0, true);
   tf_load_w(wa, a.w[2], wave, lane);
@@ -199,7 +191,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
   zero_invalid(XV);
   put(P2, ainv2, SV);
   put(P3, ainv3, XV);
-  cb_barrier();
+  lds_barrier();
   // ---- cross gating (layers.py:96-103): o = sigmoid(s_value . Wsg + b) * x_value + sigmoid(x_value . Wxg + b) * s_value
   tf_mma_lean<NT, DP_PLANE>(P2, wa, lane, accp);
   fold(T1, ainv2, true);
@@ -217,7 +209,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
   }
   zero_invalid(T1);
   put(P0, ainv0, T1);                                        // (slot 0: last read by the s_value product, a barrier ago)
-  cb_barrier();
+  lds_barrier();
   // ---- guided dense (layers.py:104)
   tf_mma_lean<NT, DP_PLANE>(P0, wa, lane, accp);
   tf_load_w(wa, a.w[6], wave, lane);
@@ -235,7 +227,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
     const float i0 = cb_store_operand_fx(P1, P1 + DP_PLANE, lr, l32, ok ? l1[u] : f4zero());
     if (l32 == 0) ainv1[lr] = ok ? i0 : 0.f;
   }
-  cb_barrier();
+  lds_barrier();
   // ---- bilinear gate and value (layers.py:48-56, 106-110): scores = ln1 . W11 + g . W12 + b1 ; values = ln1 . W21 + g . W22 + b2
   tf_mma_lean<NT, DP_PLANE>(P1, wb, lane, accp);
   fold(T1, ainv1, true);
@@ -261,7 +253,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
   }
   zero_invalid(T1);
   put(P3, ainv3, T1);                                        // (slot 3: last read by the x_gate product, two barriers ago)
-  cb_barrier();
+  lds_barrier();
   // ---- dense_1 + dropout + residual (modules.py:82-83); the rows also go to LDS as fp32 for the layer norm
   tf_mma_lean<NT, DP_PLANE>(P3, wb, lane, accp);
   fold(SV, ainv3, true);                                      // SV now holds `res`
@@ -281,7 +273,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
       scratch[lr * 32 + (ecol >> 2)] = v;                     // (slot 0 was last read two products ago)
     }
   }
-  cb_barrier();
+  lds_barrier();
   // ---- RP2: layer_norm_2 + dropout (modules.py:85-86) -> slot 2
   {
     const float4 g2 = bl[9 * 32 + l32], b2 = bl[10 * 32 + l32];
@@ -311,7 +303,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
       if (l32 == 0) ainv2[lr] = ok ? i2 : 0.f;
     }
   }
-  cb_barrier();
+  lds_barrier();
   // ---- dense_2 + dropout + residual (modules.py:87-88)
   tf_mma_lean<NT, DP_PLANE>(P2, wa, lane, accp);
   fold(T1, ainv2, true);
@@ -330,7 +322,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
     }
   }
   if (TAIL) {
-    cb_barrier();      // the rows are complete, and every wave is through its last product (slot 2)
+    lds_barrier();      // the rows are complete, and every wave is through its last product (slot 2)
     ln_proj_body<NT, true, true>(*lp, drop, P1, r0, scratch, r0, 32, DP_ROWS, TP);
   }
 }
@@ -486,7 +478,7 @@ __device__ __forceinline__ bool ln_proj_bwd_body(const LnProjBwdArgs& a, const D
       }
       tf_load_w(w[(k + 1) & 1], a.wimg_t[k + 1], wave, lane);
     }
-    cb_barrier();
+    lds_barrier();
     HUAL_STAMP_K(4, 2 + 3 * k);
     const char* S = (k & 1) ? S1 : S0;
     const float* ai = (k & 1) ? ainv1 : ainv0;
@@ -509,7 +501,7 @@ __device__ __forceinline__ bool ln_proj_bwd_body(const LnProjBwdArgs& a, const D
     if (more) fill(k + 1);                             // slot (k+1)&1 was last read by product k-1
     HUAL_STAMP_K(4, 4 + 3 * k);
   }
-  cb_barrier();                                        // every wave is through the last product: both slots are free
+  lds_barrier();                                        // every wave is through the last product: both slots are free
   HUAL_STAMP_K(4, 20);
   // ---- the two output-gradient tiles -> LDS as fp32 rows
   float4* D0 = reinterpret_cast<float4*>(S0);
@@ -547,7 +539,7 @@ __device__ __forceinline__ bool ln_proj_bwd_body(const LnProjBwdArgs& a, const D
 #pragma unroll
     for (int u = 0; u < LB_U; ++u) zv[u] = f4zero();
   }
-  cb_barrier();
+  lds_barrier();
   HUAL_STAMP_K(4, 21);
   // ---- row phase: layer norm(s) backward.  dy = dy*g ; dx = rstd * (gv - mean(gv) - xhat * mean(gv * xhat))   (ln_bwd_kernel)
   float4 sg1 = f4zero(), sb1 = f4zero();
@@ -597,7 +589,7 @@ __device__ __forceinline__ bool ln_proj_bwd_body(const LnProjBwdArgs& a, const D
       float4* dst = pb + wave * 4 * 32 + l32;
       dst[0] = sg1; dst[32] = sb1; dst[64] = sg2; dst[96] = sb2;
     }
-    cb_barrier();
+    lds_barrier();
     const float* pf = reinterpret_cast<const float*>(pb);
     const int e = threadIdx.x;                         // 4 x 128 sums, one per thread
     float s = 0.f;
@@ -723,7 +715,7 @@ __device__ __forceinline__ void da_mid_bwd_body(const DaMidBwdArgs& a, char* dm_
     tile_ld(a.gate, U1);
     tile_ld(a.val, U2);
   }
-  cb_barrier();
+  lds_barrier();
   tf_mma_lean<NT, DP_PLANE>(P1, wa, lane, accp);
   tf_load_w(wa, a.w[2], wave, lane);                   // (requests go in front of the epilogue's stores, here and below)
   fold(T1, ainv1, true);
@@ -740,10 +732,10 @@ __device__ __forceinline__ void da_mid_bwd_body(const DaMidBwdArgs& a, char* dm_
   zero_invalid(T2);
   put_max(smaxA, T1);
   put_max(smaxB, T2);
-  cb_barrier();
+  lds_barrier();
   put_planes(P0, ainv0, smaxA, T1);
   put_planes(P2, ainv2, smaxB, T2);
-  cb_barrier();
+  lds_barrier();
   // ---- gradient of ln1 through the two bilinear layers: d scores . W11^T + d values . W21^T
   tf_mma_lean<NT, DP_PLANE>(P0, wb, lane, accp);
   fold(T1, ainv0, true);
@@ -769,9 +761,9 @@ __device__ __forceinline__ void da_mid_bwd_body(const DaMidBwdArgs& a, char* dm_
   for (int rt = 0; rt < NT; ++rt) save_nt(a.d_g, rt, T2[rt]);
   zero_invalid(T2);
   put_max(smaxA, T2);
-  cb_barrier();
+  lds_barrier();
   put_planes(P1, ainv1, smaxA, T2);
-  cb_barrier();
+  lds_barrier();
   // ---- d o = d g . Wg^T ; cross gating backward (layers.py:96-103): o = sg * x + xg * s
   tf_mma_lean<NT, DP_PLANE>(P1, wb, lane, accp);
   tf_load_w(wb, a.w[7], wave, lane);
@@ -792,10 +784,10 @@ __device__ __forceinline__ void da_mid_bwd_body(const DaMidBwdArgs& a, char* dm_
   zero_invalid(T2);
   put_max(smaxA, T1);
   put_max(smaxB, T2);
-  cb_barrier();
+  lds_barrier();
   put_planes(P0, ainv0, smaxA, T1);
   put_planes(P2, ainv2, smaxB, T2);
-  cb_barrier();
+  lds_barrier();
   // ---- d s_value = dZ_sg . Wsg^T + d o * xg ; d x_value = dZ_xg . Wxg^T + d o * sg
   tf_mma_lean<NT, DP_PLANE>(P0, wa, lane, accp);
   fold(T1, ainv0, true);
@@ -814,10 +806,10 @@ __device__ __forceinline__ void da_mid_bwd_body(const DaMidBwdArgs& a, char* dm_
   zero_invalid(T2);
   put_max(smaxA, T1);
   put_max(smaxB, T2);
-  cb_barrier();
+  lds_barrier();
   put_planes(P1, ainv1, smaxA, T1);
   put_planes(P0, ainv0, smaxB, T2);
-  cb_barrier();
+  lds_barrier();
   // ---- gradients of the two attention outputs
   tf_mma_lean<NT, DP_PLANE>(P1, wa, lane, accp);
   fold(T1, ainv1, true);

@@ -469,10 +469,8 @@ __device__ __forceinline__ void dw_f16_segment(const DwJob& job, const int p, co
       ma = fmaxf(ma, f4absmax(a));
     }
     if (adrop) ma *= drop.scale;
-    m = fast_max32(m);
-    m = fmaxf(m, lane_xor32_partner(m));
-    ma = fast_max32(ma);
-    ma = fmaxf(ma, lane_xor32_partner(ma));
+    m = wave_max64(m);
+    ma = wave_max64(ma);
     if (lane == 0) { mxs[par * 16 + wave] = m; mxs[par * 16 + 8 + wave] = ma; }
   };
   // ... and the scale for the tile whose maxima sit in row `par`: the first tile sets it, a later one only lowers it
@@ -490,9 +488,8 @@ __device__ __forceinline__ void dw_f16_segment(const DwJob& job, const int p, co
     // tile would pass 2^14
     auto running = [&](float g, float& sc, float& sc_inv) {
       if (sc == 0.f || g * sc > 16384.0f) {      // (uniform)
-        uint32_t eb = (__float_as_uint(g) >> 23) & 0xffu;
-        eb = eb < 27u ? 27u : (eb > 240u ? 240u : eb);
-        const float s_new = __uint_as_float((265u - eb) << 23);
+        float inv_new;
+        const float s_new = pow2_scale<240u, 265u>(g, inv_new);
         if (sc != 0.f) {
           const float f = s_new * sc_inv;                              // < 1, exact
 #pragma unroll
@@ -501,7 +498,7 @@ __device__ __forceinline__ void dw_f16_segment(const DwJob& job, const int p, co
             for (int r = 0; r < 16; ++r) acc[c][r] *= f;
         }
         sc = s_new;
-        sc_inv = __uint_as_float((eb - 11u) << 23);
+        sc_inv = inv_new;
       }
     };
     running(wgmax(mxs + par * 16), s_y, s_y_inv);

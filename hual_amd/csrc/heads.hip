@@ -38,7 +38,7 @@ __device__ __forceinline__ double block_sum_d(double v, double* sm) {
   return s;
 }
 __device__ __forceinline__ float block_max(float v, float* sm) {
-  v = wave_max64(v);
+  v = wave_max64_bperm(v);
   const int w = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sm[w] = v;
@@ -66,7 +66,7 @@ __device__ __forceinline__ void pool_fwd_body(const PoolArgs& a, const RowSpace&
     const float4 w4 = ld4(a.wp + 4 * l32);
     for (int l = grp; l < L; l += 8) {
       const float4 f = ld4(F + (size_t)l * HUAL_D + 4 * l32);
-      const float d = half_sum32(f.x * w4.x + f.y * w4.y + f.z * w4.z + f.w * w4.w);
+      const float d = fast_sum32(f.x * w4.x + f.y * w4.y + f.z * w4.z + f.w * w4.w);
       if (l32 == 0) al[l] = d * m[l] + HUAL_MASK_VALUE * (1.0f - m[l]);   // mask_logits, layers.py:139
     }
   }
@@ -121,7 +121,7 @@ __device__ __forceinline__ void match_fwd_body(const MatchArgs& a, const RowSpac
     float l1 = f.x * w0.y + f.y * w1.y + f.z * w2.y + f.w * w3.y;
     float l2 = f.x * w0.z + f.y * w1.z + f.z * w2.z + f.w * w3.z;
     float l3 = f.x * w0.w + f.y * w1.w + f.z * w2.w + f.w * w3.w;
-    l0 = half_sum32(l0) + bm.x; l1 = half_sum32(l1) + bm.y; l2 = half_sum32(l2) + bm.z; l3 = half_sum32(l3) + bm.w;
+    l0 = fast_sum32(l0) + bm.x; l1 = fast_sum32(l1) + bm.y; l2 = fast_sum32(l2) + bm.z; l3 = fast_sum32(l3) + bm.w;
     if (a.rng) {      // gumbel noise (ops.py:6-9): u on the 2^-24 grid from the four words of one call, oracle/philox.py gumbel_uniform
       const uint4_ r = philox4x32(0u, (uint32_t)row, (uint32_t)HUAL_SITE_GUMBEL, gk.z, gk.x, gk.y);
       l0 = (l0 + gumbel_noise(r.x)) * a.inv_tau; l1 = (l1 + gumbel_noise(r.y)) * a.inv_tau;
@@ -204,10 +204,10 @@ __global__ __launch_bounds__(256) void match_bwd_kernel(MatchArgs a, MatchBwd g,
       pp = *reinterpret_cast<const float4*>(a.probs + (size_t)rn * 4);
     }
     d = make_float4(d.x * mk, d.y * mk, d.z * mk, d.w * mk);   // through the *v_mask of model.py:97
-    float q0 = half_sum32(d.x * e0.x + d.y * e0.y + d.z * e0.z + d.w * e0.w);
-    float q1 = half_sum32(d.x * e1.x + d.y * e1.y + d.z * e1.z + d.w * e1.w);
-    float q2 = half_sum32(d.x * e2.x + d.y * e2.y + d.z * e2.z + d.w * e2.w);
-    float q3 = half_sum32(d.x * e3.x + d.y * e3.y + d.z * e3.z + d.w * e3.w);
+    float q0 = fast_sum32(d.x * e0.x + d.y * e0.y + d.z * e0.z + d.w * e0.w);
+    float q1 = fast_sum32(d.x * e1.x + d.y * e1.y + d.z * e1.z + d.w * e1.w);
+    float q2 = fast_sum32(d.x * e2.x + d.y * e2.y + d.z * e2.z + d.w * e2.w);
+    float q3 = fast_sum32(d.x * e3.x + d.y * e3.y + d.z * e3.z + d.w * e3.w);
     const float dot = p.x * q0 + p.y * q1 + p.z * q2 + p.w * q3;
     float dl0 = p.x * (q0 - dot), dl1 = p.y * (q1 - dot), dl2 = p.z * (q2 - dot), dl3 = p.w * (q3 - dot);
     if (a.labels) {
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void match_bwd_kernel(MatchArgs a, MatchBwd g,
 // With `h` null the logits are read instead of computed (hual_span_argmax).
 // two block-wide reductions for one pair of barriers
 __device__ __forceinline__ void block_max2(float& a, float& b, float* sm) {       // sm: 2 * (blockDim.x / 64) floats
-  a = wave_max64(a); b = wave_max64(b);
+  a = wave_max64_bperm(a); b = wave_max64_bperm(b);
   const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) { sm[w] = a; sm[nw + w] = b; }
@@ -343,8 +343,8 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a, int T, int B) {
 #pragma unroll
     for (int u = 0; u < NR; ++u) {
       const int t = grp + 16 * u;
-      const float ds = half_sum32(hs[u].x * ws.x + hs[u].y * ws.y + hs[u].z * ws.z + hs[u].w * ws.w) + bs;
-      const float de = half_sum32(he[u].x * we.x + he[u].y * we.y + he[u].z * we.z + he[u].w * we.w) + be;
+      const float ds = fast_sum32(hs[u].x * ws.x + hs[u].y * ws.y + hs[u].z * ws.z + hs[u].w * ws.w) + bs;
+      const float de = fast_sum32(he[u].x * we.x + he[u].y * we.y + he[u].z * we.z + he[u].w * we.w) + be;
       if (l32 == 0 && t < T) { zs_[t] = ds; ze_[t] = de; a.logit[0][b * T + t] = ds; a.logit[1][b * T + t] = de; }
     }
   } else if (tid < T) {

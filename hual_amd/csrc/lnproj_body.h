@@ -155,7 +155,7 @@ __device__ __forceinline__ void ln_proj_body(const hual::LnProjArgs& a, const hu
   for (int p = 0; p < HUAL_LNPROJ_MAX; ++p) {
     if (p >= a.nproj) break;                                 // uniform
     tf_load_w_if(w[(p + 1) & 1], a.wimg[p + 1 < a.nproj ? p + 1 : p], p + 1 < a.nproj, wave, lane);      // (straight-line: no traffic behind the last one)
-    if (p == 0) cb_barrier();
+    if (p == 0) lds_barrier();
     if (FUSED && p == 0) HUAL_STAMP_K(2, 27);
     const char* P = a.src[p] ? P2 : P1;
     const float* ai = a.src[p] ? ainv2 : ainv1;

@@ -197,7 +197,7 @@ __device__ __forceinline__ void mproj_body(const MProjArgs& a, const DropCfg& dr
       rows_load(nxt);
     }
     MP_STAMP(4 + 7 * k);
-    cb_barrier();                                       // operand planes of this step complete (LDS only: nothing waits for HBM here)
+    lds_barrier();                                       // operand planes of this step complete (LDS only: nothing waits for HBM here)
     MP_STAMP(5 + 7 * k);
     const char* S = slot ? S1 : S0;
     const float* ai = slot ? ainv1 : ainv0;
@@ -302,13 +302,13 @@ __device__ __forceinline__ void mproj_body(const MProjArgs& a, const DropCfg& dr
   if (!(F & MPF_LN) || !a.ln_g) return;
   // ---- LN mode: the last tile (+ bias) -> LDS as fp32 rows -> layer norm (+ position embeddings) row by row
   float4* D0 = reinterpret_cast<float4*>(S0);                // both slots are free behind the last matrix phase (barrier above)
-  cb_barrier();                                         // every wave is past the last matrix phase
+  lds_barrier();                                         // every wave is past the last matrix phase
   {
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) D0[(16 * rt + j) * 32 + (ecol >> 2)] = cb_add(acc[rt], lastb);
   }
   const float4 gam = ld4(a.ln_g + col), bet = ld4(a.ln_b + col);
-  cb_barrier();
+  lds_barrier();
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     const int lr = grp + 16 * u, row = r0 + lr;

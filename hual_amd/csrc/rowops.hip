@@ -21,9 +21,9 @@ __device__ __forceinline__ float4 f4fma_(float4 a, float4 b, float4 c) {
 
 // mean / rstd of one row held as one float4 per lane of a 32-lane half (biased variance, layers.py:13-15)
 __device__ __forceinline__ void row_stats(float4 v, float& mean, float& rstd) {
-  mean = half_sum32(f4hsum_(v)) * (1.0f / HUAL_D);
+  mean = fast_sum32(f4hsum_(v)) * (1.0f / HUAL_D);
   float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
-  float var = half_sum32(f4hsum_(f4mul_(d, d))) * (1.0f / HUAL_D);
+  float var = fast_sum32(f4hsum_(f4mul_(d, d))) * (1.0f / HUAL_D);
   rstd = rsqrtf(var + LN_EPS);
 }
 
@@ -103,8 +103,8 @@ __device__ __forceinline__ void ln_bwd_body(const LnBwd& a, const DropCfg& drop,
       sg2 = f4fma_(dy2, xh, sg2);
       gv = f4fma_(dy2, g2, gv);
     }
-    float m1 = half_sum32(f4hsum_(gv)) * (1.0f / HUAL_D);
-    float m2 = half_sum32(f4hsum_(f4mul_(gv, xh))) * (1.0f / HUAL_D);
+    float m1 = fast_sum32(f4hsum_(gv)) * (1.0f / HUAL_D);
+    float m2 = fast_sum32(f4hsum_(f4mul_(gv, xh))) * (1.0f / HUAL_D);
     float4 dx = make_float4(rstd * (gv.x - m1 - xh.x * m2), rstd * (gv.y - m1 - xh.y * m2),
                             rstd * (gv.z - m1 - xh.z * m2), rstd * (gv.w - m1 - xh.w * m2));
     if (a.add1) dx = f4add_(dx, ld4(a.add1 + off));

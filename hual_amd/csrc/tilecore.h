@@ -46,8 +46,6 @@ __device__ __forceinline__ float4 cb_mul(float4 a, float4 b) { return make_float
 __device__ __forceinline__ float4 cb_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float cb_hsum(float4 a) { return (a.x + a.y) + (a.z + a.w); }
 
-// (the 32-lane butterfly reductions fast_sum32 / fast_max32 live in common.h)
-
 // ---- dropout with the Philox key / offset held in registers ---------------------------------------------------------------
 // philox.h's drop_mask4 reads the three state words from global memory on every call; in a latency-bound fused kernel that
 // is a memory round trip per call (and, next to an LDS-DMA in flight, a vmcnt(0) that also waits for every store issued
@@ -135,16 +133,6 @@ __device__ __forceinline__ void cb_segment(int row, const hual::RowSpace& rs, in
   const int n = v ? rs.T : rs.L, base = v ? 0 : rs.Nv;
   lo = base + __mul24(small_div(row - base, n), n);
   hi = lo + n;
-}
-
-// Workgroup barrier for LDS hand-offs only.  __syncthreads() is a workgroup-scope fence + s_barrier, and the fence makes
-// hipcc wait for every outstanding global store of the wave (s_waitcnt vmcnt(0)) - at one workgroup per CU that puts a
-// store round trip in front of every barrier of an epilogue.  The fused kernels never read back their own global
-// stores, so they only wait for their LDS operations.
-__device__ __forceinline__ void cb_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // ---- "T-form" tile product: register-resident weights -----------------------------------------------------------------
@@ -273,22 +261,6 @@ __device__ __forceinline__ void tf_mma_regs(const TfA<NT>& x, const TfW& w, f32x
     }
 }
 
-// lane partners across the 16-lane rows of a wave (v_permlane16_swap / v_permlane32_swap, one instruction each) and the maximum
-// over the four lanes (j, 0..3) that hold one row's 16-column slice in the T-form accumulator layout
-__device__ __forceinline__ float lane_xor16(float v, int lane) {
-  const unsigned x = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-  return __builtin_bit_cast(float, (lane & 16) ? r[0] : r[1]);
-}
-__device__ __forceinline__ float lane_xor32(float v, int lane) {
-  const unsigned x = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return __builtin_bit_cast(float, (lane & 32) ? r[0] : r[1]);
-}
-__device__ __forceinline__ float slice16_max(float v, int lane) {
-  v = fmaxf(v, lane_xor16(v, lane));
-  return fmaxf(v, lane_xor32(v, lane));
-}
 // drop_nib2_store_r for the T-form accumulator layout: col4 = 4 wave + (lane >> 4), the lane with the other half of the 8-column group
 // is lane ^ 16.  The even lane of the pair draws rowA's call, the odd one rowB's (rowB = rowA with okB = false: a single row - both
 // draw the same call); all lanes of the wave must be active

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(TK_THREADS) void span_topk_kernel(const float* __re
       zs = t < v ? zs_[row + t] : HUAL_MASK_VALUE;      // (= x * 0 + HUAL_MASK_VALUE for a finite padding logit, never read here)
       ze = t < v ? ze_[row + t] : HUAL_MASK_VALUE;
     }
-    float mxs = wave_max64(zs), mxe = wave_max64(ze);
+    float mxs = wave_max64_bperm(zs), mxe = wave_max64_bperm(ze);
     if (lane == 0) { smf[w] = mxs; smf[TK_WAVES + w] = mxe; }
     __syncthreads();
     mxs = -INFINITY; mxe = -INFINITY;

@@ -135,8 +135,14 @@ def test_conv_block_fwd_bwd(shape):
 DA_LONG_SHAPES = [dict(B=2, T=256, L=20, C=4, seed=41, max_vlen=256), dict(B=3, T=170, L=9, C=4, seed=42, max_vlen=192),
                   dict(B=2, T=131, L=12, C=4, seed=43, max_vlen=160)]
 
+# clip counts that are a multiple of 8 give every XCD whole clips: the backward's workgroup -> (job, clip) maps take their XCD-grouped
+# branch (csrc/attn.hip attn_bwd_job_clip, and the chain kernel's own map).  The smallest shapes that reach the chain kernel, the
+# eight-wave kernel and attn_bwd_kernel with four jobs (36 query words: no chain) that way, and the last one's interleaved fallback
+DA_GROUPED_SHAPES = [dict(B=8, T=24, L=9, C=4, seed=51, max_vlen=24), dict(B=8, T=136, L=8, C=4, seed=52, max_vlen=160),
+                     dict(B=8, T=40, L=36, C=4, seed=53, max_vlen=40), dict(B=3, T=40, L=36, C=4, seed=54, max_vlen=40)]
 
-@pytest.mark.parametrize('shape', SHAPES + DA_LONG_SHAPES)
+
+@pytest.mark.parametrize('shape', SHAPES + DA_LONG_SHAPES + DA_GROUPED_SHAPES)
 @pytest.mark.parametrize('layer', [0, 1])
 def test_dual_attn_fwd_bwd(shape, layer):
     blk = Block(**shape)
