@@ -20,6 +20,12 @@ K-pass uncertainty (neither has): infer_trainset(mc_dropout=0.5, mc_samples=K, b
 and folds each into a device-resident bank of per-frame statistics (hual_al_mc_fold); no stochastic logit reaches the host, the records
 carry 'prop_uncert' instead of 'prop_logits1/2', and LabelUpdater.from_bank / update_labels(bank=) score straight from the bank
 (hual_al_score_mc).  Without mc_samples every launch, record and result is what it was.
+
+Information-theoretic acquisition (neither has): mc_stat 'bald', 'entropy' or 'expected_entropy' instead of 'range' / 'std' - the
+mutual information between prediction and dropout mask, the entropy of the mean prediction and the mean entropy of the passes, in bits,
+summed over the two heads: each in [0, 2] at every K.  They need a McBank built with info=True, whose folds (hual_al_mc_fold_info) also
+keep the running mean of the per-pass entropy, and are scored by hual_al_score_info.  Without those names every launch, record and
+result is what it was.
 """
 import ctypes
 import math
@@ -52,14 +58,19 @@ def get_coff(task, I):
 
 
 # ---------------------------------------------------------------- K-pass uncertainty bank ---------
+STAT_NAMES = "the statistic is 'range' or 'std', or - from a McBank with info=True - 'bald', 'entropy' or 'expected_entropy'"
+
+
 class McBank:
     """Per-sample statistics of K stochastic forwards over a training set of N samples, resident on the device (hual_al_bank):
     tlen i32 [N]; the deterministic logits s0 / e0 f32 [N, ld]; per head (0 = start, 1 = end) the minimum, maximum, Welford mean and
     sum of squared deviations of the per-frame probabilities, stats f32 [2, 4, N, ld] = [head, (lo, hi, mean, m2)].
-    K: the number of stochastic passes folded so far (the largest k seen since the last k = 1)."""
+    K: the number of stochastic passes folded so far (the largest k seen since the last k = 1).
+    info=True adds ent f32 [2, N, ld] (hual_al_info): per head the running mean of the passes' binary entropy h2(p_k) in bits, folded by
+    the same launch (hual_al_mc_fold_info) - what the statistics 'bald', 'entropy' and 'expected_entropy' are read from."""
     FIELDS = ('lo', 'hi', 'mean', 'm2')
 
-    def __init__(self, N, ld, device='cuda:0'):
+    def __init__(self, N, ld, device='cuda:0', info=False):
         if not torch.cuda.is_available():
             raise lib.HualError('McBank needs a GPU: the HIP path has no CPU fallback')
         if N < 1 or not 2 <= ld <= 1024:
@@ -71,21 +82,30 @@ class McBank:
         self.s0 = torch.zeros(N, ld, device=self.dev)
         self.e0 = torch.zeros(N, ld, device=self.dev)
         self.stats = torch.zeros(2, 4, N, ld, device=self.dev)
+        self.ent = torch.zeros(2, N, ld, device=self.dev) if info else None
         self._bind()
 
     @classmethod
-    def for_dataset(cls, dataset, device='cuda:0'):
+    def for_dataset(cls, dataset, device='cuda:0', info=False):
         """a bank over a DeviceDataset: one row per sample, as wide as its longest clip"""
-        return cls(len(dataset), max(2, int(np.max(dataset.vlen_h))), device=device)
+        return cls(len(dataset), max(2, int(np.max(dataset.vlen_h))), device=device, info=info)
 
     def _bind(self):
         a, st = lib._addr, self.stats
         self.c = lib.hual_al_bank(self.N, self.ld, a(self.tlen), a(self.s0), a(self.e0), a(st[0, 0]), a(st[0, 1]), a(st[0, 2]), a(st[0, 3]),
                                   a(st[1, 0]), a(st[1, 1]), a(st[1, 2]), a(st[1, 3]))
+        self.info_c = lib.hual_al_info(a(self.ent[0]), a(self.ent[1])) if self.ent is not None else None
 
     def stat(self, head, name):
-        """[N, ld] view: head 0 = start / 1 = end, name in ('lo', 'hi', 'mean', 'm2')"""
+        """[N, ld] view: head 0 = start / 1 = end, name in ('lo', 'hi', 'mean', 'm2'), and 'ent' on a bank with info=True"""
+        if name == 'ent':
+            self.need_info('ent')
+            return self.ent[head]
         return self.stats[head, self.FIELDS.index(name)]
+
+    def need_info(self, what):
+        if self.ent is None:
+            raise lib.HualError("McBank: '%s' needs the passes' entropy, which this bank does not fold - build the bank with info=True" % what)
 
     def rows(self, ids):
         """device i32 row ids of one fold, checked on the host: inside the bank, none twice (the rows of a launch must be disjoint)"""
@@ -109,15 +129,24 @@ class McBank:
         vl = v_len.to(device=self.dev, dtype=torch.int32).contiguous()
         if ids.numel() != B or vl.numel() != B:
             raise lib.HualError('McBank.fold: ids and v_len must hold B = %d entries' % B)
-        lib.check(self._lib.hual_al_mc_fold(ctypes.byref(self.c), lib.ptr(ids), lib.ptr(vl), lib.ptr(s), lib.ptr(e), B, T, int(k),
-                                            lib.stream_ptr()))
+        if self.ent is not None:
+            lib.check(self._lib.hual_al_mc_fold_info(ctypes.byref(self.c), ctypes.byref(self.info_c), lib.ptr(ids), lib.ptr(vl), lib.ptr(s),
+                                                     lib.ptr(e), B, T, int(k), lib.stream_ptr()))
+        else:
+            lib.check(self._lib.hual_al_mc_fold(ctypes.byref(self.c), lib.ptr(ids), lib.ptr(vl), lib.ptr(s), lib.ptr(e), B, T, int(k),
+                                                lib.stream_ptr()))
         if k >= 1:
             self.K = int(k) if k == 1 else max(self.K, int(k))
 
     def uncert(self, K=None, stat='range'):
-        """the model-uncertainty term f32 [N, ld] of every frame as hual_al_score_mc computes it (by that launch itself, so a value read
-        here is the value a later score uses, bit for bit); columns beyond a row's tlen are 0"""
+        """the model-uncertainty term f32 [N, ld] of every frame as hual_al_score_mc ('range', 'std') or hual_al_score_info ('bald',
+        'entropy', 'expected_entropy'; a bank with info=True) computes it (by that launch itself, so a value read here is the value a
+        later score uses, bit for bit); columns beyond a row's tlen are 0"""
         K = self.K if K is None else int(K)
+        if stat in lib.AL_STAT_INFO:
+            self.need_info(stat)
+        elif stat not in lib.AL_STAT:
+            raise ValueError(STAT_NAMES)
         N, ld = self.N, self.ld
         tl = self.tlen.cpu().numpy()
         if tl.min() < 0 or tl.max() > ld:
@@ -132,18 +161,30 @@ class McBank:
         uv = torch.empty(N, device=self.dev)
         ob = torch.empty(N, device=self.dev, dtype=torch.int32)
         p = lib.ptr
-        lib.check(self._lib.hual_al_score_mc(ctypes.byref(aset), p(self.s0), p(self.e0), ctypes.byref(self.c), K, lib.AL_STAT[stat], 0.0,
-                                             p(scratch[0]), p(scratch[1]), p(uf), p(uv), p(ob), p(um), lib.stream_ptr()))
+        if stat in lib.AL_STAT_INFO:
+            lib.check(self._lib.hual_al_score_info(ctypes.byref(aset), p(self.s0), p(self.e0), ctypes.byref(self.c), ctypes.byref(self.info_c),
+                                                   K, lib.AL_STAT_INFO[stat], 0.0, p(scratch[0]), p(scratch[1]), p(uf), p(uv), p(ob), p(um),
+                                                   lib.stream_ptr()))
+        else:
+            lib.check(self._lib.hual_al_score_mc(ctypes.byref(aset), p(self.s0), p(self.e0), ctypes.byref(self.c), K, lib.AL_STAT[stat], 0.0,
+                                                 p(scratch[0]), p(scratch[1]), p(uf), p(uv), p(ob), p(um), lib.stream_ptr()))
         torch.cuda.current_stream().synchronize()          # (the launch's inputs above are locals)
         return um
 
     # rows as host arrays and back: how the ranks of a sharded pass hand their (disjoint) rows to rank 0 - copied, never reduced
+    # ('ent' travels with them when the bank holds it; a part and a bank must agree on that)
     def export_rows(self, ids):
         i = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).to(self.dev)
-        return dict(ids=np.ascontiguousarray(ids, dtype=np.int64), tlen=self.tlen[i].cpu().numpy(), s0=self.s0[i].cpu().numpy(),
+        part = dict(ids=np.ascontiguousarray(ids, dtype=np.int64), tlen=self.tlen[i].cpu().numpy(), s0=self.s0[i].cpu().numpy(),
                     e0=self.e0[i].cpu().numpy(), stats=self.stats[:, :, i].cpu().numpy(), K=self.K)
+        if self.ent is not None:
+            part['ent'] = self.ent[:, i].cpu().numpy()
+        return part
 
     def import_rows(self, part):
+        if ('ent' in part) != (self.ent is not None):
+            raise lib.HualError("McBank.import_rows: the rows %s 'ent' and the bank %s - build both banks with the same info="
+                                % (('hold', 'has none') if 'ent' in part else ('lack', 'folds it')))
         if len(part['ids']) == 0:
             return
         i = torch.from_numpy(part['ids']).to(self.dev)
@@ -151,6 +192,8 @@ class McBank:
         self.s0[i] = torch.from_numpy(part['s0']).to(self.dev)
         self.e0[i] = torch.from_numpy(part['e0']).to(self.dev)
         self.stats[:, :, i] = torch.from_numpy(part['stats']).to(self.dev)
+        if self.ent is not None:
+            self.ent[:, i] = torch.from_numpy(part['ent']).to(self.dev)
         self.K = max(self.K, int(part['K']))
 
 
@@ -177,7 +220,8 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
     followed by one fold into the bank rows sample_ids[i] (one array of row ids per yielded batch; default: the samples in the order
     they arrive).  Only the five deterministic fetches go to the host.  Pass k of batch i uses the Philox offset base + K i + (k - 1) -
     today's two at K = 2.  The records lose prop_logits1/2 and gain 'prop_uncert' (f32 [T_b], the statistic `mc_stat` = 'range' or
-    'std' of hual_al_score_mc, read from the bank once at the end).
+    'std' of hual_al_score_mc, or 'bald', 'entropy' or 'expected_entropy' of hual_al_score_info from a bank with info=True; read from
+    the bank once at the end).
     """
     from . import data
     records, ious = [], []
@@ -190,8 +234,10 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
             raise ValueError('mc_samples needs mc_dropout: K passes without dropout are K copies of one')
         if bank is None:
             raise ValueError('mc_samples needs a McBank (bank=) over the whole training set')
-        if mc_stat not in lib.AL_STAT:
-            raise ValueError("mc_stat is 'range' or 'std'")
+        if mc_stat in lib.AL_STAT_INFO:
+            bank.need_info(mc_stat)                             # (before K forwards per batch are spent on a bank that cannot answer)
+        elif mc_stat not in lib.AL_STAT:
+            raise ValueError('mc_stat: ' + STAT_NAMES)
     sample_ids = iter(sample_ids) if sample_ids is not None else None
     rows_seen = []
     batch_ids = iter(batch_ids) if batch_ids is not None else None
@@ -278,7 +324,8 @@ def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_char
     rank 0 returns (records, ious) of the WHOLE set in sample order, the other ranks (None, None).  One rank: the plain pass.
     The batches are the single-process ones (own padded shape each), so the records equal a single-process pass; the Philox offsets
     of the stochastic forwards depend on the batch index only.
-    mc_samples=K: every rank folds its own batches into its own bank (`bank`; default: a McBank.for_dataset of this call only); the
+    mc_samples=K: every rank folds its own batches into its own bank (`bank`; default: a McBank.for_dataset of this call only, with
+    info=True when mc_stat is 'bald', 'entropy' or 'expected_entropy'); the
     rows of the other ranks reach rank 0's bank with the records (disjoint rows: copied, never reduced), and rank 0 reads
     'prop_uncert' from the gathered bank.  Every rank's own stream advances by K * n_batches."""
     from . import dist as hdist
@@ -298,7 +345,7 @@ def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_char
     K = int(mc_samples) if mc_samples is not None else None
     own_rows = [np.arange(los[i], min(N, los[i] + batch_size)) for i in own]
     if K is not None and bank is None:
-        bank = McBank.for_dataset(dataset, device=model.device)
+        bank = McBank.for_dataset(dataset, device=model.device, info=mc_stat in lib.AL_STAT_INFO)
     records, ious = infer_trainset(model, batches(), mc_dropout=mc_dropout, batch_ids=own, rng=rng, mc_samples=mc_samples, bank=bank,
                                    sample_ids=own_rows if K is not None else None, mc_stat=mc_stat, _attach=False)
     # every rank returns to its OWN dropout stream, behind the whole pass
@@ -396,7 +443,8 @@ class LabelUpdater:
     """Device-side state of one update_label round: the logits of the results pkl as [N, ld] matrices, the active
     points as CSR.  score() and renew() are one launch each.
     Bank form (from_bank, or records that hold 'prop_uncert'): the model-uncertainty term comes from a McBank of K folded passes
-    (hual_al_score_mc) instead of the two stochastic passes' logits; there is no [6, N, ld] matrix then."""
+    (hual_al_score_mc; hual_al_score_info for the statistics 'bald', 'entropy' and 'expected_entropy') instead of the two stochastic
+    passes' logits; there is no [6, N, ld] matrix then."""
 
     def __init__(self, last_prop, aps, device='cuda:0'):
         if not torch.cuda.is_available():
@@ -442,9 +490,12 @@ class LabelUpdater:
     @classmethod
     def from_bank(cls, bank, vlen, aps, K=None, stat='range'):
         """score straight from a McBank (no upload, no logits matrix).  vlen: host [N] valid frames; K: the stochastic passes the bank
-        holds (default: bank.K); stat: 'range' or 'std' (hual_al_score_mc)."""
-        if stat not in lib.AL_STAT:
-            raise ValueError("stat is 'range' or 'std'")
+        holds (default: bank.K); stat: 'range' or 'std' (hual_al_score_mc), or 'bald', 'entropy' or 'expected_entropy' (hual_al_score_info;
+        the bank was built with info=True)."""
+        if stat in lib.AL_STAT_INFO:
+            bank.need_info(stat)
+        elif stat not in lib.AL_STAT:
+            raise ValueError('stat: ' + STAT_NAMES)
         self = cls.__new__(cls)
         self._lib = lib.load()
         self.dev = bank.dev
@@ -455,7 +506,7 @@ class LabelUpdater:
         self.bank, self.bank_c, self.logits = bank, bank.c, None
         self._s0, self._e0 = bank.s0, bank.e0
         self.K, self.stat = int(bank.K if K is None else K), stat
-        if self.K < 2:
+        if self.K < (1 if stat in ('entropy', 'expected_entropy') else 2):
             raise ValueError('the bank holds K = %d stochastic passes: a spread needs two' % self.K)
         self._finish(bank.N, bank.ld, tlen, vlen, bank.tlen, aps)
         return self
@@ -487,6 +538,12 @@ class LabelUpdater:
 
     def score(self, coff_uncert):
         p, lg = lib.ptr, self.logits
+        if self.bank_c is not None and self.stat in lib.AL_STAT_INFO:
+            lib.check(self._lib.hual_al_score_info(ctypes.byref(self.set), p(self._s0), p(self._e0), ctypes.byref(self.bank_c),
+                                                   ctypes.byref(self.bank.info_c), self.K, lib.AL_STAT_INFO[self.stat], float(coff_uncert),
+                                                   p(self.sprob), p(self.eprob), p(self.uncert_frame), p(self.uncert_video), p(self.observe),
+                                                   None, lib.stream_ptr()))
+            return
         if self.bank_c is not None:
             lib.check(self._lib.hual_al_score_mc(ctypes.byref(self.set), p(self._s0), p(self._e0), ctypes.byref(self.bank_c), self.K,
                                                  lib.AL_STAT[self.stat], float(coff_uncert), p(self.sprob), p(self.eprob),
@@ -514,8 +571,9 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     data/<task>_re<I>/train.json; last_prop: the records of results/<task>/re<I-1>.pkl; coff: get_coff(task, I).
     Mutates and returns data_old exactly as the reference writes it to data/<task>_re<I>/train.json.
     bank: the McBank the K-pass inference that made last_prop folded into - the model uncertainty is then read from it on the device
-    (mc_samples = its K, default bank.K; mc_stat 'range' or 'std'); last_prop then only names the samples ('vid', 'v_len').  Without
-    a bank, records that hold 'prop_uncert' are scored from that recorded term.
+    (mc_samples = its K, default bank.K; mc_stat 'range' or 'std', or 'bald', 'entropy' or 'expected_entropy' from a bank with
+    info=True); last_prop then only names the samples ('vid', 'v_len').  Without a bank, records that hold 'prop_uncert' are scored from
+    that recorded term, whichever statistic it is.
     """
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -579,7 +637,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     list, the epochs run data parallel (`batch_size` clips per rank, Trainer.run_epoch), infer_trainset is sharded by batch and its
     records are gathered on rank 0.
     mc_samples=K: the round's inference runs K stochastic passes folded into a McBank (metrics['mc_bank']; `bank` if given, else a new
-    one).  A `bank` that already holds the passes behind last_prop (the previous round's metrics['mc_bank']) feeds this round's label
+    one - with info=True when mc_stat is 'bald', 'entropy' or 'expected_entropy', which a given bank must have been built with).
+    A `bank` that already holds the passes behind last_prop (the previous round's metrics['mc_bank']) feeds this round's label
     update on the device before it is refilled; otherwise last_prop's own 'prop_uncert' or 'prop_logits1/2' do.
     Returns (new train list, new results records - rank 0 only, else None -, metrics dict)."""
     import time
@@ -612,7 +671,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     if mc_samples is not None and bank is None:
-        bank = McBank.for_dataset(dataset, device=model.device)
+        bank = McBank.for_dataset(dataset, device=model.device, info=mc_stat in lib.AL_STAT_INFO)
     records, ious = infer_trainset_sharded(model, dataset, batch_size, mc_dropout=mc_dropout, min_chars=4, mc_samples=mc_samples,
                                            bank=bank if mc_samples is not None else None, mc_stat=mc_stat)
     torch.cuda.synchronize()

@@ -1,5 +1,6 @@
 // Active-learning label update kernels (see al.hip).
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 #define HUAL_AL_MAX_T 1024
@@ -57,6 +58,33 @@ struct AlFoldArgs {
   float *lo[2], *hi[2], *mean[2], *m2[2];     // [N, ld] per head (0 = start, 1 = end)
 };
 
+// hual_al_mc_fold_info: the same fold plus the running mean of the per-pass binary entropy (the existing arguments keep their offsets)
+struct AlFoldInfoArgs : AlFoldArgs {
+  float* ent[2];                              // [N, ld] per head: mean over the stochastic passes of h2(p_k), in bits
+};
+
+// hual_al_score_info: hual_al_score_mc's scoring with an information-theoretic model-uncertainty term (the fields al_score_kernel
+// reads carry the names of AlScoreArgs)
+struct AlScoreInfoArgs {
+  const float *s0, *e0;                       // [N, ld] deterministic logits
+  const float *mean_s, *ent_s;                // [N, ld] start head: mean probability, mean entropy of the passes
+  const float *mean_e, *ent_e;                // [N, ld] end head
+  int ld, N;
+  const int32_t* vlen;
+  const int32_t* tlen;
+  const int32_t* ap_off;
+  const int32_t* ap_idx;
+  const int8_t* ap_pos;
+  float coff_uncert;
+  int stat;                                   // HUAL_AL_STAT_BALD / HUAL_AL_STAT_ENTROPY / HUAL_AL_STAT_EXPECTED_ENTROPY
+  float* sprob;
+  float* eprob;
+  double* uncert_frame;
+  float* uncert_video;
+  int32_t* observe;
+  float* uncert_model;                        // [N, ld] the model-uncertainty term itself (NULL: not written)
+};
+
 struct AlRenewArgs {
   const int32_t* sel;                         // [nsel] sample ids to update (NULL: all)
   const float* sprob;
@@ -75,6 +103,8 @@ struct AlRenewArgs {
 int launch_al_score(const AlScoreArgs& a, hipStream_t s);
 int launch_al_score_mc(const AlScoreMcArgs& a, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
+int launch_al_score_info(const AlScoreInfoArgs& a, hipStream_t s);
+int launch_al_mc_fold_info(const AlFoldInfoArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);
 
 }  // namespace hual

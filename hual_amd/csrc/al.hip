@@ -128,6 +128,17 @@ __device__ void distance_block(const int* seg, int nseg, double shift, int vlen,
 
 __device__ __forceinline__ float sigmoid_np(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// binary entropy in bits, every operation rounded on its own (tests/mc_info_ref.py is its float64 yardstick).  The fold and the score
+// evaluate this one function: K identical passes leave mean == p and ent == h2(p), and BALD = h2(mean) - ent is then exactly 0.
+__device__ __forceinline__ float h2_bits(float p) {
+#pragma clang fp contract(off)
+  if (p <= 0.0f || p >= 1.0f) return 0.0f;
+  const float q = 1.0f - p;
+  const float a = p * log2f(p);
+  const float b = q * log2f(q);
+  return -(a + b);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------
@@ -153,9 +164,23 @@ __device__ __forceinline__ void keep_uncert(const AlScoreMcArgs& a, size_t i, fl
   if (a.uncert_model) a.uncert_model[i] = um;
 }
 
+// ... or the bank's mean probability and the mean entropy of the passes beside it (hual_al_info), in bits per head: total (ENTROPY) =
+// epistemic (BALD, the mutual information) + aleatoric (EXPECTED_ENTROPY).  Jensen keeps BALD >= 0 in exact arithmetic; the clamp only
+// removes negative rounding residue.
+__device__ __forceinline__ float model_uncert(const AlScoreInfoArgs& a, size_t i) {
+  if (a.stat == HUAL_AL_STAT_EXPECTED_ENTROPY) return a.ent_s[i] + a.ent_e[i];
+  const float hs = h2_bits(a.mean_s[i]), he = h2_bits(a.mean_e[i]);
+  if (a.stat == HUAL_AL_STAT_ENTROPY) return hs + he;
+  return fmaxf(0.0f, hs - a.ent_s[i]) + fmaxf(0.0f, he - a.ent_e[i]);
+}
+__device__ __forceinline__ void keep_uncert(const AlScoreInfoArgs& a, size_t i, float um) {
+  if (a.uncert_model) a.uncert_model[i] = um;
+}
+
 }  // namespace
 
-// Args = AlScoreArgs: hual_al_score, the code it always was; Args = AlScoreMcArgs: hual_al_score_mc
+// Args = AlScoreArgs: hual_al_score, the code it always was; Args = AlScoreMcArgs: hual_al_score_mc; Args = AlScoreInfoArgs:
+// hual_al_score_info
 template <class Args>
 __global__ __launch_bounds__(AL_THREADS) void al_score_kernel(Args a) {
   extern __shared__ float lds[];            // dist[T] | tmp[T]
@@ -230,9 +255,19 @@ __device__ __forceinline__ void welford_step(float p, float k, float& mean, floa
   m2 = m2 + q;
 }
 
+// the running mean of the per-pass entropy, rounded like Welford's mean above: a subtraction, a division, an add
+__device__ __forceinline__ void mean_step(float x, float k, float& mean) {
+#pragma clang fp contract(off)
+  const float d = x - mean;
+  mean = mean + d / k;
+}
+
 }  // namespace
 
-__global__ __launch_bounds__(AL_THREADS) void al_mc_fold_kernel(AlFoldArgs a) {
+// INFO = false: hual_al_mc_fold, the code it always was (its arguments too); INFO = true: hual_al_mc_fold_info, which also folds the
+// entropy h2(p) of the pass into ent - p is computed once and shared
+template <bool INFO>
+__global__ __launch_bounds__(AL_THREADS) void al_mc_fold_kernel(std::conditional_t<INFO, AlFoldInfoArgs, AlFoldArgs> a) {
   const int b = blockIdx.x;
   const int n = a.ids[b];
   if (n < 0 || n >= a.N) return;                      // an id outside the bank writes nothing
@@ -260,6 +295,16 @@ __global__ __launch_bounds__(AL_THREADS) void al_mc_fold_kernel(AlFoldArgs a) {
         a.hi[h][row + t] = fmaxf(a.hi[h][row + t], p[h]);
         a.mean[h][row + t] = mean;
         a.m2[h][row + t] = m2;
+      }
+      if constexpr (INFO) {
+        const float e = h2_bits(p[h]);
+        if (a.k == 1) {
+          a.ent[h][row + t] = e;
+        } else {
+          float ent = a.ent[h][row + t];
+          mean_step(e, kf, ent);
+          a.ent[h][row + t] = ent;
+        }
       }
     }
   }
@@ -390,14 +435,43 @@ int launch_al_score_mc(const AlScoreMcArgs& a, hipStream_t s) {
   return 0;
 }
 
-int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s) {
+int launch_al_score_info(const AlScoreInfoArgs& a, hipStream_t s) {
+  HUAL_REQUIRE(a.s0 && a.e0 && a.mean_s && a.mean_e && a.vlen && a.tlen && a.ap_off, "al_score_info: null input");
+  HUAL_REQUIRE(a.ent_s && a.ent_e, "al_score_info: null info->ent_s or info->ent_e");
+  HUAL_REQUIRE(a.sprob && a.eprob && a.uncert_frame && a.uncert_video && a.observe, "al_score_info: null output");
+  HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_score_info: need N > 0 and 2 <= ld <= 1024");
+  HUAL_LAUNCH(0.0, 44.0 * a.N * a.ld, al_score_kernel<AlScoreInfoArgs>, dim3(a.N), dim3(AL_THREADS), 2 * a.ld * sizeof(float), s, a);
+  HUAL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+namespace {
+
+// the argument checks of both folds
+int check_al_mc_fold(const AlFoldArgs& a) {
   HUAL_REQUIRE(a.ids && a.vlen && a.s && a.e, "al_mc_fold: null input");
   HUAL_REQUIRE(a.tlen && a.s0 && a.e0, "al_mc_fold: null bank");
   for (int h = 0; h < 2; ++h) HUAL_REQUIRE(a.lo[h] && a.hi[h] && a.mean[h] && a.m2[h], "al_mc_fold: null bank");
   HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_mc_fold: need N > 0 and 2 <= ld <= 1024");
   HUAL_REQUIRE(a.B > 0 && a.T >= 2 && a.T <= a.ld, "al_mc_fold: need B > 0 and 2 <= T_b <= ld");
   HUAL_REQUIRE(a.k >= 0, "al_mc_fold: pass index k >= 0");
-  HUAL_LAUNCH(0.0, (a.k == 0 ? 16.0 : a.k == 1 ? 40.0 : 72.0) * a.B * a.T, al_mc_fold_kernel, dim3(a.B), dim3(AL_THREADS), 0, s, a);
+  return 0;
+}
+
+}  // namespace
+
+int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s) {
+  if (const int rc = check_al_mc_fold(a)) return rc;
+  HUAL_LAUNCH(0.0, (a.k == 0 ? 16.0 : a.k == 1 ? 40.0 : 72.0) * a.B * a.T, al_mc_fold_kernel<false>, dim3(a.B), dim3(AL_THREADS), 0, s, a);
+  HUAL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// per frame one more store per head at k = 1, one more load and store per head at k >= 2
+int launch_al_mc_fold_info(const AlFoldInfoArgs& a, hipStream_t s) {
+  if (const int rc = check_al_mc_fold(a)) return rc;
+  HUAL_REQUIRE(a.ent[0] && a.ent[1], "al_mc_fold_info: null info->ent_s or info->ent_e");
+  HUAL_LAUNCH(0.0, (a.k == 0 ? 16.0 : a.k == 1 ? 48.0 : 88.0) * a.B * a.T, al_mc_fold_kernel<true>, dim3(a.B), dim3(AL_THREADS), 0, s, a);
   HUAL_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -448,15 +522,51 @@ int hual_al_score_mc(const hual_al_set* set, const float* s0, const float* e0, c
   return launch_al_score_mc(a, (hipStream_t)stream);
 }
 
-int hual_al_mc_fold(const hual_al_bank* bank, const int32_t* ids, const int32_t* v_len, const float* start_logits,
-                    const float* end_logits, int B, int T_b, int k, void* stream) {
-  HUAL_REQUIRE(bank, "hual_al_mc_fold: null bank");
-  AlFoldArgs a{};
+static void fold_args(AlFoldArgs& a, const hual_al_bank* bank, const int32_t* ids, const int32_t* v_len, const float* start_logits,
+                      const float* end_logits, int B, int T_b, int k) {
   a.ids = ids; a.vlen = v_len; a.s = start_logits; a.e = end_logits; a.B = B; a.T = T_b; a.k = k;
   a.ld = bank->ld; a.N = bank->N; a.tlen = bank->tlen; a.s0 = bank->s0; a.e0 = bank->e0;
   a.lo[0] = bank->lo_s; a.hi[0] = bank->hi_s; a.mean[0] = bank->mean_s; a.m2[0] = bank->m2_s;
   a.lo[1] = bank->lo_e; a.hi[1] = bank->hi_e; a.mean[1] = bank->mean_e; a.m2[1] = bank->m2_e;
+}
+
+int hual_al_mc_fold(const hual_al_bank* bank, const int32_t* ids, const int32_t* v_len, const float* start_logits,
+                    const float* end_logits, int B, int T_b, int k, void* stream) {
+  HUAL_REQUIRE(bank, "hual_al_mc_fold: null bank");
+  AlFoldArgs a{};
+  fold_args(a, bank, ids, v_len, start_logits, end_logits, B, T_b, k);
   return launch_al_mc_fold(a, (hipStream_t)stream);
+}
+
+int hual_al_mc_fold_info(const hual_al_bank* bank, const hual_al_info* info, const int32_t* ids, const int32_t* v_len,
+                         const float* start_logits, const float* end_logits, int B, int T_b, int k, void* stream) {
+  HUAL_REQUIRE(bank, "hual_al_mc_fold_info: null bank");
+  HUAL_REQUIRE(info, "hual_al_mc_fold_info: null info");
+  AlFoldInfoArgs a{};
+  fold_args(a, bank, ids, v_len, start_logits, end_logits, B, T_b, k);
+  a.ent[0] = info->ent_s; a.ent[1] = info->ent_e;
+  return launch_al_mc_fold_info(a, (hipStream_t)stream);
+}
+
+int hual_al_score_info(const hual_al_set* set, const float* s0, const float* e0, const hual_al_bank* bank, const hual_al_info* info,
+                       int K, int stat, float coff_uncert, float* sprob, float* eprob, double* uncert_frame, float* uncert_video,
+                       int32_t* observe_point, float* uncert_model, void* stream) {
+  HUAL_REQUIRE(set && bank, "hual_al_score_info: null pointer");
+  HUAL_REQUIRE(info, "hual_al_score_info: null info");
+  HUAL_REQUIRE(stat == HUAL_AL_STAT_BALD || stat == HUAL_AL_STAT_ENTROPY || stat == HUAL_AL_STAT_EXPECTED_ENTROPY,
+               "hual_al_score_info: stat is HUAL_AL_STAT_BALD, HUAL_AL_STAT_ENTROPY or HUAL_AL_STAT_EXPECTED_ENTROPY");
+  HUAL_REQUIRE(K >= (stat == HUAL_AL_STAT_BALD ? 2 : 1),
+               "hual_al_score_info: K >= 2 stochastic passes for BALD (one sample has no disagreement), K >= 1 for the entropies");
+  HUAL_REQUIRE(bank->N == set->N && bank->ld == set->ld, "hual_al_score_info: bank and set differ in N or ld");
+  AlScoreInfoArgs a{};
+  a.s0 = s0; a.e0 = e0;
+  a.mean_s = bank->mean_s; a.ent_s = info->ent_s; a.mean_e = bank->mean_e; a.ent_e = info->ent_e;
+  a.ld = set->ld; a.N = set->N; a.vlen = set->vlen; a.tlen = set->tlen;
+  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos;
+  a.coff_uncert = coff_uncert; a.stat = stat;
+  a.sprob = sprob; a.eprob = eprob; a.uncert_frame = uncert_frame; a.uncert_video = uncert_video; a.observe = observe_point;
+  a.uncert_model = uncert_model;
+  return launch_al_score_info(a, (hipStream_t)stream);
 }
 
 int hual_al_renew(const hual_al_set* set, const int32_t* sel, int nsel, const float* sprob, const float* eprob,

@@ -63,7 +63,13 @@ class hual_al_bank(ctypes.Structure):
                 ('lo_e', ctypes.c_void_p), ('hi_e', ctypes.c_void_p), ('mean_e', ctypes.c_void_p), ('m2_e', ctypes.c_void_p)]
 
 
-AL_STAT = {'range': 0, 'std': 1}      # HUAL_AL_STAT_RANGE / HUAL_AL_STAT_STD
+class hual_al_info(ctypes.Structure):
+    _fields_ = [('ent_s', ctypes.c_void_p), ('ent_e', ctypes.c_void_p)]
+
+
+AL_STAT = {'range': 0, 'std': 1}      # HUAL_AL_STAT_RANGE / HUAL_AL_STAT_STD: hual_al_score_mc
+# HUAL_AL_STAT_BALD / _ENTROPY / _EXPECTED_ENTROPY: hual_al_score_info, from a bank that also folds the passes' entropy (hual_al_info)
+AL_STAT_INFO = {'bald': 2, 'entropy': 3, 'expected_entropy': 4}
 
 
 class hual_dataset(ctypes.Structure):
@@ -149,6 +155,8 @@ def load():
     lib.hual_al_score.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
     lib.hual_al_mc_fold.argtypes = [P(hual_al_bank), vp, vp, vp, vp, i32, i32, i32, vp]
     lib.hual_al_score_mc.argtypes = [P(hual_al_set), vp, vp, P(hual_al_bank), i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
+    lib.hual_al_mc_fold_info.argtypes = [P(hual_al_bank), P(hual_al_info), vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.hual_al_score_info.argtypes = [P(hual_al_set), vp, vp, P(hual_al_bank), P(hual_al_info), i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_al_renew.argtypes = [P(hual_al_set), vp, i32, vp, vp, vp, P(ctypes.c_double), vp, vp]
     lib.hual_assemble_batch.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_carry.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]

@@ -269,7 +269,8 @@ class Runner:
     def infer_trainset(self, path=None, mc_dropout=None, load_best=True, weights=None, mc_samples=None, mc_stat='range', bank=None):
         """results/<task>/<suffix>.pkl of runner_utils.py:103-104.  mc_dropout=None: as the reference runs.
         weights: 'ema' (the default with train.ema_decay) or 'raw'.  mc_samples=K (with mc_dropout): K stochastic passes folded into
-        `bank` (al.McBank; default: one of this call only) - the records then hold 'prop_uncert' instead of prop_logits1/2."""
+        `bank` (al.McBank; default: one of this call only) - the records then hold 'prop_uncert' instead of prop_logits1/2: the statistic
+        mc_stat = 'range' or 'std', or 'bald', 'entropy' or 'expected_entropy' (a given bank was then built with info=True)."""
         if load_best:
             hdist.barrier()
             self.load(os.path.join(self.ckpt_dir, 'best_SeqPAN.npz'))

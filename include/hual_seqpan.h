@@ -500,6 +500,39 @@ int hual_al_score_mc(const hual_al_set* set, const float* s0, const float* e0, c
                      int32_t* observe_point, float* uncert_model, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Information-theoretic acquisition from the same K passes (HUAL_ABI_VERSION unchanged: new symbols, nothing else moved; hual_al_mc_fold
+ * and hual_al_score_mc are what they were).  RANGE and STD measure the spread of p; neither separates "the passes disagree" from "every
+ * pass is unsure", and RANGE grows with K.  With the binary entropy in bits
+ *   h2(p) = 0.0f if p <= 0.0f or p >= 1.0f, else -(p * log2f(p) + q * log2f(q)), q = 1.0f - p
+ * (float32, every operation rounded on its own) the fold also keeps, per head, the running mean `ent` of h2(p_k) over the stochastic
+ * passes - p_k the very value the fold computes, 0 at t >= v_len, so a masked frame contributes exactly 0.  Per head each statistic
+ * below lies in [0, 1] at every K, their sum over the two heads in [0, 2]: the interval RANGE lives in.
+ * The arrays belong to the caller and sit beside its hual_al_bank: each f32 [N, ld] row major, device memory.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hual_al_info {
+  float *ent_s, *ent_e;                /* start / end head: mean over the stochastic passes of h2(p_k) */
+} hual_al_info;
+
+/* hual_al_mc_fold - one launch, the same arguments and checks, every hual_al_bank array bit-identical to it - that also folds ent:
+ *   k = 0: untouched;  k = 1: ent = h2(p);  k >= 2: ent += (h2(p) - ent) / k
+ * Writes columns [0, T_b) of the listed rows only.  Allocates nothing, does not synchronise. */
+int hual_al_mc_fold_info(const hual_al_bank* bank, const hual_al_info* info, const int32_t* ids, const int32_t* v_len,
+                         const float* start_logits, const float* end_logits, int B, int T_b, int k, void* stream);
+
+/* the sum over the start and end heads of (mean = the bank's Welford mean of p): */
+#define HUAL_AL_STAT_BALD 2              /* fmaxf(0.0f, h2(mean) - ent): the mutual information between the prediction and the dropout
+                                            mask - disagreement between the passes (epistemic).  >= 0 by Jensen in exact arithmetic; the
+                                            clamp only removes negative rounding residue.  K identical passes give exactly 0 */
+#define HUAL_AL_STAT_ENTROPY 3           /* h2(mean): total predictive uncertainty = BALD + EXPECTED_ENTROPY */
+#define HUAL_AL_STAT_EXPECTED_ENTROPY 4  /* ent: what every single pass is unsure about (aleatoric) */
+/* hual_al_score_mc with the model-uncertainty term one of the three statistics above (no other value of stat is accepted; K >= 2 for
+ * BALD, K >= 1 for the two entropies; bank and set agree in N and ld).  Everything else - distance score, float64 mixture,
+ * uncert_video, the first maximal frame, uncert_model (may be NULL) - is hual_al_score_mc's. */
+int hual_al_score_info(const hual_al_set* set, const float* s0, const float* e0, const hual_al_bank* bank, const hual_al_info* info,
+                       int K, int stat, float coff_uncert, float* sprob, float* eprob, double* uncert_frame, float* uncert_video,
+                       int32_t* observe_point, float* uncert_model, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
