@@ -26,6 +26,12 @@ mutual information between prediction and dropout mask, the entropy of the mean 
 summed over the two heads: each in [0, 2] at every K.  They need a McBank built with info=True, whose folds (hual_al_mc_fold_info) also
 keep the running mean of the per-pass entropy, and are scored by hual_al_score_info.  Without those names every launch, record and
 result is what it was.
+
+Span confidence (neither has): infer_trainset(span_conf=True) adds to every record the expected temporal IoU of its own proposal under
+the deterministic pass's span distribution ('prop_conf', in [0, 1]) and that distribution's entropy in bits ('prop_span_entropy') - one
+hual_span_expected_iou launch per batch, fetched with the deterministic fetches.  update_labels(rank_by='span_risk') then selects the
+half of the set with the smallest risk 1 - prop_conf instead of the smallest uncert_video.  Off by default: every launch, record and
+result is then what it was.
 """
 import ctypes
 import math
@@ -207,7 +213,7 @@ def attach_uncert(records, rows, bank, K, stat):
 
 # ---------------------------------------------------------------- infer_trainset ----------------
 def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc_samples=None, bank=None, sample_ids=None,
-                   mc_stat='range', _attach=True):
+                   mc_stat='range', _attach=True, span_conf=False):
     """eval_test_save (runner_utils.py:69-110) without the file write: returns (records, ious).
 
     batches: iterable of (raw_records, video, video_seq_len, word_ids, char_ids) as TestLoader.test_iter yields them
@@ -222,6 +228,9 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
     today's two at K = 2.  The records lose prop_logits1/2 and gain 'prop_uncert' (f32 [T_b], the statistic `mc_stat` = 'range' or
     'std' of hual_al_score_mc, or 'bald', 'entropy' or 'expected_entropy' of hual_al_score_info from a bank with info=True; read from
     the bank once at the end).
+    span_conf=True: every record gains 'prop_conf' (float: the expected temporal IoU of its own prop_idx under the span distribution of
+    the deterministic pass, -1.0 where the forward gave no span) and 'prop_span_entropy' (float, bits): one hual_span_expected_iou
+    launch per batch with k = 1 on the forward's start_index / end_index, fetched with the five deterministic fetches.
     """
     from . import data
     records, ious = [], []
@@ -255,6 +264,10 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
         raw, video, lens, word_ids, char_ids = batch
         o = model.forward(video, lens, word_ids, char_ids, drop_rate=0.0)
         dev = [o['start_logits'], o['end_logits'], o['match_scores'], o['start_index'], o['end_index']]
+        conf = None
+        if span_conf:
+            nb = o['start_index'].numel()
+            conf = lib.span_expected_iou(o['start_logits'], o['end_logits'], lens, o['start_index'].view(nb, 1), o['end_index'].view(nb, 1))
         if K is not None:
             n0 = sum(len(x) for x in rows_seen)
             ids = np.asarray(next(sample_ids)) if sample_ids is not None else np.arange(n0, n0 + len(raw))
@@ -275,6 +288,8 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
             o2 = model.forward(video, lens, word_ids, char_ids, drop_rate=mc_dropout)
             model.rng_state[2] += 1
             dev += [o1['start_logits'], o1['end_logits'], o2['start_logits'], o2['end_logits']]
+        if conf is not None:
+            dev += [conf[0], conf[1]]                            # (last: the positions of the fetches above stay)
         # device -> pinned host, asynchronously on the compute stream; the event marks their arrival
         host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in dev]
         for h, t in zip(host, dev):
@@ -303,6 +318,8 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
                 s1, e1, s2, e2 = stoch
                 rec['prop_logits1'], rec['prop_logits2'] = [s1[i], e1[i]], [s2[i], e2[i]]
             rec['m_score'] = ms[i]
+            if span_conf:
+                rec['prop_conf'], rec['prop_span_entropy'] = float(host[-2][i, 0]), float(host[-1][i])
             records.append(rec)
 
     pending = None
@@ -318,7 +335,8 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
     return records, ious
 
 
-def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_chars=4, mc_samples=None, bank=None, mc_stat='range'):
+def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_chars=4, mc_samples=None, bank=None, mc_stat='range',
+                           span_conf=False):
     """infer_trainset over a DeviceDataset in the reference's order (TrainNoSuffleLoader.test_iter, data_loader.py:167-206), the
     batches dealt round-robin to the ranks of the process group (batch i -> rank i % world; every rank holds the whole set):
     rank 0 returns (records, ious) of the WHOLE set in sample order, the other ranks (None, None).  One rank: the plain pass.
@@ -327,7 +345,8 @@ def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_char
     mc_samples=K: every rank folds its own batches into its own bank (`bank`; default: a McBank.for_dataset of this call only, with
     info=True when mc_stat is 'bald', 'entropy' or 'expected_entropy'); the
     rows of the other ranks reach rank 0's bank with the records (disjoint rows: copied, never reduced), and rank 0 reads
-    'prop_uncert' from the gathered bank.  Every rank's own stream advances by K * n_batches."""
+    'prop_uncert' from the gathered bank.  Every rank's own stream advances by K * n_batches.
+    span_conf: as infer_trainset (the two floats travel with the records)."""
     from . import dist as hdist
     world, rank = hdist.world_size(), hdist.rank()
     N = len(dataset)
@@ -347,7 +366,7 @@ def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_char
     if K is not None and bank is None:
         bank = McBank.for_dataset(dataset, device=model.device, info=mc_stat in lib.AL_STAT_INFO)
     records, ious = infer_trainset(model, batches(), mc_dropout=mc_dropout, batch_ids=own, rng=rng, mc_samples=mc_samples, bank=bank,
-                                   sample_ids=own_rows if K is not None else None, mc_stat=mc_stat, _attach=False)
+                                   sample_ids=own_rows if K is not None else None, mc_stat=mc_stat, _attach=False, span_conf=span_conf)
     # every rank returns to its OWN dropout stream, behind the whole pass
     model.set_rng(own_rng[0], own_rng[1] + ((2 if K is None else K) * len(los) if mc_dropout is not None else 0))
     part = None
@@ -564,7 +583,18 @@ class LabelUpdater:
         return new_d.cpu().numpy()
 
 
-def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range'):
+RANK_BY = ('uncert_video', 'span_risk')
+
+
+def span_risk(last_prop):
+    """1 - prop_conf of every record (float64 [N]): the expected loss of temporal IoU of the record's own proposal"""
+    if not all('prop_conf' in p for p in last_prop):
+        raise ValueError("rank_by='span_risk' needs records that hold 'prop_conf': run infer_trainset(span_conf=True)")
+    return 1.0 - np.array([float(p['prop_conf']) for p in last_prop], dtype=np.float64)
+
+
+def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
+                  rank_by='uncert_video'):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -574,7 +604,12 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     (mc_samples = its K, default bank.K; mc_stat 'range' or 'std', or 'bald', 'entropy' or 'expected_entropy' from a bank with
     info=True); last_prop then only names the samples ('vid', 'v_len').  Without a bank, records that hold 'prop_uncert' are scored from
     that recorded term, whichever statistic it is.
+    rank_by: 'uncert_video' (the reference's key) or 'span_risk' - the samples are then ranked by 1 - prop_conf of their records
+    (infer_trainset(span_conf=True)), the same stable argsort, the same half selected; everything else in the round is unchanged.
     """
+    if rank_by not in RANK_BY:
+        raise ValueError("rank_by: 'uncert_video' or 'span_risk'")
+    risk = span_risk(last_prop) if rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
             r.append({'pos_idx': [], 'neg_idx': []})
@@ -591,7 +626,7 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     up.score(coff[6])
     uv = up.uncert_video.cpu().numpy()
     observe = up.observe.cpu().numpy()
-    order = np.argsort(uv, kind='stable')                       # sorted(key=uncert_video), ties in sample order
+    order = np.argsort(uv if risk is None else risk, kind='stable')      # sorted(key=uncert_video), ties in sample order
     sel = order[:math.ceil(N / 2)]
     vlen = up.vlen_h
     gt_idx = np.array([[_round_half_even_index(t, data_gt[i][1], int(vlen[i])) for t in data_gt[i][2]] for i in range(N)])
@@ -608,9 +643,12 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         dur, vl = data_old[i][1], int(vlen[i])
         data_old[i][2] = [round(int(t) / (vl - 1) * dur, 2) for t in new_idx[i]]          # index_to_time, update_label.py:50-57
     if return_debug:
-        return data_old, dict(order=order, uncert_video=uv, observe=observe, uncert_frame=up.uncert_frame.cpu().numpy(),
-                              sprob=up.sprob.cpu().numpy(), eprob=up.eprob.cpu().numpy(), new_idx=new_idx, gt_idx=gt_idx,
-                              old_idx=old_idx, updater=up)
+        dbg = dict(order=order, uncert_video=uv, observe=observe, uncert_frame=up.uncert_frame.cpu().numpy(),
+                   sprob=up.sprob.cpu().numpy(), eprob=up.eprob.cpu().numpy(), new_idx=new_idx, gt_idx=gt_idx,
+                   old_idx=old_idx, updater=up)
+        if risk is not None:
+            dbg['span_risk'] = risk
+        return data_old, dbg
     return data_old
 
 
@@ -628,7 +666,7 @@ def labels_from_times(data, vlens):
 
 
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
-              shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None):
+              shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -640,6 +678,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     one - with info=True when mc_stat is 'bald', 'entropy' or 'expected_entropy', which a given bank must have been built with).
     A `bank` that already holds the passes behind last_prop (the previous round's metrics['mc_bank']) feeds this round's label
     update on the device before it is refilled; otherwise last_prop's own 'prop_uncert' or 'prop_logits1/2' do.
+    span_conf=True: the round's inference records 'prop_conf' / 'prop_span_entropy' (infer_trainset).
     Returns (new train list, new results records - rank 0 only, else None -, metrics dict)."""
     import time
     from . import dist as hdist
@@ -673,7 +712,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     if mc_samples is not None and bank is None:
         bank = McBank.for_dataset(dataset, device=model.device, info=mc_stat in lib.AL_STAT_INFO)
     records, ious = infer_trainset_sharded(model, dataset, batch_size, mc_dropout=mc_dropout, min_chars=4, mc_samples=mc_samples,
-                                           bank=bank if mc_samples is not None else None, mc_stat=mc_stat)
+                                           bank=bank if mc_samples is not None else None, mc_stat=mc_stat, span_conf=span_conf)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     met = hdist.broadcast_object(iou_metrics(ious) if rank == 0 else None)

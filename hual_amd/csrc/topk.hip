@@ -1,22 +1,23 @@
 // The k best spans of each clip with greedy temporal NMS (hual_span_topk, include/hual_seqpan.h): what R@k evaluation and the
 // "best few moments" of a video need, on the device.  Beside the forward, not in it: heads.hip keeps its span argmax as it is.
 //
-// One 1024-thread workgroup per clip.  Thread t < 256 computes frame t's probabilities exactly as the span stage of heads_kernel does (same
-// masking, same max / double-sum reduction trees, same rounding), so the numbers are bit for bit those of hual_span_argmax.  The
-// triangle of up to 32,896 candidates (i <= j < vlen, j - i < max_len) is cut into 1024 contiguous stretches of the row-major order, one
+// One 1024-thread workgroup per clip.  Thread t < 256 computes frame t's probabilities exactly as the span stage of heads_kernel does
+// (spanprob.h, shared with spanconf.hip), so the numbers are bit for bit those of hual_span_argmax.  The triangle of up to 32,896
+// candidates (i <= j < vlen, j - i < max_len) is cut into 1024 contiguous stretches of the row-major order, one
 // per thread.  A thread keeps the best candidate of its stretch that no selected span suppresses; each of the k rounds is one
 // (score, key) arg-reduction (wave64 butterfly, then the 16 waves through LDS), and after it only the threads whose best the new span
 // suppresses rescan their stretch - the suppressed set only grows, so a best that survives stays best.
 // Latency bound: at most 2 KB of logits in and 20 * k bytes out per clip, no matrix work; one barrier per round (ABI 9).
 #include "common.h"
 #include "prof.h"
+#include "spanprob.h"
 
 using namespace hual;
 
 namespace {
 
-constexpr int TK_THREADS = 1024;      // 16 waves: four per SIMD hide each other's LDS latency in the candidate scans
-constexpr int TK_WAVES = TK_THREADS / 64;
+constexpr int TK_THREADS = SPAN_THREADS;      // 16 waves: four per SIMD hide each other's LDS latency in the candidate scans
+constexpr int TK_WAVES = SPAN_WAVES;
 constexpr int TK_NONE = 0x7fffffff;      // key of "no candidate" (score -1: below every real score, which is >= 0)
 
 // candidate order: higher score first, then the smaller key i * 256 + j (smaller i, then smaller j).  A NaN score is never better.
@@ -78,37 +79,12 @@ __global__ __launch_bounds__(TK_THREADS) void span_topk_kernel(const float* __re
   __shared__ int wbk[2][TK_WAVES];
   __shared__ int sel[16];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int vr = vlen_[b];
-  const int v = vr < 1 ? 0 : (vr > T ? T : vr);
+  const int v = span_clip_len(vlen_[b], T);
   const size_t row = (size_t)b * T;
   int nout = 0;
-  const int nanlogit = __syncthreads_or(t < v && (zs_[row + t] != zs_[row + t] || ze_[row + t] != ze_[row + t]));
+  const int nanlogit = span_row_poisoned(zs_, ze_, row, v);
   if (v > 0 && !nanlogit) {
-    // ---- probabilities: heads_kernel's span stage (mask_logits, reproducible softmax; oracle/seqpan_ref.py::softmax_cr)
-    const bool in = t < T;
-    float zs = -INFINITY, ze = -INFINITY;
-    if (in) {
-      zs = t < v ? zs_[row + t] : HUAL_MASK_VALUE;      // (= x * 0 + HUAL_MASK_VALUE for a finite padding logit, never read here)
-      ze = t < v ? ze_[row + t] : HUAL_MASK_VALUE;
-    }
-    float mxs = wave_max64_bperm(zs), mxe = wave_max64_bperm(ze);
-    if (lane == 0) { smf[w] = mxs; smf[TK_WAVES + w] = mxe; }
-    __syncthreads();
-    mxs = -INFINITY; mxe = -INFINITY;
-    for (int q = 0; q < TK_WAVES; ++q) { mxs = fmaxf(mxs, smf[q]); mxe = fmaxf(mxe, smf[TK_WAVES + q]); }
-    const float xs = in ? (float)exp((double)(zs - mxs)) : 0.f;
-    const float xe = in ? (float)exp((double)(ze - mxe)) : 0.f;
-    double dss = (double)xs, dse = (double)xe;
-    for (int off = 32; off >= 1; off >>= 1) { dss += __shfl_xor(dss, off); dse += __shfl_xor(dse, off); }
-    if (lane == 0) { smd[w] = dss; smd[TK_WAVES + w] = dse; }
-    __syncthreads();
-    dss = 0.0; dse = 0.0;
-    for (int q = 0; q < TK_WAVES; ++q) { dss += smd[q]; dse += smd[TK_WAVES + q]; }      // (waves 4.. add exact zeros, as in heads_kernel)
-    if (t < 256) {
-      ps[t] = __fdiv_rn(xs, (float)dss);
-      pe[t] = __fdiv_rn(xe, (float)dse);
-    }
-    __syncthreads();
+    span_probabilities(zs_, ze_, row, T, v, ps, pe, smf, smd);      // (spanprob.h: the numbers of hual_span_argmax)
     // ---- candidates: this thread's stretch of the row-major triangle
     const int L = max_len > 0 ? min(max_len, v) : v;
     const int n = tk_row_off(v, v, L);

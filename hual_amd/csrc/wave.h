@@ -91,6 +91,20 @@ __device__ __forceinline__ float wave_max64(float v) {
   v = fast_max32(v);
   return fmaxf(v, lane_xor32(v));
 }
+// float64 sum across the wave: the same butterfly, each exchange moving the two halves of the partner's value
+__device__ __forceinline__ double wave_sum64_f64(double v, int lane = threadIdx.x) {
+#pragma unroll
+  for (int step = 1; step <= 32; step <<= 1) {
+    const uint2 x = __builtin_bit_cast(uint2, v);
+    const float lo = __builtin_bit_cast(float, x.x), hi = __builtin_bit_cast(float, x.y);
+    float plo, phi;
+    if (step <= 8) { plo = dpp_xor_partner(lo, step); phi = dpp_xor_partner(hi, step); }
+    else if (step == 16) { plo = lane_xor16(lo, lane); phi = lane_xor16(hi, lane); }
+    else { plo = lane_xor32(lo, lane); phi = lane_xor32(hi, lane); }
+    v += __builtin_bit_cast(double, make_uint2(__builtin_bit_cast(unsigned, plo), __builtin_bit_cast(unsigned, phi)));
+  }
+  return v;
+}
 // The same maximum (max is exact and commutative: identical results) with its last step through the LDS crossbar (ds_bpermute): the
 // form the workgroup maxima of the context-query kernels (cq_wgmax_put), heads.hip, al.hip, topk.hip and the V maximum of the
 // attention backward are compiled with.  Ending them on lane_xor32 gives 15 kernels another instruction stream, 11 of them outside

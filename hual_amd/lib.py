@@ -151,6 +151,7 @@ def load():
     lib.hual_attention_keep_row_bytes.argtypes = [i32]
     lib.hual_span_argmax.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
     lib.hual_span_topk.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]
+    lib.hual_span_expected_iou.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.hual_linear_dw.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, u64, vp]
     lib.hual_al_score.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
     lib.hual_al_mc_fold.argtypes = [P(hual_al_bank), vp, vp, vp, vp, i32, i32, i32, vp]
@@ -292,3 +293,41 @@ def span_topk(start_logits, end_logits, video_seq_len, k, max_len=0, nms_iou=1.0
     check(load().hual_span_topk(ptr(s), ptr(e), ptr(vl), B, T, k, int(max_len), ctypes.c_float(nms_iou), ptr(out[0]), ptr(out[1]),
                                 ptr(out[2]), stream_ptr()))
     return out
+
+
+def span_expected_iou(start_logits, end_logits, video_seq_len, starts, ends, score=None, reorder=False, entropy=True, out=None):
+    """expected temporal IoU of the proposals starts / ends (int64 [B,k] on the device, k <= 16; -1 = no proposal) under the span
+    distribution of start_logits / end_logits f32 [B,T] and video_seq_len [B], and that distribution's entropy in bits
+    (hual_span_expected_iou) -> (expected_iou [B,k] float32, span_entropy [B] float32 or None with entropy=False), enqueued on the
+    current stream.  Invalid slots, empty clips and rows with a NaN logit give -1.0.  reorder=True sorts every row's slots by expected
+    IoU, best first, stable: starts, ends and score (float32 [B,k] or None) are permuted in place along with the result.
+    out: (expected_iou, span_entropy) contiguous device tensors of those shapes to write into instead (span_entropy may be None)."""
+    import torch
+    if start_logits.dtype != torch.float32 or end_logits.dtype != torch.float32:
+        raise HualError('span_expected_iou: float32 logits required')
+    if start_logits.dim() != 2 or end_logits.shape != start_logits.shape:
+        raise HualError('span_expected_iou: start / end logits must both be [B,T]')
+    s, e = start_logits.contiguous(), end_logits.contiguous()
+    B, T = s.shape
+    vl = video_seq_len.to(device=s.device, dtype=torch.int32).contiguous()
+    if vl.numel() != B:
+        raise HualError('span_expected_iou: video_seq_len must hold B = %d lengths' % B)
+    if starts.dim() != 2 or starts.shape[0] != B:
+        raise HualError('span_expected_iou: starts / ends must be [B,k] with B = %d' % B)
+    k = int(starts.shape[1])
+    # (no .contiguous() here: reorder writes them in place, and a copy would take the permutation with it)
+    for x, dt, what in ((starts, torch.int64, 'starts'), (ends, torch.int64, 'ends'), (score, torch.float32, 'score')):
+        if x is not None and (x.dtype != dt or tuple(x.shape) != (B, k) or not x.is_contiguous() or x.device != s.device):
+            raise HualError('span_expected_iou: %s must be a contiguous [B,k] %s tensor on the logits\' device'
+                            % (what, str(dt).replace('torch.', '')))
+    if out is None:
+        out = (torch.empty(B, k, dtype=torch.float32, device=s.device), torch.empty(B, dtype=torch.float32, device=s.device) if entropy else None)
+    else:
+        if len(out) != 2 or out[0] is None:
+            raise HualError('span_expected_iou: out is (expected_iou [B,k], span_entropy [B] or None)')
+        for o, shape in zip(out, ((B, k), (B,))):
+            if o is not None and (o.dtype != torch.float32 or tuple(o.shape) != shape or not o.is_contiguous() or o.device != s.device):
+                raise HualError('span_expected_iou: out tensors must be contiguous float32 [B,k] and [B] on the logits\' device')
+    check(load().hual_span_expected_iou(ptr(s), ptr(e), ptr(vl), B, T, k, ptr(starts), ptr(ends), ptr(score), ptr(out[0]), ptr(out[1]),
+                                        1 if reorder else 0, stream_ptr()))
+    return out[0], out[1]

@@ -153,16 +153,24 @@ class Runner:
         return al.iou_metrics(ious)
 
     # ------------------------------------------------------------------ R@k evaluation (top-k proposals after temporal NMS)
-    def evaluate(self, dataset=None, k=5, nms_iou=0.5, max_len=0, return_proposals=False, weights=None):
+    def evaluate(self, dataset=None, k=5, nms_iou=0.5, max_len=0, return_proposals=False, weights=None, rerank=None):
         """weights: 'ema' (the default with train.ema_decay) or 'raw'; everything else: _evaluate"""
+        if rerank not in (None, 'expected_iou'):
+            raise ValueError("rerank: None or 'expected_iou'")
         with self._weights(weights):
-            return self._evaluate(dataset, k, nms_iou, max_len, return_proposals)
+            return self._evaluate(dataset, k, nms_iou, max_len, return_proposals, rerank)
 
-    def _evaluate(self, dataset, k, nms_iou, max_len, return_proposals):
+    def _evaluate(self, dataset, k, nms_iou, max_len, return_proposals, rerank=None):
         """R1 and R<k> at IoU 0.3 / 0.5 / 0.7 and mIoU (percent) of the k best spans per clip after greedy temporal NMS
         (hual_span_topk).  Batches and ranks as test_epoch; the proposals of all batches collect on the device and come back in one
         transfer.  R1 and mIoU are those of the first proposal, which is the span test_epoch scores.  return_proposals: also a list
-        with one entry per clip of the dataset, [(start_sec, end_sec, score), ...] best first (data.index_to_time)."""
+        with one entry per clip of the dataset, [(start_sec, end_sec, score), ...] best first (data.index_to_time).
+        rerank='expected_iou': the k proposals of every clip are re-ordered by their expected temporal IoU under the clip's span
+        distribution, best first (hual_span_expected_iou with reorder, one more launch per batch into the same buffers) - the
+        minimum-Bayes-risk choice among them.  R1 and mIoU are then those of the re-ranked first proposal (R<k> does not depend on the
+        order); the result gains 'conf', the mean expected IoU of the first proposal, and 'span_entropy', the mean entropy of the span
+        distribution in bits (clips without a value - a poisoned row - count out), and the proposal tuples a fourth element, the
+        expected IoU."""
         ds = dataset or self.test_set
         N, bs, k = len(ds), self.batch_size, int(k)
         mine = [(lo, min(N, lo + bs)) for b, lo in enumerate(range(0, N, bs)) if b % self.world == self.rank]
@@ -173,6 +181,8 @@ class Runner:
         st = buf[:8 * n * k].view(torch.int64).view(n, k)
         en = buf[8 * n * k:16 * n * k].view(torch.int64).view(n, k)
         sc = buf[16 * n * k:].view(torch.float32).view(n, k)
+        # re-ranking: expected IoU [n,k] | span entropy [n] (float32), one more buffer
+        cbuf = torch.empty(n * k + n, dtype=torch.float32, device=dev) if rerank else None
         pos = 0
         for lo, hi in mine:
             sel = np.arange(lo, hi)
@@ -180,17 +190,24 @@ class Runner:
             o = self.model.forward(f['video'], f['video_seq_len'], f['word_ids'], f['char_ids'], drop_rate=0.0)
             lib.span_topk(o['start_logits'], o['end_logits'], f['video_seq_len'], k, max_len=max_len, nms_iou=nms_iou,
                           out=(st[pos:pos + hi - lo], en[pos:pos + hi - lo], sc[pos:pos + hi - lo]))
+            if rerank:
+                lib.span_expected_iou(o['start_logits'], o['end_logits'], f['video_seq_len'], st[pos:pos + hi - lo], en[pos:pos + hi - lo],
+                                      score=sc[pos:pos + hi - lo], reorder=True,
+                                      out=(cbuf[:n * k].view(n, k)[pos:pos + hi - lo], cbuf[n * k:][pos:pos + hi - lo]))
             pos += hi - lo
         h = buf.cpu().numpy()
         ids = np.concatenate([np.arange(lo, hi) for lo, hi in mine]) if mine else np.zeros(0, dtype=np.int64)
         part = (ids, h[:8 * n * k].view(np.int64).reshape(n, k), h[8 * n * k:16 * n * k].view(np.int64).reshape(n, k),
                 h[16 * n * k:].view(np.float32).reshape(n, k))
+        if rerank:
+            hc = cbuf.cpu().numpy()
+            part += (hc[:n * k].reshape(n, k), hc[n * k:])
         if self.world > 1:
             parts = hdist.gather_objects(part)
             if self.rank == 0:
-                part = tuple(np.concatenate([p[x] for p in parts]) for x in range(4))
+                part = tuple(np.concatenate([p[x] for p in parts]) for x in range(len(part)))
             part = hdist.broadcast_object(part if self.rank == 0 else None)
-        ids, S, E, SC = part
+        ids, S, E, SC = part[:4]
         recs = [ds.records[i] for i in ids]
         ious = al.topk_ious(recs, S, E)
         r1 = al.iou_metrics(ious[:, 0])
@@ -199,15 +216,21 @@ class Runner:
                'mIoU': r1[3]}
         self.log.info('EVAL (k={}, nms_iou={}):\tR1 {:.2f}\t{:.2f}\t{:.2f}\tR{} {:.2f}\t{:.2f}\t{:.2f}\tmIoU {:.2f}'.format(
             k, nms_iou, r1[0], r1[1], r1[2], k, rk[0], rk[1], rk[2], r1[3]))
+        if rerank:
+            EI, ENT = part[4], part[5]
+            c0, ent = EI[:, 0][EI[:, 0] >= 0], ENT[ENT >= 0]
+            res['conf'] = float(np.mean(c0, dtype=np.float64)) if c0.size else float('nan')
+            res['span_entropy'] = float(np.mean(ent, dtype=np.float64)) if ent.size else float('nan')
+            self.log.info('EVAL re-ranked by expected IoU:\tconf {:.4f}\tspan entropy {:.3f} bits'.format(res['conf'], res['span_entropy']))
         if not return_proposals:
             return res
         props = [None] * N
         for row, i in enumerate(ids):
             r, p = ds.records[i], []
-            for s, e, x in zip(S[row], E[row], SC[row]):
+            for c, (s, e, x) in enumerate(zip(S[row], E[row], SC[row])):
                 if s >= 0:
                     t0, t1 = data.index_to_time((s, e), r['v_len'], r['duration'])
-                    p.append((float(t0), float(t1), float(x)))
+                    p.append((float(t0), float(t1), float(x)) + ((float(EI[row, c]),) if rerank else ()))
             props[i] = p
         return res, props
 
@@ -266,11 +289,13 @@ class Runner:
         return t
 
     # ------------------------------------------------------------------ main.py --mode infer_trainset (:99-111)
-    def infer_trainset(self, path=None, mc_dropout=None, load_best=True, weights=None, mc_samples=None, mc_stat='range', bank=None):
+    def infer_trainset(self, path=None, mc_dropout=None, load_best=True, weights=None, mc_samples=None, mc_stat='range', bank=None,
+                       span_conf=False):
         """results/<task>/<suffix>.pkl of runner_utils.py:103-104.  mc_dropout=None: as the reference runs.
         weights: 'ema' (the default with train.ema_decay) or 'raw'.  mc_samples=K (with mc_dropout): K stochastic passes folded into
         `bank` (al.McBank; default: one of this call only) - the records then hold 'prop_uncert' instead of prop_logits1/2: the statistic
-        mc_stat = 'range' or 'std', or 'bald', 'entropy' or 'expected_entropy' (a given bank was then built with info=True)."""
+        mc_stat = 'range' or 'std', or 'bald', 'entropy' or 'expected_entropy' (a given bank was then built with info=True).
+        span_conf=True: the records also hold 'prop_conf' and 'prop_span_entropy' (al.infer_trainset)."""
         if load_best:
             hdist.barrier()
             self.load(os.path.join(self.ckpt_dir, 'best_SeqPAN.npz'))
@@ -278,7 +303,7 @@ class Runner:
             self.train_set = DeviceDataset(*self._host_train, device=self.model.device)
         with self._weights(weights):
             records, ious = al.infer_trainset_sharded(self.model, self.train_set, self.batch_size, mc_dropout=mc_dropout, min_chars=4,
-                                                      mc_samples=mc_samples, bank=bank, mc_stat=mc_stat)
+                                                      mc_samples=mc_samples, bank=bank, mc_stat=mc_stat, span_conf=span_conf)
         if self.rank != 0:
             return None, hdist.broadcast_object(None)
         if path:

@@ -388,6 +388,31 @@ int hual_span_argmax(const float* start_logits, const float* end_logits, const f
 int hual_span_topk(const float* start_logits, const float* end_logits, const int32_t* video_seq_len, int B, int T, int k, int max_len,
                    float nms_iou, int64_t* start_index, int64_t* end_index, float* score, void* stream);
 
+/* expected temporal IoU of k proposed spans per clip under the clip's own span distribution, that distribution's entropy, and the
+ * minimum-Bayes-risk order of the proposals (ABI 9 unchanged, a new symbol).  With v = video_seq_len[b] read as hual_span_topk reads it
+ * (> T as T, < 1 as empty), p_s / p_e are the masked softmaxes bit for bit as hual_span_topk and hual_span_argmax compute them; the
+ * weights are w(i,j) = p_s[i] * p_e[j] (one fp32 product) for 0 <= i <= j < v, Z their sum, P = w / Z.  1 <= k <= 16, 1 <= T <= 256.
+ *  - expected_iou [B, k] (float): for the candidate (a, b) = (start_index, end_index)[b][slot] the sum over the triangle of
+ *    P(i,j) * iou on the half-open frame intervals of hual_span_topk's NMS: inter = max(0, min(b,j) + 1 - max(a,i)), union =
+ *    (b - a + 1) + (j - i + 1) - inter - the time IoU of the spans in seconds, the evaluation's metric.  Arithmetic: each term is
+ *    w * ((float)inter / (float)union), the division and the product rounded to fp32; the terms and Z are accumulated in float64 in a
+ *    fixed order; the result is (float)(sum / Z), in [0, 1].
+ *  - span_entropy [B] (float; may be NULL): H = log2(Z) - (1/Z) * sum w * (log2f(p_s[i]) + log2f(p_e[j])) in bits, the sum of the two
+ *    logarithms in fp32, product and accumulation in float64, terms with w == 0 skipped, clamped at >= 0, <= log2(v (v + 1) / 2).
+ *    v == 1: H = 0 and every valid candidate has expected IoU exactly 1.0f.
+ *  - a slot is invalid when an index is negative, a > b or b >= v: its expected_iou is -1.0f (not an error).
+ *  - an empty clip (v < 1), a NaN logit at t < v (the poison rule of hual_span_topk) or a Z that is not a positive finite number
+ *    (every weight of the triangle underflowed, or an infinite logit): every expected_iou of the row is -1.0f, span_entropy is -1.0f
+ *    and the row is never reordered.  Logits at t >= v are not read.
+ *  - reorder != 0: the row's slots are sorted by expected_iou descending, stable (equal values and the invalid slots, last, keep their
+ *    incoming order); start_index, end_index, score (when not NULL) and expected_iou are permuted alike, in place.  reorder == 0:
+ *    start_index / end_index / score are only read.
+ * Allocates nothing and does not synchronise: capturable in a hipGraph.  Argument errors (a null pointer other than score and
+ * span_entropy, the ranges above, B < 1) return before any HIP call. */
+int hual_span_expected_iou(const float* start_logits, const float* end_logits, const int32_t* video_seq_len, int B, int T, int k,
+                           int64_t* start_index, int64_t* end_index, float* score, float* expected_iou, float* span_entropy,
+                           int reorder, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Device-side batch assembly: TrainLoader.process_batch / TestLoader.process_batch
  * (/root/reference/utils/data_loader.py:30-98,145-164) from a training set that stays resident in HBM.
