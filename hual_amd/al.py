@@ -113,6 +113,13 @@ class McBank:
         if self.ent is None:
             raise lib.HualError("McBank: '%s' needs the passes' entropy, which this bank does not fold - build the bank with info=True" % what)
 
+    def check_stat(self, stat):
+        """raises unless this bank can be read as the statistic `stat`"""
+        if stat in lib.AL_STAT_INFO:
+            self.need_info(stat)
+        elif stat not in lib.AL_STAT:
+            raise ValueError('stat: ' + STAT_NAMES)
+
     def rows(self, ids):
         """device i32 row ids of one fold, checked on the host: inside the bank, none twice (the rows of a launch must be disjoint)"""
         ids = np.ascontiguousarray(ids.cpu().numpy() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
@@ -149,10 +156,7 @@ class McBank:
         'entropy', 'expected_entropy'; a bank with info=True) computes it (by that launch itself, so a value read here is the value a
         later score uses, bit for bit); columns beyond a row's tlen are 0"""
         K = self.K if K is None else int(K)
-        if stat in lib.AL_STAT_INFO:
-            self.need_info(stat)
-        elif stat not in lib.AL_STAT:
-            raise ValueError(STAT_NAMES)
+        self.check_stat(stat)
         N, ld = self.N, self.ld
         tl = self.tlen.cpu().numpy()
         if tl.min() < 0 or tl.max() > ld:
@@ -166,14 +170,8 @@ class McBank:
         uf = torch.empty(N, ld, device=self.dev, dtype=torch.float64)
         uv = torch.empty(N, device=self.dev)
         ob = torch.empty(N, device=self.dev, dtype=torch.int32)
-        p = lib.ptr
-        if stat in lib.AL_STAT_INFO:
-            lib.check(self._lib.hual_al_score_info(ctypes.byref(aset), p(self.s0), p(self.e0), ctypes.byref(self.c), ctypes.byref(self.info_c),
-                                                   K, lib.AL_STAT_INFO[stat], 0.0, p(scratch[0]), p(scratch[1]), p(uf), p(uv), p(ob), p(um),
-                                                   lib.stream_ptr()))
-        else:
-            lib.check(self._lib.hual_al_score_mc(ctypes.byref(aset), p(self.s0), p(self.e0), ctypes.byref(self.c), K, lib.AL_STAT[stat], 0.0,
-                                                 p(scratch[0]), p(scratch[1]), p(uf), p(uv), p(ob), p(um), lib.stream_ptr()))
+        lib.al_score(aset, self.s0, self.e0, 0.0, (scratch[0], scratch[1], uf, uv, ob), bank=self.c, info=self.info_c, K=K, stat=stat,
+                     uncert_model=um)
         torch.cuda.current_stream().synchronize()          # (the launch's inputs above are locals)
         return um
 
@@ -243,23 +241,17 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
             raise ValueError('mc_samples needs mc_dropout: K passes without dropout are K copies of one')
         if bank is None:
             raise ValueError('mc_samples needs a McBank (bank=) over the whole training set')
-        if mc_stat in lib.AL_STAT_INFO:
-            bank.need_info(mc_stat)                             # (before K forwards per batch are spent on a bank that cannot answer)
-        elif mc_stat not in lib.AL_STAT:
-            raise ValueError('mc_stat: ' + STAT_NAMES)
+        bank.check_stat(mc_stat)                                # (before K forwards per batch are spent on a bank that cannot answer)
     sample_ids = iter(sample_ids) if sample_ids is not None else None
     rows_seen = []
     batch_ids = iter(batch_ids) if batch_ids is not None else None
     rng_base = rng_seed = None
     if batch_ids is not None and mc_dropout is not None:
-        if rng is not None:
-            rng_seed, rng_base = int(rng[0]), int(rng[1])
-        else:
-            st = model.rng_state.cpu().numpy().view(np.uint32)
-            rng_seed, rng_base = int(st[0]) | (int(st[1]) << 32), int(st[2])
+        rng_seed, rng_base = (int(rng[0]), int(rng[1])) if rng is not None else model.get_rng()
+    P = 0 if mc_dropout is None else 2 if K is None else K      # stochastic passes per batch: folded into the bank, or two kept
 
     def enqueue(batch):
-        """all forwards of a batch (one deterministic + two stochastic), nothing fetched: the device runs them while the host
+        """all forwards of a batch (one deterministic + P stochastic), nothing fetched: the device runs them while the host
         writes the records of the batch before"""
         raw, video, lens, word_ids, char_ids = batch
         o = model.forward(video, lens, word_ids, char_ids, drop_rate=0.0)
@@ -274,20 +266,15 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
             rows_seen.append(ids)
             rows = bank.rows(ids)
             bank.fold(rows, lens, o['start_logits'], o['end_logits'], 0, _checked=True)
-            if rng_base is not None:
-                model.set_rng(rng_seed, rng_base + K * int(next(batch_ids)))
-            for k in range(1, K + 1):
-                ok = model.forward(video, lens, word_ids, char_ids, drop_rate=mc_dropout)
-                model.rng_state[2] += 1                          # a fresh Philox offset for the next stochastic pass
+        if P and rng_base is not None:
+            model.set_rng(rng_seed, rng_base + P * int(next(batch_ids)))
+        for k in range(1, P + 1):
+            ok = model.forward(video, lens, word_ids, char_ids, drop_rate=mc_dropout)
+            model.rng_state[2] += 1                              # a fresh Philox offset for the next stochastic pass
+            if K is not None:
                 bank.fold(rows, lens, ok['start_logits'], ok['end_logits'], k, _checked=True)
-        elif mc_dropout is not None:
-            if rng_base is not None:
-                model.set_rng(rng_seed, rng_base + 2 * int(next(batch_ids)))
-            o1 = model.forward(video, lens, word_ids, char_ids, drop_rate=mc_dropout)
-            model.rng_state[2] += 1                              # a fresh Philox offset for the second stochastic pass
-            o2 = model.forward(video, lens, word_ids, char_ids, drop_rate=mc_dropout)
-            model.rng_state[2] += 1
-            dev += [o1['start_logits'], o1['end_logits'], o2['start_logits'], o2['end_logits']]
+            else:
+                dev += [ok['start_logits'], ok['end_logits']]
         if conf is not None:
             dev += [conf[0], conf[1]]                            # (last: the positions of the fetches above stay)
         # device -> pinned host, asynchronously on the compute stream; the event marks their arrival
@@ -358,8 +345,7 @@ def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_char
             sel = np.arange(los[i], min(N, los[i] + batch_size))
             f = dataset.assemble(sel, out=None, labels=False, min_chars=min_chars)
             yield [dataset.records[k] for k in sel], f['video'], f['video_seq_len'], f['word_ids'], f['char_ids']
-    st0 = model.rng_state.cpu().numpy().view(np.uint32).copy()
-    own_rng = (int(st0[0]) | (int(st0[1]) << 32), int(st0[2]))
+    own_rng = model.get_rng()
     rng = hdist.broadcast_object(own_rng)                       # rank 0's stream for the stochastic passes: the records do not depend on `world`
     K = int(mc_samples) if mc_samples is not None else None
     own_rows = [np.arange(los[i], min(N, los[i] + batch_size)) for i in own]
@@ -463,7 +449,9 @@ class LabelUpdater:
     points as CSR.  score() and renew() are one launch each.
     Bank form (from_bank, or records that hold 'prop_uncert'): the model-uncertainty term comes from a McBank of K folded passes
     (hual_al_score_mc; hual_al_score_info for the statistics 'bald', 'entropy' and 'expected_entropy') instead of the two stochastic
-    passes' logits; there is no [6, N, ld] matrix then."""
+    passes' logits; there is no [6, N, ld] matrix then.
+    Whichever way it is built, the updater records its source - logits (the [6, N, ld] matrix or None), bank (the McBank or None), K and
+    stat - and the hual_al_bank / hual_al_info that score() hands to lib.al_score."""
 
     def __init__(self, last_prop, aps, device='cuda:0'):
         if not torch.cuda.is_available():
@@ -495,15 +483,16 @@ class LabelUpdater:
             a = lib._addr
             self.bank_c = lib.hual_al_bank(N, ld, None, a(self._s0), a(self._e0), a(self._zero), a(self._um), a(self._zero), a(self._zero),
                                            a(self._zero), a(self._zero), a(self._zero), a(self._zero))
-            self.bank, self.K, self.stat, self.logits = None, 2, 'range', None
+            self._source(None, None, 2, 'range')
         else:
             lg = np.zeros((6, N, ld), dtype=np.float32)
             for n, p in enumerate(last_prop):
                 for k, key in enumerate(('prop_logits', 'prop_logits1', 'prop_logits2')):
                     lg[2 * k, n, :tlen[n]] = p[key][0]
                     lg[2 * k + 1, n, :tlen[n]] = p[key][1]
-            self.logits = torch.from_numpy(lg).to(self.dev)
-            self.bank_c = None
+            lg_d = torch.from_numpy(lg).to(self.dev)
+            self._s0, self._e0, self.bank_c = lg_d[0], lg_d[1], None
+            self._source(lg_d, None, 2, None)
         self._finish(N, ld, tlen, vlen, torch.from_numpy(tlen).to(self.dev), aps)
 
     @classmethod
@@ -511,10 +500,7 @@ class LabelUpdater:
         """score straight from a McBank (no upload, no logits matrix).  vlen: host [N] valid frames; K: the stochastic passes the bank
         holds (default: bank.K); stat: 'range' or 'std' (hual_al_score_mc), or 'bald', 'entropy' or 'expected_entropy' (hual_al_score_info;
         the bank was built with info=True)."""
-        if stat in lib.AL_STAT_INFO:
-            bank.need_info(stat)
-        elif stat not in lib.AL_STAT:
-            raise ValueError('stat: ' + STAT_NAMES)
+        bank.check_stat(stat)
         self = cls.__new__(cls)
         self._lib = lib.load()
         self.dev = bank.dev
@@ -522,13 +508,16 @@ class LabelUpdater:
         vlen = np.ascontiguousarray(vlen, dtype=np.int32)
         if len(vlen) != bank.N or int(tlen.min()) < 2 or int(tlen.max()) > bank.ld or (vlen < 1).any() or (vlen > tlen).any():
             raise ValueError('need one v_len per bank row, every row folded (tlen >= 2) and 1 <= v_len <= tlen')
-        self.bank, self.bank_c, self.logits = bank, bank.c, None
-        self._s0, self._e0 = bank.s0, bank.e0
-        self.K, self.stat = int(bank.K if K is None else K), stat
+        self._s0, self._e0, self.bank_c = bank.s0, bank.e0, bank.c
+        self._source(None, bank, int(bank.K if K is None else K), stat)
         if self.K < (1 if stat in ('entropy', 'expected_entropy') else 2):
             raise ValueError('the bank holds K = %d stochastic passes: a spread needs two' % self.K)
         self._finish(bank.N, bank.ld, tlen, vlen, bank.tlen, aps)
         return self
+
+    def _source(self, logits, bank, K, stat):
+        """where score() reads the model-uncertainty term from: the stochastic rows of `logits`, or self.bank_c as `stat` over K passes"""
+        self.logits, self.bank, self.K, self.stat = logits, bank, K, stat
 
     def _finish(self, N, ld, tlen, vlen, tlen_d, aps):
         self.N, self.ld = N, ld
@@ -556,21 +545,9 @@ class LabelUpdater:
                                    p(self.ap_idx).value, p(self.ap_pos).value)
 
     def score(self, coff_uncert):
-        p, lg = lib.ptr, self.logits
-        if self.bank_c is not None and self.stat in lib.AL_STAT_INFO:
-            lib.check(self._lib.hual_al_score_info(ctypes.byref(self.set), p(self._s0), p(self._e0), ctypes.byref(self.bank_c),
-                                                   ctypes.byref(self.bank.info_c), self.K, lib.AL_STAT_INFO[self.stat], float(coff_uncert),
-                                                   p(self.sprob), p(self.eprob), p(self.uncert_frame), p(self.uncert_video), p(self.observe),
-                                                   None, lib.stream_ptr()))
-            return
-        if self.bank_c is not None:
-            lib.check(self._lib.hual_al_score_mc(ctypes.byref(self.set), p(self._s0), p(self._e0), ctypes.byref(self.bank_c), self.K,
-                                                 lib.AL_STAT[self.stat], float(coff_uncert), p(self.sprob), p(self.eprob),
-                                                 p(self.uncert_frame), p(self.uncert_video), p(self.observe), None, lib.stream_ptr()))
-            return
-        lib.check(self._lib.hual_al_score(ctypes.byref(self.set), p(lg[0]), p(lg[1]), p(lg[2]), p(lg[3]), p(lg[4]), p(lg[5]),
-                                          float(coff_uncert), p(self.sprob), p(self.eprob), p(self.uncert_frame),
-                                          p(self.uncert_video), p(self.observe), lib.stream_ptr()))
+        lib.al_score(self.set, self._s0, self._e0, coff_uncert, (self.sprob, self.eprob, self.uncert_frame, self.uncert_video, self.observe),
+                     pair=self.logits[2:] if self.logits is not None else None, bank=self.bank_c,
+                     info=self.bank.info_c if self.bank is not None else None, K=self.K, stat=self.stat)
 
     def renew(self, sel, old_idx, coff):
         """sel: sample ids (numpy); old_idx: int [N,2]; returns new_idx int32 [N,2] (valid for the selected rows)"""

@@ -1,21 +1,34 @@
 // Active-learning label update kernels (see al.hip).
 #pragma once
-#include <type_traits>
 #include "common.h"
 
 #define HUAL_AL_MAX_T 1024
 
 namespace hual {
 
+// which of AlScoreArgs' sources the model-uncertainty term of a launch is read from
+enum AlSource {
+  AL_SRC_PAIR,                                // hual_al_score: the two stochastic passes' logits
+  AL_SRC_SPREAD,                              // hual_al_score_mc: the bank's min / max / sum of squared deviations
+  AL_SRC_INFO,                                // hual_al_score_info: the bank's mean and the mean entropy of the passes beside it
+};
+
 struct AlScoreArgs {
-  const float *s0, *e0, *s1, *e1, *s2, *e2;   // [N, ld] start / end logits: deterministic pass, two stochastic passes
-  int ld, N;
+  int ld, N;                                  // the set (hual_al_set) ...
   const int32_t* vlen;                        // [N] valid frames
   const int32_t* tlen;                        // [N] length of the logits record (padded length of its batch)
   const int32_t* ap_off;                      // [N+1] CSR offsets of the active points
   const int32_t* ap_idx;                      // frame index of each active point
   const int8_t* ap_pos;                       // 1 = inside the ground-truth span, 0 = outside
+  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
   float coff_uncert;
+  // the source of the model-uncertainty term: a launch reads the fields of its AlSource, the others stay null
+  const float *s1, *e1, *s2, *e2;             // PAIR: [N, ld] logits of the two stochastic passes
+  const float *lo[2], *hi[2], *mean[2], *m2[2];   // SPREAD, INFO: [N, ld] per head (0 = start, 1 = end), the bank (hual_al_bank)
+  const float* ent[2];                        // INFO: [N, ld] per head, mean entropy of the passes (hual_al_info)
+  int stat;                                   // SPREAD: HUAL_AL_STAT_RANGE / _STD; INFO: HUAL_AL_STAT_BALD / _ENTROPY / _EXPECTED_ENTROPY
+  float km1;                                  // SPREAD: (float)(K - 1)
+  float* uncert_model;                        // SPREAD, INFO: [N, ld] the model-uncertainty term itself (NULL: not written)
   float* sprob;                               // [N, ld]
   float* eprob;                               // [N, ld]
   double* uncert_frame;                       // [N, ld]
@@ -23,30 +36,7 @@ struct AlScoreArgs {
   int32_t* observe;                           // [N] argmax of uncert_frame
 };
 
-// hual_al_score_mc: the same scoring with the model-uncertainty term read from the per-sample bank of K folded passes
-// (the fields al_score_body reads carry the names of AlScoreArgs)
-struct AlScoreMcArgs {
-  const float *s0, *e0;                       // [N, ld] deterministic logits
-  const float *lo_s, *hi_s, *m2_s;            // [N, ld] start head: min / max probability, sum of squared deviations
-  const float *lo_e, *hi_e, *m2_e;            // [N, ld] end head
-  int ld, N;
-  const int32_t* vlen;
-  const int32_t* tlen;
-  const int32_t* ap_off;
-  const int32_t* ap_idx;
-  const int8_t* ap_pos;
-  float coff_uncert;
-  int stat;                                   // HUAL_AL_STAT_RANGE / HUAL_AL_STAT_STD
-  float km1;                                  // (float)(K - 1)
-  float* sprob;
-  float* eprob;
-  double* uncert_frame;
-  float* uncert_video;
-  int32_t* observe;
-  float* uncert_model;                        // [N, ld] the model-uncertainty term itself (NULL: not written)
-};
-
-// hual_al_mc_fold: one forward's logits [B, T] folded into the rows ids[b] of the bank
+// hual_al_mc_fold / hual_al_mc_fold_info: one forward's logits [B, T] folded into the rows ids[b] of the bank
 struct AlFoldArgs {
   const int32_t* ids;                         // [B] bank rows
   const int32_t* vlen;                        // [B] valid frames of each clip
@@ -56,33 +46,7 @@ struct AlFoldArgs {
   int32_t* tlen;                              // [N]
   float *s0, *e0;                             // [N, ld]
   float *lo[2], *hi[2], *mean[2], *m2[2];     // [N, ld] per head (0 = start, 1 = end)
-};
-
-// hual_al_mc_fold_info: the same fold plus the running mean of the per-pass binary entropy (the existing arguments keep their offsets)
-struct AlFoldInfoArgs : AlFoldArgs {
-  float* ent[2];                              // [N, ld] per head: mean over the stochastic passes of h2(p_k), in bits
-};
-
-// hual_al_score_info: hual_al_score_mc's scoring with an information-theoretic model-uncertainty term (the fields al_score_kernel
-// reads carry the names of AlScoreArgs)
-struct AlScoreInfoArgs {
-  const float *s0, *e0;                       // [N, ld] deterministic logits
-  const float *mean_s, *ent_s;                // [N, ld] start head: mean probability, mean entropy of the passes
-  const float *mean_e, *ent_e;                // [N, ld] end head
-  int ld, N;
-  const int32_t* vlen;
-  const int32_t* tlen;
-  const int32_t* ap_off;
-  const int32_t* ap_idx;
-  const int8_t* ap_pos;
-  float coff_uncert;
-  int stat;                                   // HUAL_AL_STAT_BALD / HUAL_AL_STAT_ENTROPY / HUAL_AL_STAT_EXPECTED_ENTROPY
-  float* sprob;
-  float* eprob;
-  double* uncert_frame;
-  float* uncert_video;
-  int32_t* observe;
-  float* uncert_model;                        // [N, ld] the model-uncertainty term itself (NULL: not written)
+  float* ent[2];                              // [N, ld] per head: mean over the stochastic passes of h2(p_k), in bits (NULL: a plain fold)
 };
 
 struct AlRenewArgs {
@@ -100,11 +64,8 @@ struct AlRenewArgs {
   int32_t* new_idx;                           // [N, 2] (rows of unselected samples are left untouched)
 };
 
-int launch_al_score(const AlScoreArgs& a, hipStream_t s);
-int launch_al_score_mc(const AlScoreMcArgs& a, hipStream_t s);
+int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
-int launch_al_score_info(const AlScoreInfoArgs& a, hipStream_t s);
-int launch_al_mc_fold_info(const AlFoldInfoArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);
 
 }  // namespace hual

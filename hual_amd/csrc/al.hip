@@ -146,43 +146,40 @@ __device__ __forceinline__ float h2_bits(float p) {
 // ------------------------------------------------------------------------------------------------------
 namespace {
 
-// the model-uncertainty term of frame i = row + t, by its source: the two stochastic passes' logits (get_uncert_model,
-// utils_hual.py:144-161) ...
+// the model-uncertainty term of frame i = row + t, by its source
+template <AlSource SRC>
 __device__ __forceinline__ float model_uncert(const AlScoreArgs& a, size_t i) {
-  return fabsf(sigmoid_np(a.s1[i]) - sigmoid_np(a.s2[i])) + fabsf(sigmoid_np(a.e1[i]) - sigmoid_np(a.e2[i]));
+  if constexpr (SRC == AL_SRC_PAIR) {
+    // the two stochastic passes' logits (get_uncert_model, utils_hual.py:144-161)
+    return fabsf(sigmoid_np(a.s1[i]) - sigmoid_np(a.s2[i])) + fabsf(sigmoid_np(a.e1[i]) - sigmoid_np(a.e2[i]));
+  } else if constexpr (SRC == AL_SRC_SPREAD) {
+    // the bank of K folded passes.  RANGE at K = 2 is the expression above bit for bit: hi - lo = fmaxf(p1, p2) - fminf(p1, p2) is the
+    // same subtraction as |p1 - p2| up to its sign.  STD is sqrt(2) times the sample deviation (ddof = 1): |p1 - p2| at K = 2 up to
+    // rounding, and of an expectation that does not grow with K.
+    if (a.stat == HUAL_AL_STAT_RANGE) return (a.hi[0][i] - a.lo[0][i]) + (a.hi[1][i] - a.lo[1][i]);
+    return sqrtf(2.0f) * (sqrtf(a.m2[0][i] / a.km1) + sqrtf(a.m2[1][i] / a.km1));
+  } else {
+    // the bank's mean probability and the mean entropy of the passes beside it (hual_al_info), in bits per head: total (ENTROPY) =
+    // epistemic (BALD, the mutual information) + aleatoric (EXPECTED_ENTROPY).  Jensen keeps BALD >= 0 in exact arithmetic; the clamp
+    // only removes negative rounding residue.
+    if (a.stat == HUAL_AL_STAT_EXPECTED_ENTROPY) return a.ent[0][i] + a.ent[1][i];
+    const float hs = h2_bits(a.mean[0][i]), he = h2_bits(a.mean[1][i]);
+    if (a.stat == HUAL_AL_STAT_ENTROPY) return hs + he;
+    return fmaxf(0.0f, hs - a.ent[0][i]) + fmaxf(0.0f, he - a.ent[1][i]);
+  }
 }
-__device__ __forceinline__ void keep_uncert(const AlScoreArgs&, size_t, float) {}
 
-// ... or the bank of K folded passes.  RANGE at K = 2 is the expression above bit for bit: hi - lo = fmaxf(p1, p2) - fminf(p1, p2)
-// is the same subtraction as |p1 - p2| up to its sign.  STD is sqrt(2) times the sample deviation (ddof = 1): |p1 - p2| at K = 2 up to
-// rounding, and of an expectation that does not grow with K.
-__device__ __forceinline__ float model_uncert(const AlScoreMcArgs& a, size_t i) {
-  if (a.stat == HUAL_AL_STAT_RANGE) return (a.hi_s[i] - a.lo_s[i]) + (a.hi_e[i] - a.lo_e[i]);
-  return sqrtf(2.0f) * (sqrtf(a.m2_s[i] / a.km1) + sqrtf(a.m2_e[i] / a.km1));
-}
-__device__ __forceinline__ void keep_uncert(const AlScoreMcArgs& a, size_t i, float um) {
-  if (a.uncert_model) a.uncert_model[i] = um;
-}
-
-// ... or the bank's mean probability and the mean entropy of the passes beside it (hual_al_info), in bits per head: total (ENTROPY) =
-// epistemic (BALD, the mutual information) + aleatoric (EXPECTED_ENTROPY).  Jensen keeps BALD >= 0 in exact arithmetic; the clamp only
-// removes negative rounding residue.
-__device__ __forceinline__ float model_uncert(const AlScoreInfoArgs& a, size_t i) {
-  if (a.stat == HUAL_AL_STAT_EXPECTED_ENTROPY) return a.ent_s[i] + a.ent_e[i];
-  const float hs = h2_bits(a.mean_s[i]), he = h2_bits(a.mean_e[i]);
-  if (a.stat == HUAL_AL_STAT_ENTROPY) return hs + he;
-  return fmaxf(0.0f, hs - a.ent_s[i]) + fmaxf(0.0f, he - a.ent_e[i]);
-}
-__device__ __forceinline__ void keep_uncert(const AlScoreInfoArgs& a, size_t i, float um) {
-  if (a.uncert_model) a.uncert_model[i] = um;
+// the term itself for the caller (McBank.uncert); the pair form has no such output
+template <AlSource SRC>
+__device__ __forceinline__ void keep_uncert(const AlScoreArgs& a, size_t i, float um) {
+  if constexpr (SRC != AL_SRC_PAIR)
+    if (a.uncert_model) a.uncert_model[i] = um;
 }
 
 }  // namespace
 
-// Args = AlScoreArgs: hual_al_score, the code it always was; Args = AlScoreMcArgs: hual_al_score_mc; Args = AlScoreInfoArgs:
-// hual_al_score_info
-template <class Args>
-__global__ __launch_bounds__(AL_THREADS) void al_score_kernel(Args a) {
+template <AlSource SRC>
+__global__ __launch_bounds__(AL_THREADS) void al_score_kernel(AlScoreArgs a) {
   extern __shared__ float lds[];            // dist[T] | tmp[T]
   __shared__ float red[AL_THREADS / 64];
   __shared__ double redd[AL_THREADS / 64];
@@ -210,8 +207,8 @@ __global__ __launch_bounds__(AL_THREADS) void al_score_kernel(Args a) {
     a.eprob[row + t] = sigmoid_np(a.e0[row + t]);
     float um = 0.0f;
     if (t < V)
-      um = model_uncert(a, row + t);
-    keep_uncert(a, row + t, um);
+      um = model_uncert<SRC>(a, row + t);
+    keep_uncert<SRC>(a, row + t, um);
     vsum += (double)um;
     const double uf = (double)dist[t] + (double)(um * a.coff_uncert);
     a.uncert_frame[row + t] = uf;
@@ -264,10 +261,10 @@ __device__ __forceinline__ void mean_step(float x, float k, float& mean) {
 
 }  // namespace
 
-// INFO = false: hual_al_mc_fold, the code it always was (its arguments too); INFO = true: hual_al_mc_fold_info, which also folds the
-// entropy h2(p) of the pass into ent - p is computed once and shared
+// INFO = false: hual_al_mc_fold, which never reads a.ent; INFO = true: hual_al_mc_fold_info, which also folds the entropy h2(p) of the
+// pass into ent - p is computed once and shared
 template <bool INFO>
-__global__ __launch_bounds__(AL_THREADS) void al_mc_fold_kernel(std::conditional_t<INFO, AlFoldInfoArgs, AlFoldArgs> a) {
+__global__ __launch_bounds__(AL_THREADS) void al_mc_fold_kernel(AlFoldArgs a) {
   const int b = blockIdx.x;
   const int n = a.ids[b];
   if (n < 0 || n >= a.N) return;                      // an id outside the bank writes nothing
@@ -416,62 +413,48 @@ __global__ __launch_bounds__(AL_THREADS) void al_renew_kernel(AlRenewArgs a) {
 
 namespace hual {
 
-int launch_al_score(const AlScoreArgs& a, hipStream_t s) {
-  HUAL_REQUIRE(a.s0 && a.e0 && a.s1 && a.e1 && a.s2 && a.e2 && a.vlen && a.tlen && a.ap_off, "al_score: null input");
+int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s) {
+  HUAL_REQUIRE(a.s0 && a.e0 && a.vlen && a.tlen && a.ap_off, "al_score: null input");
+  if (src == AL_SRC_PAIR) HUAL_REQUIRE(a.s1 && a.e1 && a.s2 && a.e2, "al_score: null input");
+  if (src == AL_SRC_SPREAD) {
+    HUAL_REQUIRE(a.stat == HUAL_AL_STAT_RANGE || a.stat == HUAL_AL_STAT_STD, "al_score: stat is HUAL_AL_STAT_RANGE or HUAL_AL_STAT_STD");
+    for (int h = 0; h < 2; ++h) HUAL_REQUIRE(a.lo[h] && a.hi[h] && a.m2[h], "al_score: null input");
+  }
+  if (src == AL_SRC_INFO) {
+    HUAL_REQUIRE(a.stat == HUAL_AL_STAT_BALD || a.stat == HUAL_AL_STAT_ENTROPY || a.stat == HUAL_AL_STAT_EXPECTED_ENTROPY,
+                 "al_score: stat is HUAL_AL_STAT_BALD, HUAL_AL_STAT_ENTROPY or HUAL_AL_STAT_EXPECTED_ENTROPY");
+    HUAL_REQUIRE(a.mean[0] && a.mean[1], "al_score: null input");
+    HUAL_REQUIRE(a.ent[0] && a.ent[1], "al_score: null info->ent_s or info->ent_e");
+  }
   HUAL_REQUIRE(a.sprob && a.eprob && a.uncert_frame && a.uncert_video && a.observe, "al_score: null output");
   HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_score: need N > 0 and 2 <= ld <= 1024");
-  HUAL_LAUNCH(0.0, 40.0 * a.N * a.ld, al_score_kernel<AlScoreArgs>, dim3(a.N), dim3(AL_THREADS), 2 * a.ld * sizeof(float), s, a);
+  const dim3 grid(a.N), block(AL_THREADS);
+  const size_t lds = 2 * a.ld * sizeof(float);
+  // per frame: the pair form reads six logits, the bank forms up to eight (and may write the term)
+  switch (src) {
+    case AL_SRC_PAIR: HUAL_LAUNCH(0.0, 40.0 * a.N * a.ld, al_score_kernel<AL_SRC_PAIR>, grid, block, lds, s, a); break;
+    case AL_SRC_SPREAD: HUAL_LAUNCH(0.0, 44.0 * a.N * a.ld, al_score_kernel<AL_SRC_SPREAD>, grid, block, lds, s, a); break;
+    case AL_SRC_INFO: HUAL_LAUNCH(0.0, 44.0 * a.N * a.ld, al_score_kernel<AL_SRC_INFO>, grid, block, lds, s, a); break;
+  }
   HUAL_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
-int launch_al_score_mc(const AlScoreMcArgs& a, hipStream_t s) {
-  HUAL_REQUIRE(a.s0 && a.e0 && a.lo_s && a.hi_s && a.m2_s && a.lo_e && a.hi_e && a.m2_e && a.vlen && a.tlen && a.ap_off,
-               "al_score_mc: null input");
-  HUAL_REQUIRE(a.sprob && a.eprob && a.uncert_frame && a.uncert_video && a.observe, "al_score_mc: null output");
-  HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_score_mc: need N > 0 and 2 <= ld <= 1024");
-  HUAL_LAUNCH(0.0, 44.0 * a.N * a.ld, al_score_kernel<AlScoreMcArgs>, dim3(a.N), dim3(AL_THREADS), 2 * a.ld * sizeof(float), s, a);
-  HUAL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_al_score_info(const AlScoreInfoArgs& a, hipStream_t s) {
-  HUAL_REQUIRE(a.s0 && a.e0 && a.mean_s && a.mean_e && a.vlen && a.tlen && a.ap_off, "al_score_info: null input");
-  HUAL_REQUIRE(a.ent_s && a.ent_e, "al_score_info: null info->ent_s or info->ent_e");
-  HUAL_REQUIRE(a.sprob && a.eprob && a.uncert_frame && a.uncert_video && a.observe, "al_score_info: null output");
-  HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_score_info: need N > 0 and 2 <= ld <= 1024");
-  HUAL_LAUNCH(0.0, 44.0 * a.N * a.ld, al_score_kernel<AlScoreInfoArgs>, dim3(a.N), dim3(AL_THREADS), 2 * a.ld * sizeof(float), s, a);
-  HUAL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-namespace {
-
-// the argument checks of both folds
-int check_al_mc_fold(const AlFoldArgs& a) {
+// with a.ent set the launch also folds the passes' entropy: per frame one more store per head at k = 1, one more load and store per head
+// at k >= 2
+int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s) {
   HUAL_REQUIRE(a.ids && a.vlen && a.s && a.e, "al_mc_fold: null input");
   HUAL_REQUIRE(a.tlen && a.s0 && a.e0, "al_mc_fold: null bank");
   for (int h = 0; h < 2; ++h) HUAL_REQUIRE(a.lo[h] && a.hi[h] && a.mean[h] && a.m2[h], "al_mc_fold: null bank");
+  HUAL_REQUIRE(!a.ent[0] == !a.ent[1], "al_mc_fold: ent_s and ent_e are both set or both null");
   HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_mc_fold: need N > 0 and 2 <= ld <= 1024");
   HUAL_REQUIRE(a.B > 0 && a.T >= 2 && a.T <= a.ld, "al_mc_fold: need B > 0 and 2 <= T_b <= ld");
   HUAL_REQUIRE(a.k >= 0, "al_mc_fold: pass index k >= 0");
-  return 0;
-}
-
-}  // namespace
-
-int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s) {
-  if (const int rc = check_al_mc_fold(a)) return rc;
-  HUAL_LAUNCH(0.0, (a.k == 0 ? 16.0 : a.k == 1 ? 40.0 : 72.0) * a.B * a.T, al_mc_fold_kernel<false>, dim3(a.B), dim3(AL_THREADS), 0, s, a);
-  HUAL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// per frame one more store per head at k = 1, one more load and store per head at k >= 2
-int launch_al_mc_fold_info(const AlFoldInfoArgs& a, hipStream_t s) {
-  if (const int rc = check_al_mc_fold(a)) return rc;
-  HUAL_REQUIRE(a.ent[0] && a.ent[1], "al_mc_fold_info: null info->ent_s or info->ent_e");
-  HUAL_LAUNCH(0.0, (a.k == 0 ? 16.0 : a.k == 1 ? 48.0 : 88.0) * a.B * a.T, al_mc_fold_kernel<true>, dim3(a.B), dim3(AL_THREADS), 0, s, a);
+  const dim3 grid(a.B), block(AL_THREADS);
+  if (a.ent[0])
+    HUAL_LAUNCH(0.0, (a.k == 0 ? 16.0 : a.k == 1 ? 48.0 : 88.0) * a.B * a.T, al_mc_fold_kernel<true>, grid, block, 0, s, a);
+  else
+    HUAL_LAUNCH(0.0, (a.k == 0 ? 16.0 : a.k == 1 ? 40.0 : 72.0) * a.B * a.T, al_mc_fold_kernel<false>, grid, block, 0, s, a);
   HUAL_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -489,19 +472,37 @@ int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s) {
 
 }  // namespace hual
 
+namespace {
+
+// the set, the deterministic logits and the outputs of every hual_al_score* entry point
+AlScoreArgs score_args(const hual_al_set* set, const float* s0, const float* e0, float coff_uncert, float* sprob, float* eprob,
+                              double* uncert_frame, float* uncert_video, int32_t* observe_point) {
+  AlScoreArgs a{};
+  a.ld = set->ld; a.N = set->N; a.vlen = set->vlen; a.tlen = set->tlen;
+  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos;
+  a.s0 = s0; a.e0 = e0; a.coff_uncert = coff_uncert;
+  a.sprob = sprob; a.eprob = eprob; a.uncert_frame = uncert_frame; a.uncert_video = uncert_video; a.observe = observe_point;
+  return a;
+}
+
+// the bank's per-head statistics into the arguments of a score (read) or of a fold (written)
+template <class Args>
+void bank_stats(Args& a, const hual_al_bank* bank) {
+  a.lo[0] = bank->lo_s; a.hi[0] = bank->hi_s; a.mean[0] = bank->mean_s; a.m2[0] = bank->m2_s;
+  a.lo[1] = bank->lo_e; a.hi[1] = bank->hi_e; a.mean[1] = bank->mean_e; a.m2[1] = bank->m2_e;
+}
+
+}  // namespace
+
 extern "C" {
 
 int hual_al_score(const hual_al_set* set, const float* s0, const float* e0, const float* s1, const float* e1,
                   const float* s2, const float* e2, float coff_uncert, float* sprob, float* eprob, double* uncert_frame,
                   float* uncert_video, int32_t* observe_point, void* stream) {
   HUAL_REQUIRE(set, "hual_al_score: null set");
-  AlScoreArgs a{};
-  a.s0 = s0; a.e0 = e0; a.s1 = s1; a.e1 = e1; a.s2 = s2; a.e2 = e2;
-  a.ld = set->ld; a.N = set->N; a.vlen = set->vlen; a.tlen = set->tlen;
-  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos;
-  a.coff_uncert = coff_uncert;
-  a.sprob = sprob; a.eprob = eprob; a.uncert_frame = uncert_frame; a.uncert_video = uncert_video; a.observe = observe_point;
-  return launch_al_score(a, (hipStream_t)stream);
+  AlScoreArgs a = score_args(set, s0, e0, coff_uncert, sprob, eprob, uncert_frame, uncert_video, observe_point);
+  a.s1 = s1; a.e1 = e1; a.s2 = s2; a.e2 = e2;
+  return launch_al_score(a, AL_SRC_PAIR, (hipStream_t)stream);
 }
 
 int hual_al_score_mc(const hual_al_set* set, const float* s0, const float* e0, const hual_al_bank* bank, int K, int stat,
@@ -509,43 +510,11 @@ int hual_al_score_mc(const hual_al_set* set, const float* s0, const float* e0, c
                      int32_t* observe_point, float* uncert_model, void* stream) {
   HUAL_REQUIRE(set && bank, "hual_al_score_mc: null pointer");
   HUAL_REQUIRE(K >= 2, "hual_al_score_mc: K >= 2 stochastic passes (one sample has no spread)");
-  HUAL_REQUIRE(stat == HUAL_AL_STAT_RANGE || stat == HUAL_AL_STAT_STD, "hual_al_score_mc: stat is HUAL_AL_STAT_RANGE or HUAL_AL_STAT_STD");
   HUAL_REQUIRE(bank->N == set->N && bank->ld == set->ld, "hual_al_score_mc: bank and set differ in N or ld");
-  AlScoreMcArgs a{};
-  a.s0 = s0; a.e0 = e0;
-  a.lo_s = bank->lo_s; a.hi_s = bank->hi_s; a.m2_s = bank->m2_s; a.lo_e = bank->lo_e; a.hi_e = bank->hi_e; a.m2_e = bank->m2_e;
-  a.ld = set->ld; a.N = set->N; a.vlen = set->vlen; a.tlen = set->tlen;
-  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos;
-  a.coff_uncert = coff_uncert; a.stat = stat; a.km1 = (float)(K - 1);
-  a.sprob = sprob; a.eprob = eprob; a.uncert_frame = uncert_frame; a.uncert_video = uncert_video; a.observe = observe_point;
-  a.uncert_model = uncert_model;
-  return launch_al_score_mc(a, (hipStream_t)stream);
-}
-
-static void fold_args(AlFoldArgs& a, const hual_al_bank* bank, const int32_t* ids, const int32_t* v_len, const float* start_logits,
-                      const float* end_logits, int B, int T_b, int k) {
-  a.ids = ids; a.vlen = v_len; a.s = start_logits; a.e = end_logits; a.B = B; a.T = T_b; a.k = k;
-  a.ld = bank->ld; a.N = bank->N; a.tlen = bank->tlen; a.s0 = bank->s0; a.e0 = bank->e0;
-  a.lo[0] = bank->lo_s; a.hi[0] = bank->hi_s; a.mean[0] = bank->mean_s; a.m2[0] = bank->m2_s;
-  a.lo[1] = bank->lo_e; a.hi[1] = bank->hi_e; a.mean[1] = bank->mean_e; a.m2[1] = bank->m2_e;
-}
-
-int hual_al_mc_fold(const hual_al_bank* bank, const int32_t* ids, const int32_t* v_len, const float* start_logits,
-                    const float* end_logits, int B, int T_b, int k, void* stream) {
-  HUAL_REQUIRE(bank, "hual_al_mc_fold: null bank");
-  AlFoldArgs a{};
-  fold_args(a, bank, ids, v_len, start_logits, end_logits, B, T_b, k);
-  return launch_al_mc_fold(a, (hipStream_t)stream);
-}
-
-int hual_al_mc_fold_info(const hual_al_bank* bank, const hual_al_info* info, const int32_t* ids, const int32_t* v_len,
-                         const float* start_logits, const float* end_logits, int B, int T_b, int k, void* stream) {
-  HUAL_REQUIRE(bank, "hual_al_mc_fold_info: null bank");
-  HUAL_REQUIRE(info, "hual_al_mc_fold_info: null info");
-  AlFoldInfoArgs a{};
-  fold_args(a, bank, ids, v_len, start_logits, end_logits, B, T_b, k);
-  a.ent[0] = info->ent_s; a.ent[1] = info->ent_e;
-  return launch_al_mc_fold_info(a, (hipStream_t)stream);
+  AlScoreArgs a = score_args(set, s0, e0, coff_uncert, sprob, eprob, uncert_frame, uncert_video, observe_point);
+  bank_stats(a, bank);
+  a.stat = stat; a.km1 = (float)(K - 1); a.uncert_model = uncert_model;
+  return launch_al_score(a, AL_SRC_SPREAD, (hipStream_t)stream);
 }
 
 int hual_al_score_info(const hual_al_set* set, const float* s0, const float* e0, const hual_al_bank* bank, const hual_al_info* info,
@@ -553,20 +522,39 @@ int hual_al_score_info(const hual_al_set* set, const float* s0, const float* e0,
                        int32_t* observe_point, float* uncert_model, void* stream) {
   HUAL_REQUIRE(set && bank, "hual_al_score_info: null pointer");
   HUAL_REQUIRE(info, "hual_al_score_info: null info");
-  HUAL_REQUIRE(stat == HUAL_AL_STAT_BALD || stat == HUAL_AL_STAT_ENTROPY || stat == HUAL_AL_STAT_EXPECTED_ENTROPY,
-               "hual_al_score_info: stat is HUAL_AL_STAT_BALD, HUAL_AL_STAT_ENTROPY or HUAL_AL_STAT_EXPECTED_ENTROPY");
   HUAL_REQUIRE(K >= (stat == HUAL_AL_STAT_BALD ? 2 : 1),
                "hual_al_score_info: K >= 2 stochastic passes for BALD (one sample has no disagreement), K >= 1 for the entropies");
   HUAL_REQUIRE(bank->N == set->N && bank->ld == set->ld, "hual_al_score_info: bank and set differ in N or ld");
-  AlScoreInfoArgs a{};
-  a.s0 = s0; a.e0 = e0;
-  a.mean_s = bank->mean_s; a.ent_s = info->ent_s; a.mean_e = bank->mean_e; a.ent_e = info->ent_e;
-  a.ld = set->ld; a.N = set->N; a.vlen = set->vlen; a.tlen = set->tlen;
-  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos;
-  a.coff_uncert = coff_uncert; a.stat = stat;
-  a.sprob = sprob; a.eprob = eprob; a.uncert_frame = uncert_frame; a.uncert_video = uncert_video; a.observe = observe_point;
-  a.uncert_model = uncert_model;
-  return launch_al_score_info(a, (hipStream_t)stream);
+  AlScoreArgs a = score_args(set, s0, e0, coff_uncert, sprob, eprob, uncert_frame, uncert_video, observe_point);
+  bank_stats(a, bank);
+  a.ent[0] = info->ent_s; a.ent[1] = info->ent_e;
+  a.stat = stat; a.uncert_model = uncert_model;
+  return launch_al_score(a, AL_SRC_INFO, (hipStream_t)stream);
+}
+
+static int fold(const hual_al_bank* bank, const hual_al_info* info, const int32_t* ids, const int32_t* v_len, const float* start_logits,
+                const float* end_logits, int B, int T_b, int k, void* stream) {
+  AlFoldArgs a{};
+  a.ids = ids; a.vlen = v_len; a.s = start_logits; a.e = end_logits; a.B = B; a.T = T_b; a.k = k;
+  a.ld = bank->ld; a.N = bank->N; a.tlen = bank->tlen; a.s0 = bank->s0; a.e0 = bank->e0;
+  bank_stats(a, bank);
+  if (info) { a.ent[0] = info->ent_s; a.ent[1] = info->ent_e; }
+  return launch_al_mc_fold(a, (hipStream_t)stream);
+}
+
+int hual_al_mc_fold(const hual_al_bank* bank, const int32_t* ids, const int32_t* v_len, const float* start_logits,
+                    const float* end_logits, int B, int T_b, int k, void* stream) {
+  HUAL_REQUIRE(bank, "hual_al_mc_fold: null bank");
+  return fold(bank, nullptr, ids, v_len, start_logits, end_logits, B, T_b, k, stream);
+}
+
+// a null array must never turn this call into a plain fold: refused here, before launch_al_mc_fold chooses by a.ent
+int hual_al_mc_fold_info(const hual_al_bank* bank, const hual_al_info* info, const int32_t* ids, const int32_t* v_len,
+                         const float* start_logits, const float* end_logits, int B, int T_b, int k, void* stream) {
+  HUAL_REQUIRE(bank, "hual_al_mc_fold_info: null bank");
+  HUAL_REQUIRE(info, "hual_al_mc_fold_info: null info");
+  HUAL_REQUIRE(info->ent_s && info->ent_e, "hual_al_mc_fold_info: null info->ent_s or info->ent_e");
+  return fold(bank, info, ids, v_len, start_logits, end_logits, B, T_b, k, stream);
 }
 
 int hual_al_renew(const hual_al_set* set, const int32_t* sel, int nsel, const float* sprob, const float* eprob,

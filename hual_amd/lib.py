@@ -331,3 +331,22 @@ def span_expected_iou(start_logits, end_logits, video_seq_len, starts, ends, sco
     check(load().hual_span_expected_iou(ptr(s), ptr(e), ptr(vl), B, T, k, ptr(starts), ptr(ends), ptr(score), ptr(out[0]), ptr(out[1]),
                                         1 if reorder else 0, stream_ptr()))
     return out[0], out[1]
+
+
+def al_score(aset, s0, e0, coff_uncert, out, pair=None, bank=None, info=None, K=2, stat='range', uncert_model=None):
+    """one scoring launch over the hual_al_set `aset`, the model-uncertainty term from one source: pair = (s1, e1, s2, e2), the two
+    stochastic passes' logits (hual_al_score); else the hual_al_bank `bank` of K folded passes, read as `stat` in AL_STAT
+    (hual_al_score_mc) or, with the hual_al_info `info` beside it, in AL_STAT_INFO (hual_al_score_info).  s0 / e0: the deterministic
+    logits; out = (sprob, eprob, uncert_frame, uncert_video, observe); uncert_model (bank forms): the term itself.  All device tensors
+    f32 [N, ld] but uncert_frame f64, uncert_video f32 [N], observe i32 [N]; enqueued on the current stream."""
+    l, ref = load(), ctypes.byref
+    head = [ref(aset), ptr(s0), ptr(e0)]
+    tail = [float(coff_uncert)] + [ptr(t) for t in out]
+    if pair is not None:
+        rc = l.hual_al_score(*head, *[ptr(t) for t in pair], *tail, stream_ptr())
+    elif stat in AL_STAT_INFO:
+        rc = l.hual_al_score_info(*head, ref(bank), ref(info) if info is not None else None, int(K), AL_STAT_INFO[stat], *tail,
+                                  ptr(uncert_model), stream_ptr())
+    else:
+        rc = l.hual_al_score_mc(*head, ref(bank), int(K), AL_STAT[stat], *tail, ptr(uncert_model), stream_ptr())
+    check(rc)

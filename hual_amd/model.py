@@ -186,6 +186,11 @@ class SeqPAN:
         st = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, offset & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)
         self.rng_state.copy_(torch.from_numpy(st.copy()).to(self.device))
 
+    def get_rng(self):
+        """(seed, offset) of the Philox state: what set_rng takes"""
+        st = self.rng_state.cpu().numpy().view(np.uint32)
+        return int(st[0]) | (int(st[1]) << 32), int(st[2])
+
     # ------------------------------------------------------------------ workspace
     def reserve(self, B, T, L, C):
         """Size the workspace ONCE for the largest batch a loop will see (batch_size, max_vlen, longest query, longest word):

@@ -3,11 +3,13 @@
 
     python -m hual_amd.build --out A/parent.so     # at the parent commit
     python -m hual_amd.build --out B/this.so       # at this commit
-    python scripts/isa_diff.py A/parent.so.obj B/this.so.obj [--show KERNEL]
+    python scripts/isa_diff.py A/parent.so.obj B/this.so.obj [--show KERNEL] [--pair 'NAME_IN_A=NAME_IN_B' ...]
 
 For every kernel symbol of every device object: the instruction count of each side and whether the instruction streams are equal once
 the addresses, the encodings and the symbols of branch targets (objdump's trailing comment) are taken off; every operand, literal
-constants included, is compared.  --show prints a unified diff of one kernel's stream.  The script names no instruction and searches
+constants included, is compared.  --show prints a unified diff of one kernel's stream.  Kernels are paired by demangled name; --pair
+(repeatable) pairs a kernel that was renamed: the one kernel of A whose name holds the first substring with the one kernel of B, in the
+same object file, whose name holds the second, e.g. --pair 'AlScoreMcArgs=AlSource)1>'.  The script names no instruction and searches
 for nothing: it only diffs.
 """
 import difflib
@@ -58,12 +60,30 @@ def kernels_of(obj_dir):
     return res
 
 
+def rename(a, b, pair):
+    """the kernel of B that `pair` = 'x=y' names by y takes the key of the kernel of A named by x, shown as 'A name => B name'"""
+    x, y = pair.split('=', 1)
+    ka, kb = [k for k in a if x in k[1]], [k for k in b if y in k[1]]
+    if len(ka) != 1 or len(kb) != 1 or ka[0][0] != kb[0][0]:
+        sys.exit('--pair %s: needs one kernel of A and one of B in the same object file, found %s and %s' % (pair, ka, kb))
+    key = (ka[0][0], '%s => %s' % (ka[0][1], kb[0][1]))
+    a[key], b[key] = a.pop(ka[0]), b.pop(kb[0])
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith('--')]
-    show = sys.argv[sys.argv.index('--show') + 1] if '--show' in sys.argv else None
-    if show is not None:
-        args.remove(show)
+    argv = sys.argv[1:]
+    opts = {'--show': [], '--pair': []}
+    args = []
+    while argv:
+        x = argv.pop(0)
+        if x in opts:
+            opts[x].append(argv.pop(0))
+        else:
+            args.append(x)
+    show = opts['--show'][-1] if opts['--show'] else None
     a, b = kernels_of(args[0]), kernels_of(args[1])
+    for pair in opts['--pair']:
+        rename(a, b, pair)
     ndiff = 0
     print('%-16s %8s %8s  %-9s %s' % ('object', 'insns A', 'insns B', 'stream', 'kernel'))
     for key in sorted(set(a) | set(b)):
