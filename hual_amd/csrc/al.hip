@@ -17,6 +17,7 @@ using namespace hual;
 
 #define AL_THREADS 256
 #define AL_MAX_SEG 64
+#define AL_WAVES (AL_THREADS / 64)
 
 namespace {
 
@@ -55,16 +56,6 @@ __device__ __forceinline__ int isactive_at(const ApInfo& a, const int32_t* idx, 
   return 0;
 }
 
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max64_bperm(v);
-  __syncthreads();                                    // protects `red` against the previous use
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float m = red[0];
-  for (int w = 1; w < AL_THREADS / 64; ++w) m = fmaxf(m, red[w]);
-  return m;
-}
-
 // grid point t of np.linspace(-1, 1, T, dtype=float32): float64 arange * step + start, last point = stop, then cast
 __device__ __forceinline__ float grid_x(int t, int T) {
   if (t == T - 1) return 1.0f;
@@ -88,7 +79,7 @@ __device__ void gauss_block(double center, double width, int vlen, int T, float*
     out[t] = w;
     mx = fmaxf(mx, w);
   }
-  mx = block_max(mx, red);
+  mx = block_reduce<BlockMaxF, AL_WAVES>(mx, red);
   for (int t = threadIdx.x; t < T; t += AL_THREADS) out[t] = t < vlen ? (out[t] / mx) * peak : 0.0f;
   __syncthreads();
 }
@@ -181,10 +172,10 @@ __device__ __forceinline__ void keep_uncert(const AlScoreArgs& a, size_t i, floa
 template <AlSource SRC>
 __global__ __launch_bounds__(AL_THREADS) void al_score_kernel(AlScoreArgs a) {
   extern __shared__ float lds[];            // dist[T] | tmp[T]
-  __shared__ float red[AL_THREADS / 64];
-  __shared__ double redd[AL_THREADS / 64];
-  __shared__ double vs[AL_THREADS / 64];
-  __shared__ int redi[AL_THREADS / 64];
+  __shared__ float red[AL_WAVES];
+  __shared__ double redd[AL_WAVES];
+  __shared__ double vs[AL_WAVES];
+  __shared__ int redi[AL_WAVES];
   __shared__ int seg[2 * AL_MAX_SEG];
   __shared__ int nseg;
   const int n = blockIdx.x;
@@ -214,22 +205,13 @@ __global__ __launch_bounds__(AL_THREADS) void al_score_kernel(AlScoreArgs a) {
     a.uncert_frame[row + t] = uf;
     if (uf > best) { best = uf; besti = t; }       // ascending t per thread: first maximum kept
   }
-  // block reduction: sum of the model uncertainty; argmax of uncert_frame with first-index ties
-  for (int o = 32; o > 0; o >>= 1) {
-    vsum += __shfl_xor(vsum, o);
-    const double ob = __shfl_xor(best, o);
-    const int oi = __shfl_xor(besti, o);
-    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { vs[threadIdx.x >> 6] = vsum; redd[threadIdx.x >> 6] = best; redi[threadIdx.x >> 6] = besti; }
-  __syncthreads();
+  // block reduction: argmax of uncert_frame with first-index ties; sum of the model uncertainty, whose barrier publishes both
+  wave_best(best, besti);
+  if ((threadIdx.x & 63) == 0) { redd[threadIdx.x >> 6] = best; redi[threadIdx.x >> 6] = besti; }
+  vsum = block_reduce<BlockSumD, AL_WAVES, false>(vsum, vs);
   if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int w = 0; w < AL_THREADS / 64; ++w) {
-      s += vs[w];
-      if (redd[w] > best || (redd[w] == best && redi[w] < besti)) { best = redd[w]; besti = redi[w]; }
-    }
-    a.uncert_video[n] = (float)s;
+    best_of_waves(redd, redi, AL_WAVES, best, besti);
+    a.uncert_video[n] = (float)vsum;
     a.observe[n] = besti;
   }
 }
@@ -312,9 +294,9 @@ __global__ __launch_bounds__(AL_THREADS) void al_mc_fold_kernel(AlFoldArgs a) {
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(AL_THREADS) void al_renew_kernel(AlRenewArgs a) {
   extern __shared__ float lds[];            // ds[T] | de[T] | tmp[T] | (8-byte aligned) ss[T] | es[T] doubles
-  __shared__ float red[AL_THREADS / 64];
-  __shared__ double redd[2][AL_THREADS / 64];
-  __shared__ int redi[2][AL_THREADS / 64];
+  __shared__ float red[AL_WAVES];
+  __shared__ double redd[2][AL_WAVES];
+  __shared__ int redi[2][AL_WAVES];
   __shared__ int seg[2 * AL_MAX_SEG];
   __shared__ int nseg;
   const int n = a.sel ? a.sel[blockIdx.x] : (int)blockIdx.x;
@@ -390,22 +372,16 @@ __global__ __launch_bounds__(AL_THREADS) void al_renew_kernel(AlRenewArgs a) {
       if (cmax > be) { be = cmax; bei = t; }
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    const double obs = __shfl_xor(bs, o), obe = __shfl_xor(be, o);
-    const int osi = __shfl_xor(bsi, o), oei = __shfl_xor(bei, o);
-    if (obs > bs || (obs == bs && osi < bsi)) { bs = obs; bsi = osi; }
-    if (obe > be || (obe == be && oei < bei)) { be = obe; bei = oei; }
-  }
+  wave_best(bs, bsi);
+  wave_best(be, bei);
   if ((threadIdx.x & 63) == 0) {
     redd[0][threadIdx.x >> 6] = bs; redi[0][threadIdx.x >> 6] = bsi;
     redd[1][threadIdx.x >> 6] = be; redi[1][threadIdx.x >> 6] = bei;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 0; w < AL_THREADS / 64; ++w) {
-      if (redd[0][w] > bs || (redd[0][w] == bs && redi[0][w] < bsi)) { bs = redd[0][w]; bsi = redi[0][w]; }
-      if (redd[1][w] > be || (redd[1][w] == be && redi[1][w] < bei)) { be = redd[1][w]; bei = redi[1][w]; }
-    }
+    best_of_waves(redd[0], redi[0], AL_WAVES, bs, bsi);
+    best_of_waves(redd[1], redi[1], AL_WAVES, be, bei);
     a.new_idx[2 * n] = bsi;
     a.new_idx[2 * n + 1] = bei;
   }

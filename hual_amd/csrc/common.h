@@ -5,6 +5,7 @@
 #include <string>
 #include "../../include/hual_seqpan.h"
 #include "wave.h"
+#include "block.h"
 
 #define HUAL_D 128          // hidden size the kernels are specialised for (configs/*/SeqPAN.yaml model.dim)
 #define HUAL_H 8            // heads

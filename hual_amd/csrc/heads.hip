@@ -15,39 +15,6 @@ extern "C" int hual_debug_stamps(unsigned long long* out, int n) {
 #define HEADS_STAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ float block_sum(float v, float* sm) {   // blockDim multiple of 64, <= 256
-  v = wave_sum64(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[w] = v;
-  __syncthreads();
-  float s = 0.f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += sm[i];
-  return s;   // sm must hold blockDim.x/64 floats
-}
-// double-precision block sum (the span selection's softmax denominator: the sum of <= 256 floats in double is exact
-// to ~2^-53, so its float rounding does not depend on the order of the additions)
-__device__ __forceinline__ double block_sum_d(double v, double* sm) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[w] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += sm[i];
-  return s;
-}
-__device__ __forceinline__ float block_max(float v, float* sm) {
-  v = wave_max64_bperm(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[w] = v;
-  __syncthreads();
-  float s = -INFINITY;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s = fmaxf(s, sm[i]);
-  return s;
-}
-
 // ------------------------------------------------------------------------------------------------------
 // weighted pooling + pooled half of cq_cat/dense.  One block of 256 threads per clip: the L row dots are spread over
 // 8 groups of 32 lanes (float4 per lane, shuffle reduction) instead of L block-wide reductions in sequence.
@@ -269,38 +236,6 @@ __global__ __launch_bounds__(256) void match_bwd_kernel(MatchArgs a, MatchBwd g,
 //   3. dZ = dlogit * w * (hidden > 0) for the two hidden layers and the per-clip sums of d w, d b (folded by colsum_kernel)
 //   4. the workgroup that finishes last closes the loss: matching-loss denominator and the four reported terms
 // With `h` null the logits are read instead of computed (hual_span_argmax).
-// two block-wide reductions for one pair of barriers
-__device__ __forceinline__ void block_max2(float& a, float& b, float* sm) {       // sm: 2 * (blockDim.x / 64) floats
-  a = wave_max64_bperm(a); b = wave_max64_bperm(b);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { sm[w] = a; sm[nw + w] = b; }
-  __syncthreads();
-  float x = -INFINITY, y = -INFINITY;
-  for (int i = 0; i < nw; ++i) { x = fmaxf(x, sm[i]); y = fmaxf(y, sm[nw + i]); }
-  a = x; b = y;
-}
-__device__ __forceinline__ void block_sum2_d(double& a, double& b, double* sm) {
-  for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { sm[w] = a; sm[nw + w] = b; }
-  __syncthreads();
-  double x = 0.0, y = 0.0;
-  for (int i = 0; i < nw; ++i) { x += sm[i]; y += sm[nw + i]; }
-  a = x; b = y;
-}
-__device__ __forceinline__ void block_sum3(float& a, float& b, float& c, float* sm) {
-  a = wave_sum64(a); b = wave_sum64(b); c = wave_sum64(c);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { sm[w] = a; sm[nw + w] = b; sm[2 * nw + w] = c; }
-  __syncthreads();
-  float x = 0.f, y = 0.f, z = 0.f;
-  for (int i = 0; i < nw; ++i) { x += sm[i]; y += sm[nw + i]; z += sm[2 * nw + i]; }
-  a = x; b = y; c = z;
-}
-
 // NR = rows of the clip per 32-lane group (T <= 16 NR): the hidden rows are loaded ONCE, all loads in flight together, and stay
 // in registers for step 3
 template <int NR>
@@ -364,7 +299,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a, int T, int B) {
       ze = ze_[t] * m + HUAL_MASK_VALUE * (1.0f - m);
     }
     float mxs = zs, mxe = ze;
-    block_max2(mxs, mxe, sm);
+    block_reduce<BlockMaxF>(mxs, mxe, sm);
     // Reproducible float32 softmax (the span indices must be BIT EXACT, north_star): exp of the float32 difference is
     // evaluated in double and rounded once to float32 (= the correctly rounded float32 exp), the denominator is the
     // double-precision sum of those floats rounded once, the quotient is an IEEE float32 division.  None of the three
@@ -372,7 +307,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a, int T, int B) {
     const float xs = in ? (float)exp((double)(zs - mxs)) : 0.f;
     const float xe = in ? (float)exp((double)(ze - mxe)) : 0.f;
     double dss = (double)xs, dse = (double)xe;
-    block_sum2_d(dss, dse, smd);
+    block_reduce<BlockSumD>(dss, dse, smd);
     const float sums = (float)dss, sume = (float)dse;
     const float p_s = __fdiv_rn(xs, sums), p_e = __fdiv_rn(xe, sume);
     HEADS_STAMP(2);
@@ -380,7 +315,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a, int T, int B) {
       const float y1 = in ? a.y1[b * T + t] : 0.f, y2 = in ? a.y2[b * T + t] : 0.f;
       const float lsm_s = zs - mxs - logf(sums), lsm_e = ze - mxe - logf(sume);
       float lsum = in ? -(y1 * lsm_s + y2 * lsm_e) : 0.f, y1s = y1, y2s = y2;
-      block_sum3(lsum, y1s, y2s, sm);
+      block_reduce<BlockSumF>(lsum, y1s, y2s, sm);
       if (t == 0 && a.loc_part) a.loc_part[b] = lsum * a.inv_batch;
       if (in) {
         const float ds = (p_s * y1s - y1) * m * a.inv_batch, de = (p_e * y2s - y2) * m * a.inv_batch;
@@ -420,21 +355,16 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a, int T, int B) {
     }
     if (tid < 256) {
       int is = t, ie = t;
-      for (int off = 32; off >= 1; off >>= 1) {
-        float ovs = __shfl_xor(vs, off); int ois = __shfl_xor(is, off);
-        if (ovs > vs || (ovs == vs && ois < is)) { vs = ovs; is = ois; }
-        float ove = __shfl_xor(ve, off); int oie = __shfl_xor(ie, off);
-        if (ove > ve || (ove == ve && oie < ie)) { ve = ove; ie = oie; }
-      }
+      wave_best(vs, is);
+      wave_best(ve, ie);
       if ((t & 63) == 0) { bestv[0][t >> 6] = vs; besti[0][t >> 6] = is; bestv[1][t >> 6] = ve; besti[1][t >> 6] = ie; }
     }
     __syncthreads();
     if (t == 0) {
-      float v = bestv[0][0]; int i = besti[0][0];
-      for (int w = 1; w < 4; ++w) if (bestv[0][w] > v || (bestv[0][w] == v && besti[0][w] < i)) { v = bestv[0][w]; i = besti[0][w]; }
+      float v; int i;
+      best_of_waves(bestv[0], besti[0], 4, v, i);
       a.start_index[b] = i;
-      v = bestv[1][0]; i = besti[1][0];
-      for (int w = 1; w < 4; ++w) if (bestv[1][w] > v || (bestv[1][w] == v && besti[1][w] < i)) { v = bestv[1][w]; i = besti[1][w]; }
+      best_of_waves(bestv[1], besti[1], 4, v, i);
       a.end_index[b] = i;
       if (poison != poison || nanlogit) { a.start_index[b] = -1; a.end_index[b] = -1; }
     }
@@ -498,7 +428,7 @@ __device__ __forceinline__ float loss_tail_body(const LossTailArgs& a, float* sm
     for (int i = tid; i < a.novf; i += 256) bad |= a.ovf[i] != 0u;
     bad = __syncthreads_or(bad);
   }
-  block_sum3(cs, ms, ls, sm);
+  block_reduce<BlockSumF>(cs, ms, ls, sm);
   const float denom = a.denom_dev ? *a.denom_dev : (a.override_denom > 0.f ? a.override_denom : ms + 1e-12f);
   if (write && tid == 0) {
     float* la = a.loss_acc;
@@ -538,8 +468,8 @@ __device__ __forceinline__ void align_pool_body(const AlignPool& a, const RowSpa
   float tc = 0.f, vc = 0.f;
   for (int l = threadIdx.x; l < L; l += 512) tc += rs.rowmask[rs.Nv + b * L + l];
   for (int t = threadIdx.x; t < T; t += 512) vc += rs.rowmask[b * T + t];
-  tc = block_sum(tc, sm);       // exact: the mask is 0/1
-  vc = block_sum(vc, sm);
+  tc = block_reduce<BlockSumF>(tc, sm);       // exact: the mask is 0/1
+  vc = block_reduce<BlockSumF>(vc, sm);
   float ts = 0.f, vs = 0.f;
 #pragma unroll 8
   for (int l = grp; l < L; l += 4) ts += a.F2[(size_t)(rs.Nv + b * L + l) * HUAL_D + c];     // padded words included (layers.py:214)
@@ -551,8 +481,8 @@ __device__ __forceinline__ void align_pool_body(const AlignPool& a, const RowSpa
   ts = part[0][0][c] + part[0][1][c] + part[0][2][c] + part[0][3][c];
   vs = part[1][0][c] + part[1][1][c] + part[1][2][c] + part[1][3][c];
   const float tp = ts / tc;
-  const float tn = block_sum(grp == 0 ? tp * tp : 0.f, sm);
-  const float vn = block_sum(grp == 0 ? vs * vs : 0.f, sm);
+  const float tn = block_reduce<BlockSumF>(grp == 0 ? tp * tp : 0.f, sm);
+  const float vn = block_reduce<BlockSumF>(grp == 0 ? vs * vs : 0.f, sm);
   if (grp == 0) {
     a.tpre[b * HUAL_D + c] = tp;
     a.vpre[b * HUAL_D + c] = vs;
@@ -565,16 +495,6 @@ __device__ __forceinline__ void align_pool_body(const AlignPool& a, const RowSpa
 // Round 5: evaluated in DOUBLE.  The gradient of a row, p (log p + 1 - 2 p' - dot), is a small difference of O(1) terms (log-sum-exp
 // ~ ln Bg against similarities in [-1, 1]): in float32 its rounding put 1.4e-5 of noise on d that (a float32 PyTorch evaluation: 5e-6)
 // that every query-side gradient downstream carried - at [Bg, Bg] <= 1024 x 1024 elements per step the double pipe costs nothing.
-__device__ __forceinline__ double block_max_d(double v, double* sm) {
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[w] = v;
-  __syncthreads();
-  double s = sm[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) s = fmax(s, sm[i]);
-  return s;
-}
 __device__ __forceinline__ void align_sim_rows_body(const AlignSim& a, int i) {
   __shared__ float ti[HUAL_D], vi[HUAL_D];
   __shared__ double sm[4];
@@ -597,12 +517,12 @@ __device__ __forceinline__ void align_sim_rows_body(const AlignSim& a, int i) {
   }
   __syncthreads();
   for (int j = tid; j < Bg; j += 256) { mxa = fmax(mxa, sa[j]); mxq = fmax(mxq, sq[j]); }
-  mxa = block_max_d(mxa, sm);
-  mxq = block_max_d(mxq, sm);
+  mxa = block_reduce<BlockMaxD>(mxa, sm);
+  mxq = block_reduce<BlockMaxD>(mxq, sm);
   double suma = 0.0, sumq = 0.0;
   for (int j = tid; j < Bg; j += 256) { suma += exp(sa[j] - mxa); sumq += exp(sq[j] - mxq); }
-  suma = block_sum_d(suma, sm);
-  sumq = block_sum_d(sumq, sm);
+  suma = block_reduce<BlockSumD>(suma, sm);
+  sumq = block_reduce<BlockSumD>(sumq, sm);
   const double lsa = mxa + log(suma), lsq = mxq + log(sumq);
   // loss_i = sum Pq logPq + sum Pv logPv - 2 sum Pq Pv ; dPq = logPq + 1 - 2Pv ; dPv = logPv + 1 - 2Pq
   double li = 0.0, dotq = 0.0, dota = 0.0;
@@ -613,9 +533,9 @@ __device__ __forceinline__ void align_sim_rows_body(const AlignSim& a, int i) {
     dotq += pq * (lpq + 1.0 - 2.0 * pv);
     dota += pv * (lpv + 1.0 - 2.0 * pq);
   }
-  li = block_sum_d(li, sm);
-  dotq = block_sum_d(dotq, sm);
-  dota = block_sum_d(dota, sm);
+  li = block_reduce<BlockSumD>(li, sm);
+  dotq = block_reduce<BlockSumD>(dotq, sm);
+  dota = block_reduce<BlockSumD>(dota, sm);
   if (tid == 0) {
     if (a.row_loss) a.row_loss[i] = (float)li;
     else if (a.loss_acc) atomicAdd(a.loss_acc + LA_ALIGN, (float)li);

@@ -22,10 +22,8 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* g, size_t n, f
     v = make_float4(v.x * prescale, v.y * prescale, v.z * prescale, v.w * prescale);
     s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
-  s = wave_sum64(s);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];     // per-block partial: no zeroing, no atomics
+  s = block_reduce<BlockSumF, 4, false>(s, sm);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;     // per-block partial: no zeroing, no atomics
 }
 
 __global__ __launch_bounds__(256) void zero_kernel(float* p, size_t n) {

@@ -1,6 +1,6 @@
 // The span distribution's probability stage, shared by the per-clip span kernels (topk.hip, spanconf.hip): the masked softmaxes of
-// the start / end logits exactly as the span stage of heads_kernel computes them (same masking, same max / double-sum reduction
-// trees, same rounding), so every kernel that includes this sees the numbers of hual_span_argmax bit for bit.
+// the start / end logits exactly as the span stage of heads_kernel computes them (same masking, the same code for the max and the
+// double-sum reductions - block.h -, same rounding), so every kernel that includes this sees the numbers of hual_span_argmax bit for bit.
 #pragma once
 #include "common.h"
 
@@ -21,26 +21,20 @@ __device__ __forceinline__ int span_row_poisoned(const float* __restrict__ zs_, 
 // heads_kernel's span stage (mask_logits, reproducible softmax; oracle/seqpan_ref.py::softmax_cr)
 __device__ __forceinline__ void span_probabilities(const float* __restrict__ zs_, const float* __restrict__ ze_, size_t row, int T, int v,
                                                    float* ps, float* pe, float* smf, double* smd) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int t = threadIdx.x;
   const bool in = t < T;
   float zs = -INFINITY, ze = -INFINITY;
   if (in) {
     zs = t < v ? zs_[row + t] : HUAL_MASK_VALUE;      // (= x * 0 + HUAL_MASK_VALUE for a finite padding logit, never read here)
     ze = t < v ? ze_[row + t] : HUAL_MASK_VALUE;
   }
-  float mxs = wave_max64_bperm(zs), mxe = wave_max64_bperm(ze);
-  if (lane == 0) { smf[w] = mxs; smf[SPAN_WAVES + w] = mxe; }
-  __syncthreads();
-  mxs = -INFINITY; mxe = -INFINITY;
-  for (int q = 0; q < SPAN_WAVES; ++q) { mxs = fmaxf(mxs, smf[q]); mxe = fmaxf(mxe, smf[SPAN_WAVES + q]); }
+  // (smf / smd are fresh: no barrier in front.  Waves 4.. contribute -inf and exact zeros, as waves 4 - 7 of heads_kernel do)
+  float mxs = zs, mxe = ze;
+  block_reduce<BlockMaxF, SPAN_WAVES, false>(mxs, mxe, smf);
   const float xs = in ? (float)exp((double)(zs - mxs)) : 0.f;
   const float xe = in ? (float)exp((double)(ze - mxe)) : 0.f;
   double dss = (double)xs, dse = (double)xe;
-  for (int off = 32; off >= 1; off >>= 1) { dss += __shfl_xor(dss, off); dse += __shfl_xor(dse, off); }
-  if (lane == 0) { smd[w] = dss; smd[SPAN_WAVES + w] = dse; }
-  __syncthreads();
-  dss = 0.0; dse = 0.0;
-  for (int q = 0; q < SPAN_WAVES; ++q) { dss += smd[q]; dse += smd[SPAN_WAVES + q]; }      // (waves 4.. add exact zeros, as in heads_kernel)
+  block_reduce<BlockSumD, SPAN_WAVES, false>(dss, dse, smd);
   if (t < 256) {
     ps[t] = __fdiv_rn(xs, (float)dss);
     pe[t] = __fdiv_rn(xe, (float)dse);

@@ -93,16 +93,10 @@ __global__ __launch_bounds__(TK_THREADS) void span_topk_kernel(const float* __re
     tk_scan(c0, c1, v, L, ps, pe, sel, 0, TK_NONE, nms_iou, bs, bk);
     for (int r = 0; r < k; ++r) {
       float rs = bs; int rk = bk;
-      for (int off = 32; off >= 1; off >>= 1) {
-        const float os = __shfl_xor(rs, off);
-        const int ok = __shfl_xor(rk, off);
-        if (tk_better(os, ok, rs, rk)) { rs = os; rk = ok; }
-      }
+      wave_best(rs, rk, tk_better);
       if (lane == 0) { wbs[r & 1][w] = rs; wbk[r & 1][w] = rk; }      // (double buffered: one barrier per round)
       __syncthreads();
-      rs = wbs[r & 1][0]; rk = wbk[r & 1][0];
-      for (int q = 1; q < TK_WAVES; ++q)
-        if (tk_better(wbs[r & 1][q], wbk[r & 1][q], rs, rk)) { rs = wbs[r & 1][q]; rk = wbk[r & 1][q]; }
+      best_of_waves(wbs[r & 1], wbk[r & 1], TK_WAVES, rs, rk, tk_better);
       if (rk == TK_NONE) break;      // (uniform) fewer than k candidates survive
       if (t == 0) {
         sel[r] = rk;

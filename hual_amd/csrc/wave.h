@@ -105,11 +105,17 @@ __device__ __forceinline__ double wave_sum64_f64(double v, int lane = threadIdx.
   }
   return v;
 }
+// The same sum over xor 32, 16, .. 1 (ds_bpermute): another summation order, so other last bits - both stay.  Pinned to this one: the
+// double sums of block.h (heads.hip, spanprob.h and its span kernels, al.hip); to the ascending one above: the column sums of spanconf.hip.
+__device__ __forceinline__ double wave_sum64_f64_desc(double v) {
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
 // The same maximum (max is exact and commutative: identical results) with its last step through the LDS crossbar (ds_bpermute): the
-// form the workgroup maxima of the context-query kernels (cq_wgmax_put), heads.hip, al.hip, topk.hip and the V maximum of the
-// attention backward are compiled with.  Ending them on lane_xor32 gives 15 kernels another instruction stream, 11 of them outside
-// the benchmark step (profiles/wave_primitives_isa.txt: instruction counts in both forms); a caller moves to wave_max64 together
-// with a timing of its kernels against this form.  New code uses wave_max64.
+// form the workgroup maxima of the context-query kernels (cq_wgmax_put), of block.h (BlockMaxF: heads.hip, al.hip, and spanprob.h for
+// topk.hip and spanconf.hip) and the V maximum of the attention backward are compiled with.  Ending them on lane_xor32 gives 15
+// kernels another instruction stream, 11 of them outside the benchmark step (profiles/wave_primitives_isa.txt: instruction counts in
+// both forms); a caller moves to wave_max64 together with a timing of its kernels against this form.  New code uses wave_max64.
 __device__ __forceinline__ float wave_max64_bperm(float v) {
   v = fast_max32(v);
   return fmaxf(v, __shfl_xor(v, 32));
