@@ -32,6 +32,11 @@ the deterministic pass's span distribution ('prop_conf', in [0, 1]) and that dis
 hual_span_expected_iou launch per batch, fetched with the deterministic fetches.  update_labels(rank_by='span_risk') then selects the
 half of the set with the smallest risk 1 - prop_conf instead of the smallest uncert_video.  Off by default: every launch, record and
 result is then what it was.
+
+The question by expected information gain (neither has): update_labels(observe_by='info_gain') asks every selected sample about the
+frame whose answer says most about the span - the argmax of h2(q(t)), q(t) the probability that t lies inside the span under the span
+distribution of the deterministic pass restricted to the spans the earlier answers allow (LabelUpdater.query, one hual_al_query launch
+over the whole set) - instead of the argmax of uncert_frame.  Off by default: every launch, record and result is then what it was.
 """
 import ctypes
 import math
@@ -549,6 +554,13 @@ class LabelUpdater:
                      pair=self.logits[2:] if self.logits is not None else None, bank=self.bank_c,
                      info=self.bank.info_c if self.bank is not None else None, K=self.K, stat=self.stat)
 
+    def query(self, frames=True):
+        """the span posterior given the set's answered active points and the frame of most expected information gain (hual_al_query,
+        one launch) on the updater's set and deterministic logits - of the records or of the bank.  Leaves incl, gain (f32 [N, ld];
+        None with frames=False), query_point (i32 [N]), query_gain, post_entropy and agree (f32 [N]) as device tensors."""
+        (self.incl, self.gain, self.query_point, self.query_gain, self.post_entropy,
+         self.agree) = lib.al_query(self.set, self._s0, self._e0, self.tlen_h, frames=frames)
+
     def renew(self, sel, old_idx, coff):
         """sel: sample ids (numpy); old_idx: int [N,2]; returns new_idx int32 [N,2] (valid for the selected rows)"""
         sel_d = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
@@ -561,6 +573,7 @@ class LabelUpdater:
 
 
 RANK_BY = ('uncert_video', 'span_risk')
+OBSERVE_BY = ('uncert_frame', 'info_gain')
 
 
 def span_risk(last_prop):
@@ -571,7 +584,7 @@ def span_risk(last_prop):
 
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
-                  rank_by='uncert_video'):
+                  rank_by='uncert_video', observe_by='uncert_frame'):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -583,9 +596,15 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     that recorded term, whichever statistic it is.
     rank_by: 'uncert_video' (the reference's key) or 'span_risk' - the samples are then ranked by 1 - prop_conf of their records
     (infer_trainset(span_conf=True)), the same stable argsort, the same half selected; everything else in the round is unchanged.
+    observe_by: 'uncert_frame' (the reference's frame: the argmax of uncert_frame) or 'info_gain' - every selected sample is then asked
+    about the frame of most expected information gain under its span posterior given the answers of the earlier rounds
+    (LabelUpdater.query, one more launch; where that gain is not positive - a collapsed posterior, contradictory answers, a poisoned
+    row - the reference's frame); ranking, selection, append_AP, renew and the time conversion are unchanged.
     """
     if rank_by not in RANK_BY:
         raise ValueError("rank_by: 'uncert_video' or 'span_risk'")
+    if observe_by not in OBSERVE_BY:
+        raise ValueError("observe_by: 'uncert_frame' or 'info_gain'")
     risk = span_risk(last_prop) if rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -603,6 +622,10 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     up.score(coff[6])
     uv = up.uncert_video.cpu().numpy()
     observe = up.observe.cpu().numpy()
+    ask = observe
+    if observe_by == 'info_gain':
+        up.query(frames=return_debug)                            # (before set_active_points: on the answers of the earlier rounds)
+        ask = np.where(up.query_gain.cpu().numpy() > 0, up.query_point.cpu().numpy(), observe)
     order = np.argsort(uv if risk is None else risk, kind='stable')      # sorted(key=uncert_video), ties in sample order
     sel = order[:math.ceil(N / 2)]
     vlen = up.vlen_h
@@ -610,7 +633,7 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     old_idx = np.array([[_round_half_even_index(t, data_old[i][1], int(vlen[i])) for t in data_old[i][2]] for i in range(N)])
     # append_AP (utils_hual.py:133-139): the annotator answers "is the observed frame inside the ground-truth span?"
     for i in sel:
-        p = int(observe[i])
+        p = int(ask[i])
         is_pos = gt_idx[i, 0] <= p <= gt_idx[i, 1]
         data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
         aps[i].append((p, bool(is_pos)))
@@ -625,6 +648,9 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
                    old_idx=old_idx, updater=up)
         if risk is not None:
             dbg['span_risk'] = risk
+        if observe_by == 'info_gain':
+            dbg.update(query_point=up.query_point.cpu().numpy(), query_gain=up.query_gain.cpu().numpy(),
+                       post_entropy=up.post_entropy.cpu().numpy(), agree=up.agree.cpu().numpy(), observe_used=ask)
         return data_old, dbg
     return data_old
 
@@ -643,7 +669,8 @@ def labels_from_times(data, vlens):
 
 
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
-              shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False):
+              shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
+              observe_by='uncert_frame'):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -656,6 +683,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     A `bank` that already holds the passes behind last_prop (the previous round's metrics['mc_bank']) feeds this round's label
     update on the device before it is refilled; otherwise last_prop's own 'prop_uncert' or 'prop_logits1/2' do.
     span_conf=True: the round's inference records 'prop_conf' / 'prop_span_entropy' (infer_trainset).
+    observe_by: the frame the round's label update asks the annotator about (update_labels).
     Returns (new train list, new results records - rank 0 only, else None -, metrics dict)."""
     import time
     from . import dist as hdist
@@ -664,7 +692,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     t0 = time.perf_counter()
     prev = bank if bank is not None and bank.K >= 2 else None
     new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
-                             mc_stat=mc_stat) if rank == 0 else None
+                             mc_stat=mc_stat, observe_by=observe_by) if rank == 0 else None
     new_data = hdist.broadcast_object(new_data)
     torch.cuda.synchronize()
     t1a = time.perf_counter()

@@ -64,7 +64,22 @@ struct AlRenewArgs {
   int32_t* new_idx;                           // [N, 2] (rows of unselected samples are left untouched)
 };
 
+// hual_al_query: the posterior over spans given the answered active points, and the frame whose answer carries most information
+struct AlQueryArgs {
+  int ld, N;                                  // the set (hual_al_set), as in AlScoreArgs
+  const int32_t* vlen;
+  const int32_t* tlen;
+  const int32_t* ap_off;
+  const int32_t* ap_idx;
+  const int8_t* ap_pos;
+  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
+  float *incl, *gain;                         // [N, ld] q(t) and h2(q(t)) in bits, columns [0, tlen[n]) (NULL, both: not written)
+  int32_t* query_point;                       // [N] first frame of maximal gain
+  float *query_gain, *post_entropy, *agree;   // [N]
+};
+
 int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s);
+int launch_al_query(const AlQueryArgs& a, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);
 

@@ -159,6 +159,7 @@ def load():
     lib.hual_al_mc_fold_info.argtypes = [P(hual_al_bank), P(hual_al_info), vp, vp, vp, vp, i32, i32, i32, vp]
     lib.hual_al_score_info.argtypes = [P(hual_al_set), vp, vp, P(hual_al_bank), P(hual_al_info), i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_al_renew.argtypes = [P(hual_al_set), vp, i32, vp, vp, vp, P(ctypes.c_double), vp, vp]
+    lib.hual_al_query.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_carry.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     _lib = lib
@@ -350,3 +351,41 @@ def al_score(aset, s0, e0, coff_uncert, out, pair=None, bank=None, info=None, K=
     else:
         rc = l.hual_al_score_mc(*head, ref(bank), int(K), AL_STAT[stat], *tail, ptr(uncert_model), stream_ptr())
     check(rc)
+
+
+AL_QUERY_MAX_T = 256      # the span kernels' row length (csrc/spanprob.h)
+
+
+def al_query(aset, s0, e0, tlen, frames=True, out=None):
+    """the posterior over spans of every sample of the hual_al_set `aset` given its answered active points, and the frame whose answer
+    carries most information about the span (hual_al_query), one launch enqueued on the current stream.  s0 / e0: the deterministic
+    logits f32 [N, ld] on the device; tlen: the set's row lengths on the HOST (array or list) - the kernel handles rows of at most 256
+    frames, and a longer one is refused here, before the launch.
+    -> (incl, gain, query_point, query_gain, post_entropy, agree): f32 [N, ld] twice (None with frames=False: only the per-sample outputs
+    are written), i32 [N], f32 [N] three times.  out: such a tuple of contiguous device tensors to write into instead (incl / gain may be
+    None); columns beyond a row's tlen keep what they held (0 in tensors allocated here)."""
+    import numpy as np
+    import torch
+    N, ld = int(aset.N), int(aset.ld)
+    tl = np.asarray(tlen)
+    if tl.size != N:
+        raise HualError('al_query: tlen must hold N = %d row lengths' % N)
+    if int(tl.max()) > AL_QUERY_MAX_T:
+        raise HualError('al_query: a row of %d frames - the span posterior handles at most %d' % (int(tl.max()), AL_QUERY_MAX_T))
+    for x in (s0, e0):
+        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous():
+            raise HualError('al_query: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d]' % (N, ld))
+    dev = s0.device
+    if out is None:
+        out = (torch.zeros(N, ld, device=dev) if frames else None, torch.zeros(N, ld, device=dev) if frames else None,
+               torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev))
+    else:
+        if len(out) != 6 or any(o is None for o in out[2:]):
+            raise HualError('al_query: out is (incl, gain, query_point, query_gain, post_entropy, agree); only incl / gain may be None')
+        shapes = ((N, ld), (N, ld), (N,), (N,), (N,), (N,))
+        for i, (o, shape) in enumerate(zip(out, shapes)):
+            dt = torch.int32 if i == 2 else torch.float32
+            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
+                raise HualError('al_query: out tensors must be contiguous, on the logits\' device, f32 [N, ld] / [N] (query_point: i32 [N])')
+    check(load().hual_al_query(ctypes.byref(aset), ptr(s0), ptr(e0), *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)

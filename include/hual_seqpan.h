@@ -558,6 +558,38 @@ int hual_al_score_info(const hual_al_set* set, const float* s0, const float* e0,
                        int32_t* observe_point, float* uncert_model, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The frame to ask about, by expected information gain under the span posterior (HUAL_ABI_VERSION unchanged: one new symbol, nothing
+ * else moved).  The annotator answers "is frame t inside the ground-truth span?" (append_AP, utils_hual.py:133-139); the answer is a
+ * function of the true span, so its mutual information with the span is the entropy of the answer, h2(q(t)) bits, q(t) the posterior
+ * probability that t lies inside the span given the answers so far.  Per sample n of the set, T = tlen[n], v = vlen[n] clamped to
+ * [0, T], s0 / e0 f32 [N, ld] the deterministic logits (prop_logits, or a bank's s0 / e0):
+ *  - p_s, p_e: the float32 softmaxes of the logits over [0, v), bit for bit those of hual_span_argmax (as hual_span_expected_iou);
+ *    w(i,j) = (double)p_s[i] * (double)p_e[j] for 0 <= i <= j < v, Z = sum of w.
+ *  - active points with a frame index outside [0, v) are ignored.  pos = the ap_pos = 1 entries, neg = the ap_pos = 0 entries.  The
+ *    consistent set A: every span with i <= min(pos) and max(pos) <= j (when pos is not empty) and no neg frame in [i, j]; Z_A = the
+ *    sum of w over A.
+ *  - incl [N, ld] (may be NULL): q(t) = (sum of w over the spans of A with i <= t <= j) / Z_A, float64, clamped to [0, 1], stored as
+ *    float32.  gain [N, ld] (may be NULL): h2((float)q(t)), the float32 binary entropy of hual_al_score_info.  Columns [0, T) are
+ *    written, 0 at t >= v; columns [T, ld) are not touched.
+ *  - query_point [N]: the first t < v of maximal gain (the first-maximal-frame rule of hual_al_score); query_gain [N]: that gain.
+ *  - post_entropy [N]: the entropy of the posterior in bits, log2(Z_A) - (1/Z_A) * sum over A of w * (log2f(p_s[i]) + log2f(p_e[j])),
+ *    terms with w == 0 skipped, float64 accumulation, clamped at >= 0, stored as float32.  With no active point it is the span_entropy
+ *    of hual_span_expected_iou up to rounding.
+ *  - agree [N]: (float)(Z_A / Z), the mass the model puts on the spans the annotator has not ruled out; 1 with no active point.
+ *  - a poisoned row - v < 1, a NaN logit at t < v, a Z that is not a positive finite number, or T > 256 (T is device memory: the host
+ *    cannot refuse it) -: query_point = -1, query_gain = post_entropy = agree = -1.0f, incl / gain columns [0, min(T, ld)) 0.
+ *  - contradictory answers - Z_A is not positive: a negative inside the hull of the positives, every frame negative, or every weight
+ *    of A underflowed -: agree = 0, query_point = -1, query_gain = post_entropy = -1.0f, incl / gain 0.
+ *  - a collapsed posterior (one consistent span; v == 1) is not an error: every gain is 0 and query_point is the first frame.  Callers
+ *    test query_gain > 0.
+ * The sums are taken as segmented prefix / suffix sums of p_s, p_e, p_s log2f p_s and p_e log2f p_e (a negative frame closes a
+ * segment) in float64, each a sum of terms of one sign in a fixed order: no walk over the triangle, no atomics, nothing grid wide.  One
+ * launch over the whole set, one workgroup per sample.  Allocates nothing and does not synchronise: capturable in a hipGraph.
+ * Argument errors (a null pointer other than incl and gain, N < 1, ld outside [2, 1024]) return before any HIP call. */
+int hual_al_query(const hual_al_set* set, const float* s0, const float* e0, float* incl, float* gain, int32_t* query_point,
+                  float* query_gain, float* post_entropy, float* agree, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
