@@ -260,7 +260,7 @@ __device__ __forceinline__ void conv_block_fwd_body(const CbFwdArgs& a, const Ro
         v = relu_nan4(v);
         if (own[rt] && L.y) st4(L.y + (size_t)o * HUAL_D + ecol, v);
         rb[rt] = f4_posbits(v);
-        if (dropping) v = f4_select(nib[rt], make_float4(v.x * dr.scale, v.y * dr.scale, v.z * dr.scale, v.w * dr.scale));
+        if (dropping) v = drop_scale(nib[rt], v, dr.scale);
         v = cb_add(v, xres[rt]);
         X[__mul24(o - xbase, CB_XS) + (ecol >> 2)] = v;
         if (own[rt]) st4(L.xout + (size_t)o * HUAL_D + ecol, v);
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(CB_THREADS) void conv_block_bwd_kernel(CbBwdArgs a,
       const bool ok = i < XR && row >= 0 && row < R;
       float4 v = ok ? dv[u] : f4zero();
       if (i < XR) DX[i * 32 + l32] = v;
-      v = f4_select(ok ? zn[u] : 0u, make_float4(v.x * dscale3, v.y * dscale3, v.z * dscale3, v.w * dscale3));
+      v = drop_scale(ok ? zn[u] : 0u, v, dscale3);
       if (ok && row >= r0 && row < r0 + MT) st4(a.l[3].dz + (size_t)row * HUAL_D + col, v);
       const float inv = cb_store_operand(Ahi, Alo, i, l32, v);
       if (l32 == 0) ainv[i] = ok ? inv : 0.f;

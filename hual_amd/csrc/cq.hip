@@ -81,9 +81,8 @@ __global__ __launch_bounds__(256) void tri_prep_kernel(CqBufs b, CqParams p, Row
     if (dr.enabled) {      // 16-bit decisions, one call per lane for both roles of the row (tilecore.h)
       uint32_t n1, n2;
       drop_nib2_sites_r(dr, site1, (uint32_t)row, site2, (uint32_t)row, (uint32_t)l32, n1, n2);
-      const float4 xs = make_float4(x.x * dr.scale, x.y * dr.scale, x.z * dr.scale, x.w * dr.scale);
-      a = f4_select(n1, xs);
-      c = f4_select(n2, xs);
+      a = drop_scale(n1, x, dr.scale);
+      c = drop_scale(n2, x, dr.scale);
     }
     float4 w0 = ld4(p.w0[d1] + col), wm = ld4(p.wm[d1] + col), w1 = ld4(p.w1[d2] + col);
     float s0 = fast_sum32(a.x * w0.x + a.y * w0.y + a.z * w0.z + a.w * w0.w);
@@ -344,7 +343,7 @@ __device__ __forceinline__ void cq_fwd_staged_body(const CqBufs& b, const CqPara
       const bool live = first ? k < c.N1 : k < c.N2;
       const int grow = (first ? c.x1base : c.x2base) + (live ? k : 0);      // unified row (dropout counter, destination)
       float4 x = xrows.v[u];
-      if (dr.enabled) x = f4_select(nib[u], make_float4(x.x * dr.scale, x.y * dr.scale, x.z * dr.scale, x.w * dr.scale));
+      if (dr.enabled) x = drop_scale(nib[u], x, dr.scale);
       const float4 w = first ? w0 : w1;
       const float sv = fast_sum32(x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w);
       const float4 o = first ? make_float4(x.x * wm.x, x.y * wm.y, x.z * wm.z, x.w * wm.w) : x;

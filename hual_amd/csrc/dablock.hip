@@ -266,7 +266,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
     for (int rt = 0; rt < NT; ++rt) {
       const int lr = 16 * rt + j;
       float4 v = addb(SV[rt], 7);
-      if (dr.enabled) v = f4_select(nbd[rt], make_float4(v.x * dr.scale, v.y * dr.scale, v.z * dr.scale, v.w * dr.scale));
+      if (dr.enabled) v = drop_scale(nbd[rt], v, dr.scale);
       v = cb_add(v, xin[rt]);
       SV[rt] = v;
       save(a.res, rt, v);
@@ -293,6 +293,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
       float mean, rstd;
       const float4 xh = ln_row(scratch[lr * 32 + l32], mean, rstd);
       float4 y = cb_fma(xh, g2, b2);
+      // (drop_scale written out: through the helper the six da_post kernels schedule differently, profiles/tform_helpers_isa.txt)
       if (dr.enabled) y = f4_select(nb3[u], make_float4(y.x * dr.scale, y.y * dr.scale, y.z * dr.scale, y.w * dr.scale));
       if (!ok) y = f4zero();
       if (ok) {
@@ -315,7 +316,7 @@ __device__ __forceinline__ void da_post_body(const DaPostArgs& a, const DropCfg&
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) {
       float4 v = addb(T1[rt], 8);
-      if (dr.enabled) v = f4_select(nbe[rt], make_float4(v.x * dr.scale, v.y * dr.scale, v.z * dr.scale, v.w * dr.scale));
+      if (dr.enabled) v = drop_scale(nbe[rt], v, dr.scale);
       v = cb_add(v, SV[rt]);
       save(a.out, rt, v);
       if (TAIL) scratch[(16 * rt + j) * 32 + (ecol >> 2)] = v;      // (slot 0 has been free since the LN2 pass)
@@ -442,7 +443,7 @@ __device__ __forceinline__ bool ln_proj_bwd_body(const LnProjBwdArgs& a, const D
       const bool ok = row < RE;
       float4 v = ok ? nv[u] : f4zero();
       if (has_bits(k)) {      // dropout' with the keep bits the forward left (requested with the rows)
-        if (dr.enabled) v = f4_select((nkb[u] >> (4 * (l32 & 1))) & 15u, make_float4(v.x * dr.scale, v.y * dr.scale, v.z * dr.scale, v.w * dr.scale));
+        if (dr.enabled) v = drop_scale((nkb[u] >> (4 * (l32 & 1))) & 15u, v, dr.scale);
         if (ok && a.a_save[k]) st4_nt(a.a_save[k] + (size_t)row * HUAL_D + col, v);
       }
       const float inv = cb_store_operand(S, S + LB_ROWS * 256, lr, l32, v);
@@ -552,7 +553,7 @@ __device__ __forceinline__ bool ln_proj_bwd_body(const LnProjBwdArgs& a, const D
     const float mean = mu[u], rstd = rsd[u];
     const float4 xh = make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd);
     float4 dy = D0[lr * 32 + l32];
-    if (has_dy1_bits && dr.enabled) dy = f4_select((kb1[u] >> (4 * (l32 & 1))) & 15u, make_float4(dy.x * dr.scale, dy.y * dr.scale, dy.z * dr.scale, dy.w * dr.scale));
+    if (has_dy1_bits && dr.enabled) dy = drop_scale((kb1[u] >> (4 * (l32 & 1))) & 15u, dy, dr.scale);
     sb1 = cb_add(sb1, dy);
     sg1 = cb_fma(dy, xh, sg1);
     float4 gv = cb_mul(dy, g1);
@@ -569,7 +570,7 @@ __device__ __forceinline__ bool ln_proj_bwd_body(const LnProjBwdArgs& a, const D
     if (SIX || a.add1 || pre) dx = make_float4(__fadd_rn(dx.x, a1v[u].x), __fadd_rn(dx.y, a1v[u].y), __fadd_rn(dx.z, a1v[u].z), __fadd_rn(dx.w, a1v[u].w));
     st4(a.dx + off, dx);
     if (a.dz) {
-      if (a.dz_bits && dr.enabled) dx = f4_select((kbz[u] >> (4 * (l32 & 1))) & 15u, make_float4(dx.x * dr.scale, dx.y * dr.scale, dx.z * dr.scale, dx.w * dr.scale));
+      if (a.dz_bits && dr.enabled) dx = drop_scale((kbz[u] >> (4 * (l32 & 1))) & 15u, dx, dr.scale);
       st4(a.dz + off, dx);
       if (MID) zv[u] = dx;
     }

@@ -115,7 +115,7 @@ __device__ __forceinline__ void ln_proj_body(const hual::LnProjArgs& a, const hu
     float4 xr = xv[u];
     if (!PLAIN) {
       float4 t = av[u];
-      const float4 td = f4_select(nbp[u], make_float4(t.x * dr.scale, t.y * dr.scale, t.z * dr.scale, t.w * dr.scale));
+      const float4 td = drop_scale(nbp[u], t, dr.scale);
       t = f4_pick(pre_drop, td, t);
       xr = f4_pick(has_xa, cb_add(t, xr), xr);
       bst4(rs_xo, roff, xr);
@@ -124,7 +124,7 @@ __device__ __forceinline__ void ln_proj_body(const hual::LnProjArgs& a, const hu
     const float4 xh = ln_row(xr, mean, rstd);
     float4 y1 = cb_fma(xh, g1, b1);
     {
-      const float4 yd = f4_select(nb1[u], make_float4(y1.x * dr.scale, y1.y * dr.scale, y1.z * dr.scale, y1.w * dr.scale));
+      const float4 yd = drop_scale(nb1[u], y1, dr.scale);
       y1 = f4_pick(drop1, yd, y1);
     }
     y1 = f4_pick(ok, y1, f4zero());
@@ -197,7 +197,7 @@ __device__ __forceinline__ void ln_proj_body(const hual::LnProjArgs& a, const hu
       float4 v = make_float4(acc[rt].x + bias[p].x, acc[rt].y + bias[p].y, acc[rt].z + bias[p].z, acc[rt].w + bias[p].w);
       const float4 vr = relu_nan4(v);
       v = f4_pick(relu, vr, v);
-      const float4 vd = f4_select(nbo[rt], make_float4(v.x * dr.scale, v.y * dr.scale, v.z * dr.scale, v.w * dr.scale));
+      const float4 vd = drop_scale(nbo[rt], v, dr.scale);
       v = f4_pick(dropo, vd, v);
       const float4 vx = cb_add(v, scratch[lr * 32 + (ecol >> 2)]);
       v = f4_pick(addx, vx, v);

@@ -137,7 +137,7 @@ __device__ __forceinline__ void mproj_body(const MProjArgs& a, const DropCfg& dr
       }
       if ((F & MPF_A2) && st.A2) v = cb_mul(v, n2[u]);
       if (!ok) v = f4zero();
-      if ((F & MPF_DROP) && st.drop_site >= 0 && dr.enabled) v = f4_select(nb[u], make_float4(v.x * dr.scale, v.y * dr.scale, v.z * dr.scale, v.w * dr.scale));
+      if ((F & MPF_DROP) && st.drop_site >= 0 && dr.enabled) v = drop_scale(nb[u], v, dr.scale);
       const float inv = cb_store_operand(S, S + MP_ROWS * 256, lr, l32, v);      // (rows MT .. 16 NT - 1 of a slot: zeros)
       if (l32 == 0) ai[lr] = row < RE ? inv : 0.f;
     }

@@ -123,6 +123,8 @@ __device__ __forceinline__ void bits_store2(uint8_t* plane, int rowA, int rowB, 
 __device__ __forceinline__ float4 f4_select(uint32_t nib, float4 v) {
   return make_float4((nib & 1u) ? v.x : 0.f, (nib & 2u) ? v.y : 0.f, (nib & 4u) ? v.z : 0.f, (nib & 8u) ? v.w : 0.f);
 }
+// dropout of a lane's four columns: keep nibble `nib`, survivors scaled by `scale` = 1 / keep probability (f4scale1, bf16x3.h)
+__device__ __forceinline__ float4 drop_scale(uint32_t nib, float4 v, float scale) { return f4_select(nib, f4scale1(v, scale)); }
 __device__ __forceinline__ uint32_t f4_posbits(float4 v) {
   return (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
 }
