@@ -37,6 +37,12 @@ The question by expected information gain (neither has): update_labels(observe_b
 frame whose answer says most about the span - the argmax of h2(q(t)), q(t) the probability that t lies inside the span under the span
 distribution of the deterministic pass restricted to the spans the earlier answers allow (LabelUpdater.query, one hual_al_query launch
 over the whole set) - instead of the argmax of uncert_frame.  Off by default: every launch, record and result is then what it was.
+
+The pseudo-label by minimum Bayes risk (neither has): update_labels(renew_by='posterior') gives every selected sample, instead of
+renew_label's hand-tuned mix (F_RENEW), the span of maximal expected temporal IoU under that same posterior - restricted to the spans
+the answers allow, this round's included - with that expectation as its confidence (LabelUpdater.mbr_label, one hual_al_mbr_label
+launch over the selected samples; a sample whose answers contradict each other or whose row is poisoned keeps the reference's renew,
+one hual_al_renew launch over just those).  Off by default: every launch, record and result is then what it was.
 """
 import ctypes
 import math
@@ -561,6 +567,16 @@ class LabelUpdater:
         (self.incl, self.gain, self.query_point, self.query_gain, self.post_entropy,
          self.agree) = lib.al_query(self.set, self._s0, self._e0, self.tlen_h, frames=frames)
 
+    def mbr_label(self, sel, old_idx):
+        """the minimum-Bayes-risk pseudo-label of the samples `sel` (sample ids, numpy) under the span posterior given the set's
+        answered active points (hual_al_mbr_label, one launch) on the updater's set and deterministic logits - of the records or of the
+        bank, as query().  old_idx: int [N, 2].  Returns numpy (new_idx i32 [N, 2], conf f32 [N], old_conf f32 [N]): the label, its
+        expected tIoU and the old span's; rows outside `sel`, and rows that give no label, hold -1."""
+        sel_d = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
+        old_d = torch.from_numpy(np.ascontiguousarray(old_idx, dtype=np.int32)).to(self.dev)
+        new_d, conf, old_conf = lib.al_mbr_label(self.set, self._s0, self._e0, self.tlen_h, sel=sel_d, old_idx=old_d)
+        return new_d.cpu().numpy(), conf.cpu().numpy(), old_conf.cpu().numpy()
+
     def renew(self, sel, old_idx, coff):
         """sel: sample ids (numpy); old_idx: int [N,2]; returns new_idx int32 [N,2] (valid for the selected rows)"""
         sel_d = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
@@ -574,6 +590,7 @@ class LabelUpdater:
 
 RANK_BY = ('uncert_video', 'span_risk')
 OBSERVE_BY = ('uncert_frame', 'info_gain')
+RENEW_BY = ('heuristic', 'posterior')
 
 
 def span_risk(last_prop):
@@ -584,7 +601,7 @@ def span_risk(last_prop):
 
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
-                  rank_by='uncert_video', observe_by='uncert_frame'):
+                  rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic'):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -600,11 +617,17 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     about the frame of most expected information gain under its span posterior given the answers of the earlier rounds
     (LabelUpdater.query, one more launch; where that gain is not positive - a collapsed posterior, contradictory answers, a poisoned
     row - the reference's frame); ranking, selection, append_AP, renew and the time conversion are unchanged.
+    renew_by: 'heuristic' (the reference's renew_label) or 'posterior' - every selected sample's new span is then the span of maximal
+    expected temporal IoU under its span posterior given its answers, this round's included (LabelUpdater.mbr_label, one launch
+    instead of the renew; the selected samples that come back without a label - contradictory answers, a poisoned row - take the
+    reference's renew, one launch over just those); ranking, selection, append_AP and the time conversion are unchanged.
     """
     if rank_by not in RANK_BY:
         raise ValueError("rank_by: 'uncert_video' or 'span_risk'")
     if observe_by not in OBSERVE_BY:
         raise ValueError("observe_by: 'uncert_frame' or 'info_gain'")
+    if renew_by not in RENEW_BY:
+        raise ValueError("renew_by: 'heuristic' or 'posterior'")
     risk = span_risk(last_prop) if rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -638,7 +661,15 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
         aps[i].append((p, bool(is_pos)))
     up.set_active_points(aps)
-    new_idx = up.renew(sel, old_idx, coff)
+    if renew_by == 'posterior':
+        new_idx, label_conf, old_conf = up.mbr_label(sel, old_idx)
+        by_posterior = np.zeros(N, dtype=bool)
+        by_posterior[sel] = new_idx[sel, 0] >= 0
+        rest = sel[~by_posterior[sel]]                           # no label: the reference's renew for just those
+        if len(rest):
+            new_idx[rest] = up.renew(rest, old_idx, coff)[rest]
+    else:
+        new_idx = up.renew(sel, old_idx, coff)
     for i in sel:
         dur, vl = data_old[i][1], int(vlen[i])
         data_old[i][2] = [round(int(t) / (vl - 1) * dur, 2) for t in new_idx[i]]          # index_to_time, update_label.py:50-57
@@ -651,6 +682,8 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         if observe_by == 'info_gain':
             dbg.update(query_point=up.query_point.cpu().numpy(), query_gain=up.query_gain.cpu().numpy(),
                        post_entropy=up.post_entropy.cpu().numpy(), agree=up.agree.cpu().numpy(), observe_used=ask)
+        if renew_by == 'posterior':
+            dbg.update(label_conf=label_conf, old_conf=old_conf, renewed_by_posterior=by_posterior)
         return data_old, dbg
     return data_old
 
@@ -670,7 +703,7 @@ def labels_from_times(data, vlens):
 
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
-              observe_by='uncert_frame'):
+              observe_by='uncert_frame', renew_by='heuristic'):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -684,6 +717,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     update on the device before it is refilled; otherwise last_prop's own 'prop_uncert' or 'prop_logits1/2' do.
     span_conf=True: the round's inference records 'prop_conf' / 'prop_span_entropy' (infer_trainset).
     observe_by: the frame the round's label update asks the annotator about (update_labels).
+    renew_by: how the round's label update derives the new pseudo-labels (update_labels).
     Returns (new train list, new results records - rank 0 only, else None -, metrics dict)."""
     import time
     from . import dist as hdist
@@ -692,7 +726,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     t0 = time.perf_counter()
     prev = bank if bank is not None and bank.K >= 2 else None
     new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
-                             mc_stat=mc_stat, observe_by=observe_by) if rank == 0 else None
+                             mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by) if rank == 0 else None
     new_data = hdist.broadcast_object(new_data)
     torch.cuda.synchronize()
     t1a = time.perf_counter()

@@ -78,7 +78,23 @@ struct AlQueryArgs {
   float *query_gain, *post_entropy, *agree;   // [N]
 };
 
+// hual_al_mbr_label (spanlabel.hip): the span of the consistent set of maximal expected tIoU under the answered-point posterior
+struct AlLabelArgs {
+  int ld, N;                                  // the set (hual_al_set), as in AlScoreArgs
+  const int32_t* vlen;
+  const int32_t* tlen;
+  const int32_t* ap_off;
+  const int32_t* ap_idx;
+  const int8_t* ap_pos;
+  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
+  const int32_t* sel;                         // [nsel] sample ids to label (NULL: all)
+  const int32_t* old_idx;                     // [N, 2] (NULL with old_conf: not scored)
+  int32_t* new_idx;                           // [N, 2] (rows of unselected samples are left untouched, as conf and old_conf)
+  float *conf, *old_conf;                     // [N]
+};
+
 int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s);
+int launch_al_mbr_label(const AlLabelArgs& a, int nsel, hipStream_t s);
 int launch_al_query(const AlQueryArgs& a, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);

@@ -11,6 +11,7 @@
 //   * score mixtures / uncert_frame: float64 sums of float32 terms.
 // Active points arrive as one CSR list per sample (frame index + positive flag), in the order they were annotated.
 #include "al.h"
+#include "alpost.h"
 #include "prof.h"
 #include "spanprob.h"
 
@@ -434,33 +435,14 @@ __global__ __launch_bounds__(SPAN_THREADS) void al_query_kernel(AlQueryArgs a) {
     const int ap0 = a.ap_off[n], napn = a.ap_off[n + 1] - ap0;
     const int32_t* aidx = a.ap_idx + ap0;
     const int8_t* apos = a.ap_pos + ap0;
-    int npos = 0, lo = 0x7fffffff, hi = -1, negL = -1, negR = 0x7fffffff;
-    bool inside = false;                    // a negative inside the positive hull
-    for (int k = 0; k < napn; ++k) {
-      const int f = aidx[k];
-      if (f < 0 || f >= v || !apos[k]) continue;
-      ++npos; lo = min(lo, f); hi = max(hi, f);
-    }
-    if (npos > 0) {
-      for (int k = 0; k < napn; ++k) {
-        const int f = aidx[k];
-        if (f < 0 || f >= v || apos[k]) continue;
-        if (f < lo) negL = max(negL, f);
-        else if (f > hi) negR = min(negR, f);
-        else inside = true;
-      }
-    }
+    const ApHull hull = ap_hull(aidx, apos, napn, v);
+    const int npos = hull.npos, lo = hull.lo, hi = hull.hi, negL = hull.negL, negR = hull.negR;
+    const bool inside = hull.inside;        // a negative inside the positive hull
     // frame c's segment [a, b]: between the nearest negatives around it; closed: c is itself a negative
     const int kind = t >> 8, c = t & 255;
-    int sa = 0, sb = v - 1;
-    bool closed = false;
-    for (int k = 0; k < napn; ++k) {
-      const int f = aidx[k];
-      if (f < 0 || f >= v || apos[k]) continue;
-      if (f < c) sa = max(sa, f + 1);
-      else if (f > c) sb = min(sb, f - 1);
-      else closed = true;
-    }
+    const ApSegment sg = ap_segment(aidx, apos, napn, v, c);
+    const int sa = sg.sa, sb = sg.sb;
+    const bool closed = sg.closed;
     __syncthreads();                        // ls / le are read across threads from here on
     if (c < v) {
       if (kind == 0) {

@@ -160,6 +160,7 @@ def load():
     lib.hual_al_score_info.argtypes = [P(hual_al_set), vp, vp, P(hual_al_bank), P(hual_al_info), i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_al_renew.argtypes = [P(hual_al_set), vp, i32, vp, vp, vp, P(ctypes.c_double), vp, vp]
     lib.hual_al_query.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.hual_al_mbr_label.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_carry.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     _lib = lib
@@ -388,4 +389,47 @@ def al_query(aset, s0, e0, tlen, frames=True, out=None):
             if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
                 raise HualError('al_query: out tensors must be contiguous, on the logits\' device, f32 [N, ld] / [N] (query_point: i32 [N])')
     check(load().hual_al_query(ctypes.byref(aset), ptr(s0), ptr(e0), *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)
+
+
+def al_mbr_label(aset, s0, e0, tlen, sel=None, old_idx=None, out=None):
+    """the pseudo-label by minimum Bayes risk of the selected samples of the hual_al_set `aset`: the span of the consistent set of
+    maximal expected temporal IoU under the span posterior given the answered active points (hual_al_mbr_label), one launch enqueued
+    on the current stream.  s0 / e0: the deterministic logits f32 [N, ld] on the device; tlen: the set's row lengths on the HOST - a row
+    above AL_QUERY_MAX_T frames is refused here, before the launch, as in al_query; sel: device i32 [nsel] sample ids (None: all);
+    old_idx: device i32 [N, 2], the old spans to score beside the label (None: not scored).
+    -> (new_idx i32 [N, 2], conf f32 [N], old_conf f32 [N] or None).  out: such a tuple of contiguous device tensors to write into
+    instead (old_conf None exactly when old_idx is).  Only the rows of selected samples are written: the others keep what they held
+    (-1 in tensors allocated here, the value of a row that gives no label)."""
+    import numpy as np
+    import torch
+    N, ld = int(aset.N), int(aset.ld)
+    tl = np.asarray(tlen)
+    if tl.size != N:
+        raise HualError('al_mbr_label: tlen must hold N = %d row lengths' % N)
+    if int(tl.max()) > AL_QUERY_MAX_T:
+        raise HualError('al_mbr_label: a row of %d frames - the span posterior handles at most %d' % (int(tl.max()), AL_QUERY_MAX_T))
+    for x in (s0, e0):
+        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous() or x.device != s0.device:
+            raise HualError('al_mbr_label: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d] on one device' % (N, ld))
+    dev = s0.device
+    nsel = N
+    if sel is not None:
+        if sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < 1 or not sel.is_contiguous() or sel.device != dev:
+            raise HualError('al_mbr_label: sel must be a contiguous, non-empty int32 [nsel] on the logits\' device')
+        nsel = int(sel.numel())
+    if old_idx is not None and (old_idx.dtype != torch.int32 or tuple(old_idx.shape) != (N, 2) or not old_idx.is_contiguous()
+                                or old_idx.device != dev):
+        raise HualError('al_mbr_label: old_idx must be contiguous int32 [N, 2] on the logits\' device')
+    if out is None:
+        out = (torch.full((N, 2), -1, dtype=torch.int32, device=dev), torch.full((N,), -1.0, device=dev),
+               torch.full((N,), -1.0, device=dev) if old_idx is not None else None)
+    else:
+        if len(out) != 3 or out[0] is None or out[1] is None or (out[2] is None) != (old_idx is None):
+            raise HualError('al_mbr_label: out is (new_idx, conf, old_conf); old_conf is None exactly when old_idx is')
+        for o, shape, dt in zip(out, ((N, 2), (N,), (N,)), (torch.int32, torch.float32, torch.float32)):
+            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
+                raise HualError('al_mbr_label: out tensors must be contiguous, on the logits\' device, i32 [N, 2], f32 [N], f32 [N]')
+    check(load().hual_al_mbr_label(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, ptr(old_idx), ptr(out[0]), ptr(out[1]),
+                                   ptr(out[2]), stream_ptr()))
     return tuple(out)

@@ -590,6 +590,34 @@ int hual_al_query(const hual_al_set* set, const float* s0, const float* e0, floa
                   float* query_gain, float* post_entropy, float* agree, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The pseudo-label by minimum Bayes risk under the same posterior (HUAL_ABI_VERSION unchanged: one new symbol, nothing else moved).
+ * Beside hual_al_renew, the reference's hand-tuned mix: the span of the consistent set that maximises the expected temporal IoU under
+ * the span posterior given the answers - the decision of least expected loss in the evaluation's own metric - and that expectation as
+ * its confidence.  Per selected sample n (sel: device i32 [nsel] sample ids in any order, each at most once, an id outside [0, N)
+ * writes nothing; sel NULL: all N samples), with T, v, p_s, p_e, w, the ignored active points, A and Z_A exactly as hual_al_query
+ * above defines them:
+ *  - the expected tIoU of a span (a, e): R(a, e) = (1 / Z_A) * sum over (i, j) in A of w(i,j) * inter / union, inter = max(0, min(e, j)
+ *    + 1 - max(a, i)), union = (e - a + 1) + (j - i + 1) - inter: the frame-count IoU of hual_span_expected_iou.  Float64 accumulation,
+ *    clamped to [0, 1], stored as float32.
+ *  - new_idx i32 [N, 2]: the member (a, e) of A of maximal R in the kernel's own float64 arithmetic; among equal values the first in
+ *    row-major order (smallest a, then smallest e).  conf f32 [N]: that R.  Only the rows / entries of selected samples are written.
+ *  - old_idx i32 [N, 2] and old_conf f32 [N] (both or neither; both NULL: not computed): old_conf = R of the sample's old span
+ *    (old_idx[n][0], old_idx[n][1]), whether or not it lies in A; -1.0f where it is not a span of the clip (a < 0, a > e or e >= v).
+ *  - a poisoned row (v < 1, a NaN logit at t < v, a Z that is not a positive finite number, or T > 256) and a contradictory row (Z_A
+ *    not positive) give no label: new_idx = (-1, -1), conf = old_conf = -1.0f.  Callers test new_idx[n][0] >= 0.
+ *  - a collapsed posterior (one consistent span; v == 1) is not an error: the label is that span and conf is 1.
+ * No pair of spans is enumerated: A is a union of regions {sa <= i <= ihi, jlo <= j <= sb, i <= j} (a gap between negatives, or
+ * (negL, lo] x [hi, negR) around the positive hull), a candidate overlaps only the spans of its own region, and within it Z_A R(a, e)
+ * is the sum of four products of a prefix or suffix sum over i with G_e[m] = sum_{j = max(m, jlo) .. e} p_e[j] (j - m + 1) or
+ * H_e[l] = sum_{j = e + 1 .. sb} p_e[j] / (j - l + 1) - sums of terms of one sign in float64 in a fixed order, no difference of
+ * prefix sums, at most O(v^3) additions per clip, no atomics, nothing grid wide.  One launch, one workgroup per selected sample.
+ * Allocates nothing and does not synchronise: capturable in a hipGraph.
+ * Argument errors (a null pointer other than sel, old_idx and old_conf; exactly one of old_idx and old_conf null; nsel < 1 - also
+ * where sel is NULL and nsel is otherwise not read -; N < 1; ld outside [2, 1024]) return HUAL_ERR_INVALID before any HIP call. */
+int hual_al_mbr_label(const hual_al_set* set, const float* s0, const float* e0, const int32_t* sel, int nsel, const int32_t* old_idx,
+                      int32_t* new_idx, float* conf, float* old_conf, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
