@@ -43,6 +43,12 @@ renew_label's hand-tuned mix (F_RENEW), the span of maximal expected temporal Io
 the answers allow, this round's included - with that expectation as its confidence (LabelUpdater.mbr_label, one hual_al_mbr_label
 launch over the selected samples; a sample whose answers contradict each other or whose row is poisoned keeps the reference's renew,
 one hual_al_renew launch over just those).  Off by default: every launch, record and result is then what it was.
+
+Acquisition by expected label gain (neither has): update_labels(acquire_by='label_gain') chooses both the samples that are asked and
+the frame each is asked about by the temporal IoU the minimum-Bayes-risk label is expected to gain from the answer - one-step lookahead
+under that same posterior, in the evaluation's own metric (LabelUpdater.label_gain, one hual_al_label_gain launch over the whole set):
+the half of the set with the largest gain is selected, each sample asked at its frame of maximal gain (the reference's frame where no
+answer can move the label).  Off by default: every launch, record and result is then what it was.
 """
 import ctypes
 import math
@@ -567,6 +573,15 @@ class LabelUpdater:
         (self.incl, self.gain, self.query_point, self.query_gain, self.post_entropy,
          self.agree) = lib.al_query(self.set, self._s0, self._e0, self.tlen_h, frames=frames)
 
+    def label_gain(self, frames=True, cand=None):
+        """per frame, the tIoU the minimum-Bayes-risk label is expected to gain from the frame's answer under the span posterior given
+        the set's answered active points (hual_al_label_gain, one launch over the whole set) on the updater's set and deterministic
+        logits - of the records or of the bank, as query().  cand: device i32 [N, M], the only frames to evaluate (None: every frame).
+        Leaves gain (f32 [N, ld]; None with frames=False; in place of the row of bits query() leaves under that name), ask_point
+        (i32 [N]), ask_gain and label_value (f32 [N]) as device tensors."""
+        (self.gain, self.ask_point, self.ask_gain,
+         self.label_value) = lib.al_label_gain(self.set, self._s0, self._e0, self.tlen_h, cand=cand, frames=frames)
+
     def mbr_label(self, sel, old_idx):
         """the minimum-Bayes-risk pseudo-label of the samples `sel` (sample ids, numpy) under the span posterior given the set's
         answered active points (hual_al_mbr_label, one launch) on the updater's set and deterministic logits - of the records or of the
@@ -591,6 +606,7 @@ class LabelUpdater:
 RANK_BY = ('uncert_video', 'span_risk')
 OBSERVE_BY = ('uncert_frame', 'info_gain')
 RENEW_BY = ('heuristic', 'posterior')
+ACQUIRE_BY = (None, 'label_gain')
 
 
 def span_risk(last_prop):
@@ -601,7 +617,7 @@ def span_risk(last_prop):
 
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
-                  rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic'):
+                  rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -621,6 +637,11 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     expected temporal IoU under its span posterior given its answers, this round's included (LabelUpdater.mbr_label, one launch
     instead of the renew; the selected samples that come back without a label - contradictory answers, a poisoned row - take the
     reference's renew, one launch over just those); ranking, selection, append_AP and the time conversion are unchanged.
+    acquire_by: None, or 'label_gain' - samples and frames are then both chosen by the tIoU the minimum-Bayes-risk label is expected to
+    gain from the answer under the span posterior given the answers of the earlier rounds (LabelUpdater.label_gain, one more launch):
+    the samples are ranked by their largest gain, descending, the same stable argsort, the same half selected, and each is asked at its
+    frame of maximal gain (where that gain is not positive, the reference's frame).  It replaces the ranking and the question, so
+    rank_by and observe_by must be at their defaults; append_AP, renew (either renew_by) and the time conversion are unchanged.
     """
     if rank_by not in RANK_BY:
         raise ValueError("rank_by: 'uncert_video' or 'span_risk'")
@@ -628,6 +649,11 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         raise ValueError("observe_by: 'uncert_frame' or 'info_gain'")
     if renew_by not in RENEW_BY:
         raise ValueError("renew_by: 'heuristic' or 'posterior'")
+    if acquire_by not in ACQUIRE_BY:
+        raise ValueError("acquire_by: None or 'label_gain'")
+    if acquire_by is not None and (rank_by != RANK_BY[0] or observe_by != OBSERVE_BY[0]):
+        raise ValueError("acquire_by='%s' chooses the samples and the frames itself: leave rank_by and observe_by at their defaults"
+                         % acquire_by)
     risk = span_risk(last_prop) if rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -650,6 +676,11 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         up.query(frames=return_debug)                            # (before set_active_points: on the answers of the earlier rounds)
         ask = np.where(up.query_gain.cpu().numpy() > 0, up.query_point.cpu().numpy(), observe)
     order = np.argsort(uv if risk is None else risk, kind='stable')      # sorted(key=uncert_video), ties in sample order
+    if acquire_by == 'label_gain':
+        up.label_gain(frames=return_debug)                       # (before set_active_points: on the answers of the earlier rounds)
+        ask_gain = up.ask_gain.cpu().numpy()
+        ask = np.where(ask_gain > 0, up.ask_point.cpu().numpy(), observe)
+        order = np.argsort(-ask_gain, kind='stable')             # largest gain first, ties in sample order; rows at 0 and -1 last
     sel = order[:math.ceil(N / 2)]
     vlen = up.vlen_h
     gt_idx = np.array([[_round_half_even_index(t, data_gt[i][1], int(vlen[i])) for t in data_gt[i][2]] for i in range(N)])
@@ -682,6 +713,8 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         if observe_by == 'info_gain':
             dbg.update(query_point=up.query_point.cpu().numpy(), query_gain=up.query_gain.cpu().numpy(),
                        post_entropy=up.post_entropy.cpu().numpy(), agree=up.agree.cpu().numpy(), observe_used=ask)
+        if acquire_by == 'label_gain':
+            dbg.update(ask_point=up.ask_point.cpu().numpy(), ask_gain=ask_gain, label_value=up.label_value.cpu().numpy(), observe_used=ask)
         if renew_by == 'posterior':
             dbg.update(label_conf=label_conf, old_conf=old_conf, renewed_by_posterior=by_posterior)
         return data_old, dbg
@@ -703,7 +736,7 @@ def labels_from_times(data, vlens):
 
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
-              observe_by='uncert_frame', renew_by='heuristic'):
+              observe_by='uncert_frame', renew_by='heuristic', acquire_by=None):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -718,6 +751,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     span_conf=True: the round's inference records 'prop_conf' / 'prop_span_entropy' (infer_trainset).
     observe_by: the frame the round's label update asks the annotator about (update_labels).
     renew_by: how the round's label update derives the new pseudo-labels (update_labels).
+    acquire_by: how the round's label update chooses the samples and frames it asks about (update_labels).
     Returns (new train list, new results records - rank 0 only, else None -, metrics dict)."""
     import time
     from . import dist as hdist
@@ -726,7 +760,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     t0 = time.perf_counter()
     prev = bank if bank is not None and bank.K >= 2 else None
     new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
-                             mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by) if rank == 0 else None
+                             mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by) if rank == 0 else None
     new_data = hdist.broadcast_object(new_data)
     torch.cuda.synchronize()
     t1a = time.perf_counter()

@@ -93,7 +93,25 @@ struct AlLabelArgs {
   float *conf, *old_conf;                     // [N]
 };
 
+// hual_al_label_gain (spangain.hip): per frame, the tIoU the label of hual_al_mbr_label is expected to gain from the frame's answer
+struct AlGainArgs {
+  int ld, N;                                  // the set (hual_al_set), as in AlScoreArgs
+  const int32_t* vlen;
+  const int32_t* tlen;
+  const int32_t* ap_off;
+  const int32_t* ap_idx;
+  const int8_t* ap_pos;
+  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
+  const int32_t* sel;                         // [nsel] sample ids to evaluate (NULL: all)
+  const int32_t* cand;                        // [N, M] the frames to evaluate, entries outside [0, v) skipped (NULL: every frame)
+  int M;
+  float* gain;                                // [N, ld] columns [0, tlen[n]) (NULL: not written)
+  int32_t* ask_point;                         // [N] first evaluated frame of maximal gain (rows of unselected samples are left untouched)
+  float *ask_gain, *value;                    // [N] that gain | V0, the conf of hual_al_mbr_label on the same set
+};
+
 int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s);
+int launch_al_label_gain(const AlGainArgs& a, int nsel, hipStream_t s);
 int launch_al_mbr_label(const AlLabelArgs& a, int nsel, hipStream_t s);
 int launch_al_query(const AlQueryArgs& a, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);

@@ -1,7 +1,8 @@
 // The answered active points of one sample as the span-posterior kernels read them (hual_al_query in al.hip, hual_al_mbr_label in
 // spanlabel.hip; the contract is in include/hual_seqpan.h): points with a frame index outside [0, v) are ignored, the positives are
 // reduced to their hull, the negatives to the nearest one on either side of it or - without a positive - to the gaps between them.
-// One definition, so both launches see the same consistent set A.
+// One definition, so every launch sees the same consistent set A.  hual_al_label_gain (spangain.hip) asks what A would be after one more
+// answer: ap_hull and ap_segment take that hypothetical point (hf, hpos) behind the list; hf outside [0, v) - the default - is none.
 #pragma once
 #include "common.h"
 
@@ -12,18 +13,18 @@ struct ApHull {
   bool inside;
 };
 
-__device__ __forceinline__ ApHull ap_hull(const int32_t* aidx, const int8_t* apos, int napn, int v) {
+__device__ __forceinline__ ApHull ap_hull(const int32_t* aidx, const int8_t* apos, int napn, int v, int hf = -1, int hpos = 0) {
   ApHull h;
   h.npos = 0; h.lo = 0x7fffffff; h.hi = -1; h.negL = -1; h.negR = 0x7fffffff; h.inside = false;
-  for (int k = 0; k < napn; ++k) {
-    const int f = aidx[k];
-    if (f < 0 || f >= v || !apos[k]) continue;
+  for (int k = 0; k <= napn; ++k) {         // (k == napn: the hypothetical point)
+    const int f = k < napn ? aidx[k] : hf;
+    if (f < 0 || f >= v || !(k < napn ? apos[k] : hpos)) continue;
     ++h.npos; h.lo = min(h.lo, f); h.hi = max(h.hi, f);
   }
   if (h.npos > 0) {
-    for (int k = 0; k < napn; ++k) {
-      const int f = aidx[k];
-      if (f < 0 || f >= v || apos[k]) continue;
+    for (int k = 0; k <= napn; ++k) {
+      const int f = k < napn ? aidx[k] : hf;
+      if (f < 0 || f >= v || (k < napn ? apos[k] : hpos)) continue;
       if (f < h.lo) h.negL = max(h.negL, f);
       else if (f > h.hi) h.negR = min(h.negR, f);
       else h.inside = true;
@@ -38,12 +39,13 @@ struct ApSegment {
   bool closed;
 };
 
-__device__ __forceinline__ ApSegment ap_segment(const int32_t* aidx, const int8_t* apos, int napn, int v, int c) {
+__device__ __forceinline__ ApSegment ap_segment(const int32_t* aidx, const int8_t* apos, int napn, int v, int c, int hf = -1,
+                                                int hpos = 0) {
   ApSegment s;
   s.sa = 0; s.sb = v - 1; s.closed = false;
-  for (int k = 0; k < napn; ++k) {
-    const int f = aidx[k];
-    if (f < 0 || f >= v || apos[k]) continue;
+  for (int k = 0; k <= napn; ++k) {         // (k == napn: the hypothetical point)
+    const int f = k < napn ? aidx[k] : hf;
+    if (f < 0 || f >= v || (k < napn ? apos[k] : hpos)) continue;
     if (f < c) s.sa = max(s.sa, f + 1);
     else if (f > c) s.sb = min(s.sb, f - 1);
     else s.closed = true;

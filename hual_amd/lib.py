@@ -161,6 +161,7 @@ def load():
     lib.hual_al_renew.argtypes = [P(hual_al_set), vp, i32, vp, vp, vp, P(ctypes.c_double), vp, vp]
     lib.hual_al_query.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_al_mbr_label.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.hual_al_label_gain.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_carry.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     _lib = lib
@@ -432,4 +433,56 @@ def al_mbr_label(aset, s0, e0, tlen, sel=None, old_idx=None, out=None):
                 raise HualError('al_mbr_label: out tensors must be contiguous, on the logits\' device, i32 [N, 2], f32 [N], f32 [N]')
     check(load().hual_al_mbr_label(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, ptr(old_idx), ptr(out[0]), ptr(out[1]),
                                    ptr(out[2]), stream_ptr()))
+    return tuple(out)
+
+
+AL_GAIN_MAX_CAND = 256      # candidate frames per sample of hual_al_label_gain
+
+
+def al_label_gain(aset, s0, e0, tlen, sel=None, cand=None, frames=True, out=None):
+    """per frame, the temporal IoU the minimum-Bayes-risk label of the selected samples of the hual_al_set `aset` is expected to gain
+    from the annotator's answer at that frame, under the span posterior given the answered active points (hual_al_label_gain), one
+    launch enqueued on the current stream.  s0 / e0: the deterministic logits f32 [N, ld] on the device; tlen: the set's row lengths on
+    the HOST - a row above AL_QUERY_MAX_T frames is refused here, before the launch, as in al_mbr_label; sel: device i32 [nsel] sample
+    ids (None: all); cand: device i32 [N, M], 1 <= M <= 256, the frames to evaluate in that order, entries outside the clip skipped
+    (None: every frame of the clip).
+    -> (gain f32 [N, ld] or None with frames=False, ask_point i32 [N], ask_gain f32 [N], value f32 [N]): the gain per frame, the first
+    evaluated frame of maximal gain, that gain, and the expected tIoU of today's label (al_mbr_label's conf).  out: such a tuple of
+    contiguous device tensors to write into instead (gain may be None).  Only the rows of selected samples are written, and of gain only
+    the columns below a row's tlen: the rest keeps what it held (gain 0, ask_point -1, ask_gain and value -1 in tensors allocated here -
+    the values of a row that has no answer to give)."""
+    import numpy as np
+    import torch
+    N, ld = int(aset.N), int(aset.ld)
+    tl = np.asarray(tlen)
+    if tl.size != N:
+        raise HualError('al_label_gain: tlen must hold N = %d row lengths' % N)
+    if int(tl.max()) > AL_QUERY_MAX_T:
+        raise HualError('al_label_gain: a row of %d frames - the span posterior handles at most %d' % (int(tl.max()), AL_QUERY_MAX_T))
+    for x in (s0, e0):
+        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous() or x.device != s0.device:
+            raise HualError('al_label_gain: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d] on one device' % (N, ld))
+    dev = s0.device
+    nsel = N
+    if sel is not None:
+        if sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < 1 or not sel.is_contiguous() or sel.device != dev:
+            raise HualError('al_label_gain: sel must be a contiguous, non-empty int32 [nsel] on the logits\' device')
+        nsel = int(sel.numel())
+    M = 0
+    if cand is not None:
+        if (cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != N or not 1 <= cand.shape[1] <= AL_GAIN_MAX_CAND
+                or not cand.is_contiguous() or cand.device != dev):
+            raise HualError('al_label_gain: cand must be contiguous int32 [N, M], 1 <= M <= %d, on the logits\' device' % AL_GAIN_MAX_CAND)
+        M = int(cand.shape[1])
+    if out is None:
+        out = (torch.zeros(N, ld, device=dev) if frames else None, torch.full((N,), -1, dtype=torch.int32, device=dev),
+               torch.full((N,), -1.0, device=dev), torch.full((N,), -1.0, device=dev))
+    else:
+        if len(out) != 4 or any(o is None for o in out[1:]):
+            raise HualError('al_label_gain: out is (gain, ask_point, ask_gain, value); only gain may be None')
+        for o, shape, dt in zip(out, ((N, ld), (N,), (N,), (N,)), (torch.float32, torch.int32, torch.float32, torch.float32)):
+            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
+                raise HualError('al_label_gain: out tensors must be contiguous, on the logits\' device, f32 [N, ld], i32 [N], f32 [N], f32 [N]')
+    check(load().hual_al_label_gain(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, ptr(cand), M, *[ptr(o) for o in out],
+                                    stream_ptr()))
     return tuple(out)

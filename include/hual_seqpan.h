@@ -618,6 +618,41 @@ int hual_al_mbr_label(const hual_al_set* set, const float* s0, const float* e0, 
                       int32_t* new_idx, float* conf, float* old_conf, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Where to ask, by the expected gain of the pseudo-label's tIoU under the same posterior (HUAL_ABI_VERSION unchanged: one new symbol,
+ * nothing else moved).  hual_al_query chooses the question in bits, hual_al_mbr_label the label in tIoU; this is the one-step lookahead
+ * that joins them: the expected value of the answer at frame t in the metric itself - how much the expected tIoU of the label that
+ * hual_al_mbr_label would produce after the answer exceeds that of today's label.  A frame can carry a full bit and leave the best
+ * label where it was.  Per selected sample n (sel / nsel as in hual_al_mbr_label), with T, v, p_s, p_e, w, the ignored active points,
+ * A, Z_A and the poisoned / contradictory / collapsed row rules exactly those of hual_al_query and hual_al_mbr_label, and a frame t
+ * in [0, v):
+ *  - A_t+ = the spans of A with i <= t <= j (the annotator says "inside"), A_t- = the rest of A; Z_t+ and Z_t- their masses,
+ *    Z_t+ + Z_t- = Z_A.
+ *  - M_b(t), b in {+, -} = the max over the members c of A_t^b of the sum over (i, j) in A_t^b of w(i,j) * IoU(c, (i,j)), the frame-count
+ *    IoU of hual_al_mbr_label; 0 where Z_t^b is not positive.  The un-normalised value of the label after that answer.
+ *  - V0 = the max over c in A of R(c): the conf of hual_al_mbr_label on the same set.
+ *  - gain(t) = (M_+(t) + M_-(t)) / Z_A - V0, float64, clamped to [0, 1], stored as float32.  (The clamp at 0: the label is restricted
+ *    to the consistent set, so non-negativity is not a theorem.)  A frame whose answer the posterior already determines - Z_t+ or Z_t-
+ *    not positive - has gain exactly 0.0f, with no arithmetic.
+ *  - cand i32 [N, M], 1 <= M <= 256, or NULL = every frame of the clip (M is then not read).  With cand only the frames cand[n][0..M)
+ *    are evaluated, in that order; entries outside [0, v) (-1, say) are skipped.
+ *  - gain f32 [N, ld] (may be NULL): columns [0, T) are written - the gain at the evaluated frames, 0 elsewhere -, columns [T, ld) are
+ *    not touched.
+ *  - ask_point i32 [N]: the first evaluated frame of maximal gain in the kernel's own float64 arithmetic; ask_gain f32 [N]: that gain.
+ *    value f32 [N]: V0.  Only the rows / entries of selected samples are written.
+ *  - a poisoned or contradictory row: ask_point = -1, ask_gain = value = -1.0f, gain columns [0, min(T, ld)) 0.
+ *  - a collapsed posterior, or a candidate list with no frame inside the clip: every gain is 0 and ask_gain = 0; ask_point is the first
+ *    evaluated frame, -1 if there was none.  Callers test ask_gain > 0.
+ * Each branch is maximised as hual_al_mbr_label maximises A, over its regions: "inside" always leaves one, (negL', lo'] x [hi', negR');
+ * "outside" beside a positive hull moves negL or negR; without a positive it splits the gap that holds t, and the other gaps keep
+ * maxima computed once.  Both branches divide by the parent's Z_A, so a branch's best is M_b / Z_A.  Up to 2 v maximisations per clip,
+ * each at most cubic in its region: float64 sums of terms of one sign in a fixed order, no atomics, nothing grid wide.  One launch, one
+ * workgroup per selected sample.  Allocates nothing and does not synchronise: capturable in a hipGraph.
+ * Argument errors (a null pointer other than sel, cand and gain; nsel < 1; N < 1; ld outside [2, 1024]; cand given with M outside
+ * [1, 256]) return HUAL_ERR_INVALID before any HIP call. */
+int hual_al_label_gain(const hual_al_set* set, const float* s0, const float* e0, const int32_t* sel, int nsel, const int32_t* cand,
+                       int M, float* gain, int32_t* ask_point, float* ask_gain, float* value, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
