@@ -49,6 +49,12 @@ the frame each is asked about by the temporal IoU the minimum-Bayes-risk label i
 under that same posterior, in the evaluation's own metric (LabelUpdater.label_gain, one hual_al_label_gain launch over the whole set):
 the half of the set with the largest gain is selected, each sample asked at its frame of maximal gain (the reference's frame where no
 answer can move the label).  Off by default: every launch, record and result is then what it was.
+
+Training on the posterior (neither has): run_round(soft_labels=lam) trains the round's epochs not on the three-frame kernel around the
+hard pseudo-label alone but, for every sample with an answer, on its blend (weight lam) with the start and end marginals of that same
+posterior, this round's answers included (LabelUpdater.span_marginals, one hual_al_span_marginals launch over the whole set;
+update_labels(soft_out=) hands them out; DeviceDataset.set_soft_labels feeds them to the assembly launch).  Off by default: every
+launch, record and result is then what it was.
 """
 import ctypes
 import math
@@ -582,6 +588,12 @@ class LabelUpdater:
         (self.gain, self.ask_point, self.ask_gain,
          self.label_value) = lib.al_label_gain(self.set, self._s0, self._e0, self.tlen_h, cand=cand, frames=frames)
 
+    def span_marginals(self):
+        """the start and end marginals of the span posterior given the set's answered active points (hual_al_span_marginals, one launch
+        over the whole set) on the updater's set and deterministic logits - of the records or of the bank, as query().  Leaves y_start,
+        y_end (f32 [N, ld]) and marg_status (i32 [N]; 1 = live) as device tensors."""
+        self.y_start, self.y_end, self.marg_status = lib.al_span_marginals(self.set, self._s0, self._e0, self.tlen_h)
+
     def mbr_label(self, sel, old_idx):
         """the minimum-Bayes-risk pseudo-label of the samples `sel` (sample ids, numpy) under the span posterior given the set's
         answered active points (hual_al_mbr_label, one launch) on the updater's set and deterministic logits - of the records or of the
@@ -617,7 +629,7 @@ def span_risk(last_prop):
 
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
-                  rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None):
+                  rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -642,7 +654,14 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     the samples are ranked by their largest gain, descending, the same stable argsort, the same half selected, and each is asked at its
     frame of maximal gain (where that gain is not positive, the reference's frame).  It replaces the ranking and the question, so
     rank_by and observe_by must be at their defaults; append_AP, renew (either renew_by) and the time conversion are unchanged.
+    soft_out: None, or a dict that receives the soft labels of the WHOLE set under the span posterior given every answer so far, this
+    round's included (LabelUpdater.span_marginals, one more launch, where the renew runs; the answers earlier rounds left on samples
+    that are not selected count too): 'y1', 'y2' (device f32 [N, ld], the start / end marginals), 'live' (numpy bool [N]: the row gave
+    marginals) and 'answered' (numpy bool [N]: at least one active point with a frame inside [0, v_len)).  Nothing else about the call
+    changes, with any combination of the other switches.
     """
+    if soft_out is not None and not isinstance(soft_out, dict):
+        raise ValueError('soft_out: None or a dict to receive y1, y2, live and answered')
     if rank_by not in RANK_BY:
         raise ValueError("rank_by: 'uncert_video' or 'span_risk'")
     if observe_by not in OBSERVE_BY:
@@ -692,6 +711,10 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
         aps[i].append((p, bool(is_pos)))
     up.set_active_points(aps)
+    if soft_out is not None:
+        up.span_marginals()
+        soft_out.update(y1=up.y_start, y2=up.y_end, live=up.marg_status.cpu().numpy() == 1,
+                        answered=np.array([any(0 <= f < int(vlen[i]) for f, _ in aps[i]) for i in range(N)], dtype=bool))
     if renew_by == 'posterior':
         new_idx, label_conf, old_conf = up.mbr_label(sel, old_idx)
         by_posterior = np.zeros(N, dtype=bool)
@@ -736,7 +759,7 @@ def labels_from_times(data, vlens):
 
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
-              observe_by='uncert_frame', renew_by='heuristic', acquire_by=None):
+              observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -752,16 +775,37 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     observe_by: the frame the round's label update asks the annotator about (update_labels).
     renew_by: how the round's label update derives the new pseudo-labels (update_labels).
     acquire_by: how the round's label update chooses the samples and frames it asks about (update_labels).
+    soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
+    blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
+    DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
+    model's own prediction.  metrics['soft_rows'] is the number of weighted samples.  Single process only (the marginals live on
+    rank 0), and the records' v_len must be the dataset's clip lengths.
     Returns (new train list, new results records - rank 0 only, else None -, metrics dict)."""
     import time
     from . import dist as hdist
     from .train import Trainer
     world, rank = hdist.world_size(), hdist.rank()
+    soft = None
+    if soft_labels is not None:                                  # (raises before anything is touched)
+        lam = float(soft_labels)
+        if not 0.0 < lam <= 1.0:
+            raise ValueError('soft_labels: None or a weight in (0, 1]')
+        if world > 1:
+            raise ValueError('soft_labels is single-process: the marginals live on rank 0 and are not broadcast')
+        if [int(p['v_len']) for p in last_prop] != [int(n) for n in dataset.vlen_h]:
+            raise ValueError("soft_labels: a record's v_len differs from the dataset's clip length")
+        soft = {}
     t0 = time.perf_counter()
     prev = bank if bank is not None and bank.K >= 2 else None
     new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
-                             mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by) if rank == 0 else None
+                             mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
+                             soft_out=soft) if rank == 0 else None
     new_data = hdist.broadcast_object(new_data)
+    if soft is not None:
+        weighted = soft['live'] & soft['answered']
+        dataset.set_soft_labels(soft['y1'], soft['y2'], np.where(weighted, np.float32(lam), np.float32(0.0)))
+    else:
+        dataset.clear_soft_labels()                              # (banks an earlier round enabled describe the labels before this update)
     torch.cuda.synchronize()
     t1a = time.perf_counter()
     # the pseudo-label frame indices of the new train list: the reference regenerates its dataset cache for this (dataset_gen,
@@ -795,6 +839,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
              r1i3=r3, r1i5=r5, r1i7=r7, miou=mi)
     if mc_samples is not None:
         m['mc_bank'] = bank
+    if soft is not None:
+        m['soft_rows'] = int(weighted.sum())
     if log and rank == 0:
         log('round %d: update_label %.3f s | train %d steps %.3f s (%.0f clips/s) | infer_trainset %.3f s | pseudo-label '
             'R1@0.5 %.2f mIoU %.2f' % (I, m['update_s'], steps, m['train_s'], m['clips_per_s'], m['infer_s'], r5, mi))

@@ -110,7 +110,21 @@ struct AlGainArgs {
   float *ask_gain, *value;                    // [N] that gain | V0, the conf of hual_al_mbr_label on the same set
 };
 
+// hual_al_span_marginals (spanmarg.hip): the start / end marginals of the span posterior given the answered active points
+struct AlMargArgs {
+  int ld, N;                                  // the set (hual_al_set), as in AlScoreArgs
+  const int32_t* vlen;
+  const int32_t* tlen;
+  const int32_t* ap_off;
+  const int32_t* ap_idx;
+  const int8_t* ap_pos;
+  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
+  float *y_start, *y_end;                     // [N, ld] columns [0, tlen[n])
+  int32_t* status;                            // [N] 1 = live, 0 = poisoned or contradictory
+};
+
 int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s);
+int launch_al_span_marginals(const AlMargArgs& a, hipStream_t s);
 int launch_al_label_gain(const AlGainArgs& a, int nsel, hipStream_t s);
 int launch_al_mbr_label(const AlLabelArgs& a, int nsel, hipStream_t s);
 int launch_al_query(const AlQueryArgs& a, hipStream_t s);

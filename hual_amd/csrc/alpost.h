@@ -1,5 +1,5 @@
 // The answered active points of one sample as the span-posterior kernels read them (hual_al_query in al.hip, hual_al_mbr_label in
-// spanlabel.hip; the contract is in include/hual_seqpan.h): points with a frame index outside [0, v) are ignored, the positives are
+// spanlabel.hip, hual_al_span_marginals in spanmarg.hip; the contract is in include/hual_seqpan.h): points with a frame index outside [0, v) are ignored, the positives are
 // reduced to their hull, the negatives to the nearest one on either side of it or - without a positive - to the gaps between them.
 // One definition, so every launch sees the same consistent set A.  hual_al_label_gain (spangain.hip) asks what A would be after one more
 // answer: ap_hull and ap_segment take that hypothetical point (hf, hpos) behind the list; hf outside [0, v) - the default - is none.

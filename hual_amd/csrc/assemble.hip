@@ -59,6 +59,9 @@ __device__ __forceinline__ void assemble_side_body(const AssembleArgs& a, int b)
   const int et_l = max(0, et - ext);
   const int et_r = min(et + ext, n - 1);
   if (st_r >= et_l) st_r = max(st, et_l - 1);
+  // the sample's soft-label weight: 0 (or no banks) leaves the reference's labels untouched, and its bank rows unread
+  const float lam = a.soft_w ? a.soft_w[s] : 0.f;
+  const int nsoft = lam == 0.f ? 0 : min(n, a.soft_ld);
   for (int t = threadIdx.x; t < a.T; t += blockDim.x) {
     const float base = t < n ? 1e-10f : 0.0f;
     float ys = base, ye = base;
@@ -75,6 +78,11 @@ __device__ __forceinline__ void assemble_side_body(const AssembleArgs& a, int b)
       if (et >= n - 1) ye = ye + yf;
     } else if ((t == et - 1) || (t == et + 1 && et < n - 1)) {
       ye = yf;
+    }
+    if (t < nsoft) {            // three float32 operations, each rounded on its own (no contraction)
+      const size_t so = (size_t)s * a.soft_ld + t;
+      ys = __fadd_rn(ys, __fmul_rn(lam, __fsub_rn(a.soft_y1[so], ys)));
+      ye = __fadd_rn(ye, __fmul_rn(lam, __fsub_rn(a.soft_y2[so], ye)));
     }
     // later writes win: B-M (1), then I-M (2) + inner, then E-M (3)
     int m = 0, in = 0;
@@ -107,6 +115,7 @@ int launch_assemble(const AssembleArgs& a, hipStream_t s) {
   HUAL_REQUIRE(a.video && a.lens && a.word_ids && a.char_ids, "assemble: null output pointer");
   HUAL_REQUIRE(a.B > 0 && a.T > 0 && a.L > 0 && a.C > 0 && a.vdim > 0 && a.vdim % 4 == 0, "assemble: bad shape");
   HUAL_REQUIRE(!a.y1 || (a.y2 && a.match && a.inner && a.s_ind && a.e_ind), "assemble: labels need y1, y2, match, inner, s_ind, e_ind");
+  HUAL_REQUIRE(!a.soft_w || (a.soft_y1 && a.soft_y2 && a.soft_ld >= 1), "assemble: soft labels need y1, y2, w and ld >= 1");
   const size_t total = (size_t)a.B * a.T * (a.vdim >> 2);
   const unsigned grid = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   const double valid_guess = 0.75;     // bytes read depend on the lengths; reported figure assumes 3/4 valid rows
@@ -117,6 +126,34 @@ int launch_assemble(const AssembleArgs& a, hipStream_t s) {
 }
 
 }  // namespace hual
+
+namespace {
+
+// the dataset, the batch and its feeds: what every entry point below hands to the launch
+AssembleArgs assemble_args(const hual_dataset* ds, const int32_t* sel, int B, int T, int L, int C, float* video, int32_t* video_seq_len,
+                           int32_t* word_ids, int32_t* char_ids, float* y1, float* y2, int32_t* match_labels, float* inner_labels) {
+  AssembleArgs a{};
+  a.feat_bank = ds->feat_bank; a.feat_off = ds->feat_off; a.vdim = ds->vdim; a.sample_vid = ds->sample_vid;
+  a.word_off = ds->word_off; a.word_bank = ds->word_bank; a.char_off = ds->char_off; a.char_bank = ds->char_bank;
+  a.s_ind = ds->s_ind; a.e_ind = ds->e_ind;
+  a.sel = sel; a.B = B; a.T = T; a.L = L; a.C = C;
+  a.video = video; a.lens = video_seq_len; a.word_ids = word_ids; a.char_ids = char_ids;
+  a.y1 = y1; a.y2 = y2; a.match = match_labels; a.inner = inner_labels;
+  return a;
+}
+
+// the banks of a _soft entry point.  A null array must never turn the call into a plain assembly: refused here, before
+// launch_assemble chooses by a.soft_w
+int soft_args(AssembleArgs& a, const hual_soft_labels* soft, const std::string& who) {
+  HUAL_REQUIRE(soft, who + ": null soft labels");
+  HUAL_REQUIRE(soft->y1 && soft->y2 && soft->w, who + ": null soft->y1, soft->y2 or soft->w");
+  HUAL_REQUIRE(soft->ld >= 1, who + ": soft->ld >= 1");
+  HUAL_REQUIRE(a.y1, who + ": soft labels need the label feeds y1, y2, match_labels, inner_labels");
+  a.soft_y1 = soft->y1; a.soft_y2 = soft->y2; a.soft_w = soft->w; a.soft_ld = soft->ld;
+  return 0;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -132,13 +169,7 @@ int hual_assemble_batch_carry(const hual_dataset* ds, const int32_t* sel, int B,
                               int32_t* match_labels, float* inner_labels, const int64_t* carry_src, int64_t* carry_dst, int carry_n,
                               void* stream) {
   HUAL_REQUIRE(ds, "hual_assemble_batch: null dataset");
-  AssembleArgs a{};
-  a.feat_bank = ds->feat_bank; a.feat_off = ds->feat_off; a.vdim = ds->vdim; a.sample_vid = ds->sample_vid;
-  a.word_off = ds->word_off; a.word_bank = ds->word_bank; a.char_off = ds->char_off; a.char_bank = ds->char_bank;
-  a.s_ind = ds->s_ind; a.e_ind = ds->e_ind;
-  a.sel = sel; a.B = B; a.T = T; a.L = L; a.C = C;
-  a.video = video; a.lens = video_seq_len; a.word_ids = word_ids; a.char_ids = char_ids;
-  a.y1 = y1; a.y2 = y2; a.match = match_labels; a.inner = inner_labels;
+  AssembleArgs a = assemble_args(ds, sel, B, T, L, C, video, video_seq_len, word_ids, char_ids, y1, y2, match_labels, inner_labels);
   a.carry_src = carry_src; a.carry_dst = carry_dst; a.carry_n = carry_n;
   return launch_assemble(a, (hipStream_t)stream);
 }
@@ -147,13 +178,29 @@ int hual_assemble_batch_cursor(const hual_dataset* ds, const int32_t* ids, const
                                int32_t* video_seq_len, int32_t* word_ids, int32_t* char_ids, float* y1, float* y2,
                                int32_t* match_labels, float* inner_labels, void* stream) {
   HUAL_REQUIRE(ds && cursor, "hual_assemble_batch_cursor: null dataset / cursor");
-  AssembleArgs a{};
-  a.feat_bank = ds->feat_bank; a.feat_off = ds->feat_off; a.vdim = ds->vdim; a.sample_vid = ds->sample_vid;
-  a.word_off = ds->word_off; a.word_bank = ds->word_bank; a.char_off = ds->char_off; a.char_bank = ds->char_bank;
-  a.s_ind = ds->s_ind; a.e_ind = ds->e_ind;
-  a.sel = ids; a.cursor = cursor; a.B = B; a.T = T; a.L = L; a.C = C;
-  a.video = video; a.lens = video_seq_len; a.word_ids = word_ids; a.char_ids = char_ids;
-  a.y1 = y1; a.y2 = y2; a.match = match_labels; a.inner = inner_labels;
+  AssembleArgs a = assemble_args(ds, ids, B, T, L, C, video, video_seq_len, word_ids, char_ids, y1, y2, match_labels, inner_labels);
+  a.cursor = cursor;
+  return launch_assemble(a, (hipStream_t)stream);
+}
+
+int hual_assemble_batch_soft(const hual_dataset* ds, const int32_t* sel, int B, int T, int L, int C, float* video,
+                             int32_t* video_seq_len, int32_t* word_ids, int32_t* char_ids, float* y1, float* y2,
+                             int32_t* match_labels, float* inner_labels, const int64_t* carry_src, int64_t* carry_dst, int carry_n,
+                             const hual_soft_labels* soft, void* stream) {
+  HUAL_REQUIRE(ds, "hual_assemble_batch_soft: null dataset");
+  AssembleArgs a = assemble_args(ds, sel, B, T, L, C, video, video_seq_len, word_ids, char_ids, y1, y2, match_labels, inner_labels);
+  a.carry_src = carry_src; a.carry_dst = carry_dst; a.carry_n = carry_n;
+  if (int rc = soft_args(a, soft, "hual_assemble_batch_soft")) return rc;
+  return launch_assemble(a, (hipStream_t)stream);
+}
+
+int hual_assemble_batch_cursor_soft(const hual_dataset* ds, const int32_t* ids, const int64_t* cursor, int B, int T, int L, int C,
+                                    float* video, int32_t* video_seq_len, int32_t* word_ids, int32_t* char_ids, float* y1, float* y2,
+                                    int32_t* match_labels, float* inner_labels, const hual_soft_labels* soft, void* stream) {
+  HUAL_REQUIRE(ds && cursor, "hual_assemble_batch_cursor_soft: null dataset / cursor");
+  AssembleArgs a = assemble_args(ds, ids, B, T, L, C, video, video_seq_len, word_ids, char_ids, y1, y2, match_labels, inner_labels);
+  a.cursor = cursor;
+  if (int rc = soft_args(a, soft, "hual_assemble_batch_cursor_soft")) return rc;
   return launch_assemble(a, (hipStream_t)stream);
 }
 

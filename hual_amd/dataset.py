@@ -59,6 +59,7 @@ class DeviceDataset:
         self.feat_off, self.sample_vid = up(feat_off), up(self.sample_vid_h)
         self.word_off, self.word_bank, self.char_off, self.char_bank = up(word_off), up(word_bank), up(char_off), up(char_bank)
         self.s_ind = self.e_ind = None
+        self.soft = None                                         # hual_soft_labels once enable_soft_labels() has run
         if 's_ind' in records[0]:
             self.set_labels([r['s_ind'] for r in records], [r['e_ind'] for r in records])
         else:
@@ -68,10 +69,56 @@ class DeviceDataset:
         return len(self.records)
 
     def set_labels(self, s_ind, e_ind):
-        """new pseudo labels (frame indices) after an update_label round"""
-        self.s_ind = torch.from_numpy(np.ascontiguousarray(s_ind, dtype=np.int32)).to(self.dev)
-        self.e_ind = torch.from_numpy(np.ascontiguousarray(e_ind, dtype=np.int32)).to(self.dev)
+        """new pseudo labels (frame indices) after an update_label round.  Written IN PLACE once the tensors exist: a trainer's step
+        graphs hold the assembly launch with the addresses of s_ind / e_ind (Trainer.run_epoch), and a trainer kept across rounds
+        (al.run_round(trainer=)) replays them."""
+        s = torch.from_numpy(np.ascontiguousarray(s_ind, dtype=np.int32))
+        e = torch.from_numpy(np.ascontiguousarray(e_ind, dtype=np.int32))
+        if self.s_ind is not None and self.s_ind.shape == s.shape and self.e_ind.shape == e.shape:
+            self.s_ind.copy_(s)
+            self.e_ind.copy_(e)
+            return
+        self.s_ind, self.e_ind = s.to(self.dev), e.to(self.dev)
         self._struct()
+
+    # ---- soft labels: two banks of per-frame distributions beside s_ind / e_ind, blended into y1 / y2 by the assembly launch
+    def enable_soft_labels(self):
+        """allocate the soft-label banks y1 / y2 f32 [N, longest clip] and the weight vector w f32 [N] (all 0: every label is the
+        reference's), ONCE: the step graphs of an epoch loop hold the assembly launch with these addresses, so they never change.
+        From here on assemble() and enqueue_assemble_cursor() go through hual_assemble_batch_soft / _cursor_soft."""
+        if self.soft is not None:
+            return
+        if self.s_ind is None:
+            raise ValueError('soft labels need a training set (records with s_ind / e_ind)')
+        N, ld = len(self.records), int(self.vlen_h.max())
+        self.soft_y1 = torch.zeros(N, ld, device=self.dev)
+        self.soft_y2 = torch.zeros(N, ld, device=self.dev)
+        self.soft_w = torch.zeros(N, device=self.dev)
+        self.soft = lib.hual_soft_labels(lib._addr(self.soft_y1), lib._addr(self.soft_y2), lib._addr(self.soft_w), ld)
+
+    def soft_address(self):
+        """the banks' device address, 0 while they are not enabled: part of a trainer's graph-cache key"""
+        return 0 if self.soft is None else self.soft_y1.data_ptr()
+
+    def set_soft_labels(self, y1, y2, w):
+        """copy new soft labels into the banks, in place.  y1 / y2: device or host float [N, >= longest clip] - the leading columns
+        are taken (the rows of lib.al_span_marginals, say); w: [N] weights, checked on the host to be finite and in [0, 1]."""
+        self.enable_soft_labels()
+        N, ld = self.soft_y1.shape
+        w = np.ascontiguousarray(w.cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32).reshape(-1)
+        if w.size != N or not np.isfinite(w).all() or (w < 0).any() or (w > 1).any():
+            raise ValueError('soft labels: w must hold N = %d finite weights in [0, 1]' % N)
+        for y in (y1, y2):
+            if y.ndim != 2 or y.shape[0] != N or y.shape[1] < ld:
+                raise ValueError('soft labels: y1 / y2 must be [N, >= ld] = [%d, >= %d]' % (N, ld))
+        for bank, y in ((self.soft_y1, y1), (self.soft_y2, y2)):
+            bank.copy_(torch.as_tensor(y)[:, :ld])
+        self.soft_w.copy_(torch.from_numpy(w))
+
+    def clear_soft_labels(self):
+        """back to the reference's labels: every weight 0 (the banks stay where they are)"""
+        if self.soft is not None:
+            self.soft_w.zero_()
 
     def _struct(self):
         p = lambda t: None if t is None else lib.ptr(t).value
@@ -122,10 +169,13 @@ class DeviceDataset:
         L, C = views['word_ids'].shape[1], views['char_ids'].shape[2]
         labels = 'y1' in views
         p = lib.ptr
-        lib.check(self._lib.hual_assemble_batch_cursor(
-            ctypes.byref(self.ds), p(ids_dev), p(cursor), B, T, L, C, p(views['video']), p(views['video_seq_len']), p(views['word_ids']),
-            p(views['char_ids']), p(views['y1']) if labels else None, p(views['y2']) if labels else None,
-            p(views['match_labels']) if labels else None, p(views['inner_labels']) if labels else None, lib.stream_ptr()))
+        args = (ctypes.byref(self.ds), p(ids_dev), p(cursor), B, T, L, C, p(views['video']), p(views['video_seq_len']), p(views['word_ids']),
+                p(views['char_ids']), p(views['y1']) if labels else None, p(views['y2']) if labels else None,
+                p(views['match_labels']) if labels else None, p(views['inner_labels']) if labels else None)
+        if self.soft is not None and labels:
+            lib.check(self._lib.hual_assemble_batch_cursor_soft(*args, ctypes.byref(self.soft), lib.stream_ptr()))
+        else:
+            lib.check(self._lib.hual_assemble_batch_cursor(*args, lib.stream_ptr()))
 
     def assemble(self, sel, out=None, labels=True, min_chars=None, buffers=None, sel_dev=None, carry=None, shape=None):
         """Gather the batch `sel` (sample ids) on the device.  Returns a dict of device tensors named like the feeds of
@@ -174,8 +224,11 @@ class DeviceDataset:
             src, dst = carry
             assert src.dtype == torch.int64 and dst.dtype == torch.int64 and src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()
             csrc, cdst, cn = p(src), p(dst), src.numel()
-        lib.check(self._lib.hual_assemble_batch_carry(
-            ctypes.byref(self.ds), p(out['sel']), B, T, L, C, p(out['video']), p(out['video_seq_len']), p(out['word_ids']),
-            p(out['char_ids']), p(out['y1']) if labels else None, p(out['y2']) if labels else None,
-            p(out['match_labels']) if labels else None, p(out['inner_labels']) if labels else None, csrc, cdst, cn, lib.stream_ptr()))
+        args = (ctypes.byref(self.ds), p(out['sel']), B, T, L, C, p(out['video']), p(out['video_seq_len']), p(out['word_ids']),
+                p(out['char_ids']), p(out['y1']) if labels else None, p(out['y2']) if labels else None,
+                p(out['match_labels']) if labels else None, p(out['inner_labels']) if labels else None, csrc, cdst, cn)
+        if self.soft is not None and labels:
+            lib.check(self._lib.hual_assemble_batch_soft(*args, ctypes.byref(self.soft), lib.stream_ptr()))
+        else:
+            lib.check(self._lib.hual_assemble_batch_carry(*args, lib.stream_ptr()))
         return out

@@ -147,11 +147,15 @@ class HostFeeder:
                 np.copyto(views[k], np.asarray(src), casting='same_kind' if views[k].dtype.kind == 'f' else 'unsafe')
         self.submit(lr, drop_rate)
 
-    def feed_records(self, records, visual_feats, lr, drop_rate, min_chars=4):
+    def feed_records(self, records, visual_feats, lr, drop_rate, min_chars=4, soft_labels=None):
         """one batch straight from the loader's INPUTS (data_loader.py:30-98: records with vid / w_ids / c_ids / s_ind / e_ind and the
         {vid: float32 [n, V]} features): padded directly into the pinned slot - no intermediate batch, no staging copy; the clips are
-        copied by the staging threads.  float32 feed only."""
+        copied by the staging threads.  float32 feed only.  soft_labels: refused - the soft-label banks are blended by the device-side
+        assembly (DeviceDataset.set_soft_labels); this path builds the reference's labels on the host."""
         from . import data
+        if soft_labels is not None:
+            raise ValueError('the host-fed path builds the reference\'s labels: soft labels need the device-resident set '
+                             '(DeviceDataset.set_soft_labels)')
         if self.vdt != torch.float32:
             return self.feed(data.process_train_batch(records, visual_feats), lr, drop_rate)
         feats = [visual_feats[r['vid']] for r in records]

@@ -79,6 +79,10 @@ class hual_dataset(ctypes.Structure):
                 ('e_ind', ctypes.c_void_p)]
 
 
+class hual_soft_labels(ctypes.Structure):
+    _fields_ = [('y1', ctypes.c_void_p), ('y2', ctypes.c_void_p), ('w', ctypes.c_void_p), ('ld', ctypes.c_int32)]
+
+
 class hual_ws_entry(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char * 48), ('offset', ctypes.c_uint64), ('rows', ctypes.c_uint64),
                 ('cols', ctypes.c_uint64)]
@@ -164,6 +168,9 @@ def load():
     lib.hual_al_label_gain.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_carry.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.hual_al_span_marginals.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp]
+    lib.hual_assemble_batch_soft.argtypes = lib.hual_assemble_batch_carry.argtypes[:-1] + [P(hual_soft_labels), vp]
+    lib.hual_assemble_batch_cursor_soft.argtypes = lib.hual_assemble_batch_cursor.argtypes[:-1] + [P(hual_soft_labels), vp]
     _lib = lib
     return lib
 
@@ -485,4 +492,36 @@ def al_label_gain(aset, s0, e0, tlen, sel=None, cand=None, frames=True, out=None
                 raise HualError('al_label_gain: out tensors must be contiguous, on the logits\' device, f32 [N, ld], i32 [N], f32 [N], f32 [N]')
     check(load().hual_al_label_gain(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, ptr(cand), M, *[ptr(o) for o in out],
                                     stream_ptr()))
+    return tuple(out)
+
+
+def al_span_marginals(aset, s0, e0, tlen, out=None):
+    """the start and end marginals of the span posterior of every sample of the hual_al_set `aset` given its answered active points
+    (hual_al_span_marginals), one launch enqueued on the current stream: the soft labels DeviceDataset.set_soft_labels takes.  s0 / e0:
+    the deterministic logits f32 [N, ld] on the device; tlen: the set's row lengths on the HOST - a row above AL_QUERY_MAX_T frames is
+    refused here, before the launch, as in al_query.
+    -> (y_start f32 [N, ld], y_end f32 [N, ld], status i32 [N]): status 1 = a live row, 0 = a poisoned or contradictory one, whose
+    columns are 0.  out: such a tuple of contiguous device tensors to write into instead; columns beyond a row's tlen keep what they
+    held (0 in tensors allocated here)."""
+    import numpy as np
+    import torch
+    N, ld = int(aset.N), int(aset.ld)
+    tl = np.asarray(tlen)
+    if tl.size != N:
+        raise HualError('al_span_marginals: tlen must hold N = %d row lengths' % N)
+    if int(tl.max()) > AL_QUERY_MAX_T:
+        raise HualError('al_span_marginals: a row of %d frames - the span posterior handles at most %d' % (int(tl.max()), AL_QUERY_MAX_T))
+    for x in (s0, e0):
+        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous() or x.device != s0.device:
+            raise HualError('al_span_marginals: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d] on one device' % (N, ld))
+    dev = s0.device
+    if out is None:
+        out = (torch.zeros(N, ld, device=dev), torch.zeros(N, ld, device=dev), torch.zeros(N, dtype=torch.int32, device=dev))
+    else:
+        if len(out) != 3 or any(o is None for o in out):
+            raise HualError('al_span_marginals: out is (y_start, y_end, status)')
+        for o, shape, dt in zip(out, ((N, ld), (N, ld), (N,)), (torch.float32, torch.float32, torch.int32)):
+            if o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev:
+                raise HualError('al_span_marginals: out tensors must be contiguous, on the logits\' device, f32 [N, ld] twice and i32 [N]')
+    check(load().hual_al_span_marginals(ctypes.byref(aset), ptr(s0), ptr(e0), *[ptr(o) for o in out], stream_ptr()))
     return tuple(out)

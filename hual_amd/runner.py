@@ -110,6 +110,12 @@ class Runner:
                                 % (int((st < 0).sum()), float(self.trainer.last_loss()), os.path.join(self.ckpt_dir, 'best_SeqPAN.npz')))
         return al.iou_metrics(self._ious([recs[i] for i in order], st, en))
 
+    def set_soft_labels(self, y1, y2, w):
+        """soft start / end labels for the training set (DeviceDataset.set_soft_labels): the following epochs train on them"""
+        if self.feed == 'host':
+            raise ValueError("feed='host' builds the reference's labels on the host: soft labels need the device-resident set (feed='device')")
+        self.train_set.set_soft_labels(y1, y2, w)
+
     def train_epoch(self, cur_lr):
         if self.feed == 'host':
             return self._train_epoch_host(cur_lr)

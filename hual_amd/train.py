@@ -189,7 +189,7 @@ class Trainer:
         self.start_index, self.end_index = self.spans[0, :B], self.spans[1, :B]
         lp = self._loop
         key = (B, T, L, C, vdt, self.ws.data_ptr(), self._out_flat.data_ptr(), self.loss_terms.data_ptr(), self.spans.data_ptr(),
-               0 if lp is None else (lp['ids'].data_ptr(), lp['cursor'].data_ptr(), lp['bank'].data_ptr())) + tuple(
+               0 if lp is None else (lp['ids'].data_ptr(), lp['cursor'].data_ptr(), lp['bank'].data_ptr(), lp['ds'].soft_address())) + tuple(
             t.data_ptr() for t in (self.video, self.lens, self.word_ids, self.char_ids, self.y1, self.y2, self.match, self.inner))
         s = self._cache.pop(key, None)                           # (re-)inserted below: most recently used last
         if s is None:

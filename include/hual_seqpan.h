@@ -455,6 +455,35 @@ int hual_assemble_batch_cursor(const hual_dataset* ds, const int32_t* ids, const
                                int32_t* video_seq_len, int32_t* word_ids, int32_t* char_ids, float* y1, float* y2,
                                int32_t* match_labels, float* inner_labels, void* stream);
 
+/* Soft-label banks beside the dataset (HUAL_ABI_VERSION unchanged: new symbols, nothing else moved; hual_dataset and the three entry
+ * points above are what they were).  y1 / y2: device f32 [n_samples, ld] row major, a distribution over the frames of every sample's
+ * clip to train the start / end head on instead of the reference's three-frame kernel around s_ind / e_ind (the rows
+ * hual_al_span_marginals writes, say); w: device f32 [n_samples], 0 <= w <= 1, how far sample s moves towards its rows; ld >= the
+ * longest clip of the set. */
+typedef struct hual_soft_labels {
+  const float* y1;
+  const float* y2;
+  const float* w;
+  int32_t ld;
+} hual_soft_labels;
+
+/* hual_assemble_batch_carry / hual_assemble_batch_cursor - the same launch, arguments and checks, every other feed bit-identical - with
+ * the labels blended towards the banks.  With r the value the plain entry points write at frame t of sample s (clip of n frames) and
+ * lam = w[s]:
+ *  - lam == 0, or t >= n (or t >= ld): r, untouched; bank[s][t] is not read, so a NaN in the row of an unweighted sample cannot leak.
+ *  - else: r + lam * (bank[s][t] - r) as three float32 operations each rounded on its own, __fadd_rn(r, __fmul_rn(lam, __fsub_rn(bank, r))):
+ *    no contraction, so a float32 restatement on the host reproduces it bit for bit.  lam == 1 gives the bank's value up to rounding.
+ * match_labels and inner_labels stay those of the hard label s_ind / e_ind.  The weights are not validated on the device.
+ * Argument errors (those of the plain entry points; a null soft, a null array of it, ld < 1, or soft labels without the label feeds)
+ * return HUAL_ERR_INVALID before any HIP call: a null bank never turns the call into a plain assembly. */
+int hual_assemble_batch_soft(const hual_dataset* ds, const int32_t* sel, int B, int T, int L, int C, float* video,
+                             int32_t* video_seq_len, int32_t* word_ids, int32_t* char_ids, float* y1, float* y2,
+                             int32_t* match_labels, float* inner_labels, const int64_t* carry_src, int64_t* carry_dst, int carry_n,
+                             const hual_soft_labels* soft, void* stream);
+int hual_assemble_batch_cursor_soft(const hual_dataset* ds, const int32_t* ids, const int64_t* cursor, int B, int T, int L, int C,
+                                    float* video, int32_t* video_seq_len, int32_t* word_ids, int32_t* char_ids, float* y1, float* y2,
+                                    int32_t* match_labels, float* inner_labels, const hual_soft_labels* soft, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Active-learning label update (BASELINE.json configs[4]): what /root/reference/update_label.py does
  * per training sample between two training rounds, for the whole training set in two launches.
@@ -651,6 +680,28 @@ int hual_al_mbr_label(const hual_al_set* set, const float* s0, const float* e0, 
  * [1, 256]) return HUAL_ERR_INVALID before any HIP call. */
 int hual_al_label_gain(const hual_al_set* set, const float* s0, const float* e0, const int32_t* sel, int nsel, const int32_t* cand,
                        int M, float* gain, int32_t* ask_point, float* ask_gain, float* value, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * What to train on, under the same posterior (HUAL_ABI_VERSION unchanged: one new symbol, nothing else moved).  hual_al_query reads the
+ * posterior for the question, hual_al_mbr_label for one hard span; these are its two marginals - the distribution of the start frame
+ * and of the end frame given the answers - in the shape of the model's y1 / y2 feeds, whose loss is a soft cross entropy: a clip whose
+ * posterior still spreads over twenty frames is trained with that spread, and an answered negative carries no mass.  Per sample n of
+ * the set, with T, v, p_s, p_e, w, the ignored active points, A and Z_A exactly as hual_al_query above defines them:
+ *  - y_start f32 [N, ld]: y_start[n][i] = (1 / Z_A) * the sum over the j with (i, j) in A of w(i,j);
+ *    y_end f32 [N, ld]: y_end[n][j] = (1 / Z_A) * the sum over the i with (i, j) in A of w(i,j).  Float64 accumulation, stored as
+ *    float32; each row sums to 1 up to that rounding.  Columns [0, T) are written, 0 at t >= v; columns [T, ld) are not touched.
+ *  - status i32 [N]: 1 for a live row; 0 for a poisoned row (v < 1, a NaN logit at t < v, a Z that is not a positive finite number, or
+ *    T > 256) and for a contradictory one (Z_A not positive), whose columns [0, min(T, ld)) of both outputs are 0.
+ *  - a collapsed posterior (one consistent span; v == 1) is not an error: the row is live and both outputs are one-hot.
+ * No walk over the triangle: within A the partners of a frame form one interval.  Around a positive hull A = (negL, lo] x [hi, negR)
+ * and the marginals are independent, p_s[i] / S and p_e[j] / E with S and E the sums over those two intervals; without a positive A is
+ * the union of the triangles over the gaps between negatives, Z_A y_start[i] = p_s[i] * (the sum of p_e from i to the end of i's gap)
+ * and Z_A y_end[j] = p_e[j] * (the sum of p_s from the start of j's gap to j).  Every sum adds terms of one sign in float64 in a fixed
+ * order: no difference of prefix sums, no atomics, nothing grid wide.  One launch over the whole set, one workgroup per sample.
+ * Allocates nothing and does not synchronise: capturable in a hipGraph.
+ * Argument errors (a null pointer, N < 1, ld outside [2, 1024]) return HUAL_ERR_INVALID before any HIP call. */
+int hual_al_span_marginals(const hual_al_set* set, const float* s0, const float* e0, float* y_start, float* y_end, int32_t* status,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
