@@ -14,12 +14,7 @@ enum AlSource {
 };
 
 struct AlScoreArgs {
-  int ld, N;                                  // the set (hual_al_set) ...
-  const int32_t* vlen;                        // [N] valid frames
-  const int32_t* tlen;                        // [N] length of the logits record (padded length of its batch)
-  const int32_t* ap_off;                      // [N+1] CSR offsets of the active points
-  const int32_t* ap_idx;                      // frame index of each active point
-  const int8_t* ap_pos;                       // 1 = inside the ground-truth span, 0 = outside
+  hual_al_set set;                            // N, ld | vlen [N] valid frames | tlen [N] length of the logits record | the active points (CSR)
   const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
   float coff_uncert;
   // the source of the model-uncertainty term: a launch reads the fields of its AlSource, the others stay null
@@ -53,26 +48,21 @@ struct AlRenewArgs {
   const int32_t* sel;                         // [nsel] sample ids to update (NULL: all)
   const float* sprob;
   const float* eprob;
-  int ld;
-  const int32_t* vlen;
-  const int32_t* tlen;
-  const int32_t* ap_off;
-  const int32_t* ap_idx;
-  const int8_t* ap_pos;
+  hual_al_set set;
   const int32_t* old_idx;                     // [N, 2]
   double coff[6];                             // pos.distance, pos.model, pos.old, neg.distance, neg.model, neg.old
   int32_t* new_idx;                           // [N, 2] (rows of unselected samples are left untouched)
 };
 
-// hual_al_query: the posterior over spans given the answered active points, and the frame whose answer carries most information
+// what every span-posterior launch reads (spanpost.h opens a row from it): the set and the deterministic pass
+struct AlSpanIn {
+  hual_al_set set;
+  const float *s0, *e0;                       // [N, ld] start / end logits
+};
+
+// hual_al_query (spanquery.hip): the posterior over spans given the answered active points, and the frame whose answer carries most information
 struct AlQueryArgs {
-  int ld, N;                                  // the set (hual_al_set), as in AlScoreArgs
-  const int32_t* vlen;
-  const int32_t* tlen;
-  const int32_t* ap_off;
-  const int32_t* ap_idx;
-  const int8_t* ap_pos;
-  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
+  AlSpanIn in;
   float *incl, *gain;                         // [N, ld] q(t) and h2(q(t)) in bits, columns [0, tlen[n]) (NULL, both: not written)
   int32_t* query_point;                       // [N] first frame of maximal gain
   float *query_gain, *post_entropy, *agree;   // [N]
@@ -80,13 +70,7 @@ struct AlQueryArgs {
 
 // hual_al_mbr_label (spanlabel.hip): the span of the consistent set of maximal expected tIoU under the answered-point posterior
 struct AlLabelArgs {
-  int ld, N;                                  // the set (hual_al_set), as in AlScoreArgs
-  const int32_t* vlen;
-  const int32_t* tlen;
-  const int32_t* ap_off;
-  const int32_t* ap_idx;
-  const int8_t* ap_pos;
-  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
+  AlSpanIn in;
   const int32_t* sel;                         // [nsel] sample ids to label (NULL: all)
   const int32_t* old_idx;                     // [N, 2] (NULL with old_conf: not scored)
   int32_t* new_idx;                           // [N, 2] (rows of unselected samples are left untouched, as conf and old_conf)
@@ -95,13 +79,7 @@ struct AlLabelArgs {
 
 // hual_al_label_gain (spangain.hip): per frame, the tIoU the label of hual_al_mbr_label is expected to gain from the frame's answer
 struct AlGainArgs {
-  int ld, N;                                  // the set (hual_al_set), as in AlScoreArgs
-  const int32_t* vlen;
-  const int32_t* tlen;
-  const int32_t* ap_off;
-  const int32_t* ap_idx;
-  const int8_t* ap_pos;
-  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
+  AlSpanIn in;
   const int32_t* sel;                         // [nsel] sample ids to evaluate (NULL: all)
   const int32_t* cand;                        // [N, M] the frames to evaluate, entries outside [0, v) skipped (NULL: every frame)
   int M;
@@ -112,16 +90,21 @@ struct AlGainArgs {
 
 // hual_al_span_marginals (spanmarg.hip): the start / end marginals of the span posterior given the answered active points
 struct AlMargArgs {
-  int ld, N;                                  // the set (hual_al_set), as in AlScoreArgs
-  const int32_t* vlen;
-  const int32_t* tlen;
-  const int32_t* ap_off;
-  const int32_t* ap_idx;
-  const int8_t* ap_pos;
-  const float *s0, *e0;                       // [N, ld] start / end logits of the deterministic pass
+  AlSpanIn in;
   float *y_start, *y_end;                     // [N, ld] columns [0, tlen[n])
   int32_t* status;                            // [N] 1 = live, 0 = poisoned or contradictory
 };
+
+// the null and N / ld requirements of an AlSpanIn, refused under the entry point's prefix `who`; between the two, in the order the
+// launches have always checked in, the launch's own requirements (`own`: null outputs, nsel, ... - returns 0 or the failure)
+template <class Own>
+int check_span_in(const AlSpanIn& in, const char* who, Own own) {
+  const hual_al_set& s = in.set;
+  HUAL_REQUIRE(in.s0 && in.e0 && s.vlen && s.tlen && s.ap_off && s.ap_idx && s.ap_pos, std::string(who) + ": null input");
+  if (const int rc = own()) return rc;
+  HUAL_REQUIRE(s.N > 0 && s.ld >= 2 && s.ld <= HUAL_AL_MAX_T, std::string(who) + ": need N > 0 and 2 <= ld <= 1024");
+  return 0;
+}
 
 int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s);
 int launch_al_span_marginals(const AlMargArgs& a, hipStream_t s);
@@ -130,5 +113,16 @@ int launch_al_mbr_label(const AlLabelArgs& a, int nsel, hipStream_t s);
 int launch_al_query(const AlQueryArgs& a, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);
+
+// binary entropy in bits, every operation rounded on its own (tests/mc_info_ref.py is its float64 yardstick).  The fold, the score and the
+// query evaluate this one function: K identical passes leave mean == p and ent == h2(p), and BALD = h2(mean) - ent is then exactly 0.
+__device__ __forceinline__ float h2_bits(float p) {
+#pragma clang fp contract(off)
+  if (p <= 0.0f || p >= 1.0f) return 0.0f;
+  const float q = 1.0f - p;
+  const float a = p * log2f(p);
+  const float b = q * log2f(q);
+  return -(a + b);
+}
 
 }  // namespace hual

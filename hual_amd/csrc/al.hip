@@ -11,9 +11,7 @@
 //   * score mixtures / uncert_frame: float64 sums of float32 terms.
 // Active points arrive as one CSR list per sample (frame index + positive flag), in the order they were annotated.
 #include "al.h"
-#include "alpost.h"
 #include "prof.h"
-#include "spanprob.h"
 
 using namespace hual;
 
@@ -121,17 +119,6 @@ __device__ void distance_block(const int* seg, int nseg, double shift, int vlen,
 
 __device__ __forceinline__ float sigmoid_np(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// binary entropy in bits, every operation rounded on its own (tests/mc_info_ref.py is its float64 yardstick).  The fold and the score
-// evaluate this one function: K identical passes leave mean == p and ent == h2(p), and BALD = h2(mean) - ent is then exactly 0.
-__device__ __forceinline__ float h2_bits(float p) {
-#pragma clang fp contract(off)
-  if (p <= 0.0f || p >= 1.0f) return 0.0f;
-  const float q = 1.0f - p;
-  const float a = p * log2f(p);
-  const float b = q * log2f(q);
-  return -(a + b);
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------
@@ -181,17 +168,17 @@ __global__ __launch_bounds__(AL_THREADS) void al_score_kernel(AlScoreArgs a) {
   __shared__ int seg[2 * AL_MAX_SEG];
   __shared__ int nseg;
   const int n = blockIdx.x;
-  const int T = a.tlen[n], V = a.vlen[n];
+  const int T = a.set.tlen[n], V = a.set.vlen[n];
   float* dist = lds;
-  float* tmp = lds + a.ld;
-  const int ap0 = a.ap_off[n], napn = a.ap_off[n + 1] - ap0;
-  const int32_t* aidx = a.ap_idx + ap0;
-  const int8_t* apos = a.ap_pos + ap0;
+  float* tmp = lds + a.set.ld;
+  const int ap0 = a.set.ap_off[n], napn = a.set.ap_off[n + 1] - ap0;
+  const int32_t* aidx = a.set.ap_idx + ap0;
+  const int8_t* apos = a.set.ap_pos + ap0;
   const ApInfo ap = scan_ap(aidx, apos, napn);
   find_segments(ap, aidx, apos, napn, V, T, seg, &nseg);
   distance_block(seg, nseg, 0.0, V, T, dist, tmp, red);
 
-  const size_t row = (size_t)n * a.ld;
+  const size_t row = (size_t)n * a.set.ld;
   double vsum = 0.0;
   double best = -1.0;
   int besti = 0x7fffffff;
@@ -302,23 +289,23 @@ __global__ __launch_bounds__(AL_THREADS) void al_renew_kernel(AlRenewArgs a) {
   __shared__ int seg[2 * AL_MAX_SEG];
   __shared__ int nseg;
   const int n = a.sel ? a.sel[blockIdx.x] : (int)blockIdx.x;
-  const int T = a.tlen[n], V = a.vlen[n];
-  const int ldp = (a.ld + 1) & ~1;
+  const int T = a.set.tlen[n], V = a.set.vlen[n];
+  const int ldp = (a.set.ld + 1) & ~1;
   float* ds = lds;
   float* de = lds + ldp;
   float* tmp = lds + 2 * ldp;
   double* ss = reinterpret_cast<double*>(lds + 4 * ldp);
   double* es = ss + ldp;
-  const int ap0 = a.ap_off[n], napn = a.ap_off[n + 1] - ap0;
-  const int32_t* aidx = a.ap_idx + ap0;
-  const int8_t* apos = a.ap_pos + ap0;
+  const int ap0 = a.set.ap_off[n], napn = a.set.ap_off[n + 1] - ap0;
+  const int32_t* aidx = a.set.ap_idx + ap0;
+  const int8_t* apos = a.set.ap_pos + ap0;
   const ApInfo ap = scan_ap(aidx, apos, napn);
   const bool has_pos = ap.npos > 0;
   const double a1 = has_pos ? a.coff[0] : a.coff[3];
   const float a2 = (float)(has_pos ? a.coff[1] : a.coff[4]);
   const float a3 = (float)(has_pos ? a.coff[2] : a.coff[5]);
   const double shift = has_pos ? -0.3 : 0.9;
-  const size_t row = (size_t)n * a.ld;
+  const size_t row = (size_t)n * a.set.ld;
 
   find_segments(ap, aidx, apos, napn, V, T, seg, &nseg);
   distance_block(seg, nseg, -shift, V, T, ds, tmp, red);     // start: centre - width*shift/2
@@ -389,152 +376,10 @@ __global__ __launch_bounds__(AL_THREADS) void al_renew_kernel(AlRenewArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------------
-// hual_al_query: the frame whose answer says most about the span.  The annotator's answer at frame t is a function of the true span,
-// so its mutual information with the span is the entropy h2(q(t)) of the answer, q(t) the posterior probability that t lies inside
-// the span: the span distribution P(i,j) ~ p_s[i] p_e[j] (spanprob.h: the numbers of hual_span_argmax) restricted to the set A of
-// spans the answered active points allow.  One 1024-thread workgroup per sample, as the other span kernels.
-//
-// No walk over the triangle: i <= t <= j implies i <= j, and A is a product of a start range and an end range (with a positive point:
-// (negL, lo] x [hi, negR)) or a union of triangles, one per gap between negatives (without one).  Both are read from SEGMENTED sums -
-// a negative frame closes a segment -: Ps(t) = sum of p_s over the segment's frames <= t, Pe(t) = sum of p_e over its frames >= t, and
-// the same two of p log2f p.  Then q(t) Z_A = Ps(min(t, lo)) Pe(max(t, hi)) resp. Ps(t) Pe(t), Z_A = Ps(lo) Pe(hi) resp. the sum over j of
-// p_e[j] Ps(j), and the entropy sum factors alike.  Every sum adds terms of one sign in float64 (no difference of prefix sums: a gap
-// that holds 1e-10 of the mass keeps its digits).  The four segmented sums and the unsegmented one behind Z are each a serial walk of one
-// thread per frame, the four kinds on the four quarters of the workgroup: at most 256 LDS reads and additions per thread, fixed order,
-// the segment's ends known before the walk (from the active-point list), so the reads are not chained to a flag read on every step.
-// ------------------------------------------------------------------------------------------------------
-namespace {
-
-enum AlQueryRow { AQ_LIVE, AQ_POISONED, AQ_CONTRADICTORY };
-
-// p log2f(p) in float64, 0 at p == 0 (where the logarithm is -inf)
-__device__ __forceinline__ double p_log2(float p, float l) { return p > 0.f ? (double)p * (double)l : 0.0; }
-
-}  // namespace
-
-__global__ __launch_bounds__(SPAN_THREADS) void al_query_kernel(AlQueryArgs a) {
-  __shared__ float ps[256], pe[256], ls[256], le[256];
-  __shared__ double cum[5][256];            // segmented: Ps | Ps of p log2 p | Pe | Pe of p log2 p;  [4]: the unsegmented Ps
-  __shared__ float smf[2 * SPAN_WAVES];
-  __shared__ double smd[3 * SPAN_WAVES];
-  __shared__ float bestv[SPAN_WAVES];
-  __shared__ int besti[SPAN_WAVES];
-  const int n = blockIdx.x, t = threadIdx.x;
-  const int T = a.tlen[n];
-  const size_t row = (size_t)n * a.ld;
-  const bool fits = T >= 1 && T <= 256 && T <= a.ld;      // a longer row is poisoned (the host cannot see tlen without a read-back)
-  const int v = fits ? span_clip_len(a.vlen[n], T) : 0;
-  int status = (v == 0 || span_row_poisoned(a.s0, a.e0, row, v)) ? AQ_POISONED : AQ_LIVE;      // (uniform)
-  double zf = 0.0, za = 0.0, hs = 0.0;
-  float q = 0.f, g = 0.f;
-  if (status == AQ_LIVE) {
-    span_probabilities(a.s0, a.e0, row, T, v, ps, pe, smf, smd);
-    if (t < v) { ls[t] = log2f(ps[t]); le[t] = log2f(pe[t]); }
-    // the active points inside the clip, as scan_ap reads them: the positive hull, the nearest negatives around it
-    const int ap0 = a.ap_off[n], napn = a.ap_off[n + 1] - ap0;
-    const int32_t* aidx = a.ap_idx + ap0;
-    const int8_t* apos = a.ap_pos + ap0;
-    const ApHull hull = ap_hull(aidx, apos, napn, v);
-    const int npos = hull.npos, lo = hull.lo, hi = hull.hi, negL = hull.negL, negR = hull.negR;
-    const bool inside = hull.inside;        // a negative inside the positive hull
-    // frame c's segment [a, b]: between the nearest negatives around it; closed: c is itself a negative
-    const int kind = t >> 8, c = t & 255;
-    const ApSegment sg = ap_segment(aidx, apos, napn, v, c);
-    const int sa = sg.sa, sb = sg.sb;
-    const bool closed = sg.closed;
-    __syncthreads();                        // ls / le are read across threads from here on
-    if (c < v) {
-      if (kind == 0) {
-        double below = 0.0, seg = 0.0;
-        for (int i = 0; i < sa; ++i) below += (double)ps[i];
-        for (int i = sa; i <= c; ++i) seg += (double)ps[i];
-        cum[4][c] = below + seg;            // (no negative below c: below == 0 and the sum is seg bit for bit)
-        cum[0][c] = closed ? 0.0 : seg;
-      } else if (kind == 1) {
-        double seg = 0.0;
-        for (int i = sa; i <= c; ++i) seg += p_log2(ps[i], ls[i]);
-        cum[1][c] = closed ? 0.0 : seg;
-      } else if (kind == 2) {
-        double seg = 0.0;
-        for (int i = c; i <= sb; ++i) seg += (double)pe[i];
-        cum[2][c] = closed ? 0.0 : seg;
-      } else {
-        double seg = 0.0;
-        for (int i = c; i <= sb; ++i) seg += p_log2(pe[i], le[i]);
-        cum[3][c] = closed ? 0.0 : seg;
-      }
-    }
-    __syncthreads();
-    // Z over the whole triangle, and over the gaps' triangles Z_A and the entropy sum (a negative frame holds zeros)
-    if (t < v) {
-      const double e = (double)pe[t];
-      zf = e * cum[4][t];
-      za = e * cum[0][t];
-      hs = e * cum[1][t] + p_log2(pe[t], le[t]) * cum[0][t];
-    }
-    block_reduce<BlockSumD, SPAN_WAVES>(zf, za, hs, smd);
-    if (npos > 0) {                         // starts in (negL, lo] x ends in [hi, negR)
-      const double S = cum[0][lo], E = cum[2][hi];
-      za = inside ? 0.0 : S * E;
-      hs = inside ? 0.0 : cum[1][lo] * E + S * cum[3][hi];
-    }
-    // (uniform) every weight underflowed or an infinite logit made them NaN: poisoned, as hual_span_expected_iou; nothing left in A
-    if (!(zf > 0.0 && zf < INFINITY)) status = AQ_POISONED;
-    else if (!(za > 0.0)) status = AQ_CONTRADICTORY;
-    if (status == AQ_LIVE) {
-      if (t < v) {
-        double num;
-        if (npos > 0) num = (t > negL && t < negR) ? cum[0][min(t, lo)] * cum[2][max(t, hi)] : 0.0;      // (on the hull: S * E, q == 1)
-        else num = cum[0][t] * cum[2][t];
-        q = (float)fmin(fmax(num / za, 0.0), 1.0);
-        g = h2_bits(q);
-      }
-      float best = t < v ? g : -1.0f;
-      int bi = t < v ? t : 0x7fffffff;
-      wave_best(best, bi);
-      if ((t & 63) == 0) { bestv[t >> 6] = best; besti[t >> 6] = bi; }
-      __syncthreads();
-      if (t == 0) {
-        best_of_waves(bestv, besti, SPAN_WAVES, best, bi);
-        const double h = log2(za) - hs / za;
-        a.query_point[n] = bi;
-        a.query_gain[n] = best;
-        a.post_entropy[n] = h > 0.0 ? (float)h : 0.f;
-        a.agree[n] = (float)(za / zf);
-      }
-    }
-  }
-  if (status != AQ_LIVE && t == 0) {
-    a.query_point[n] = -1;
-    a.query_gain[n] = -1.0f;
-    a.post_entropy[n] = -1.0f;
-    a.agree[n] = status == AQ_CONTRADICTORY ? 0.f : -1.0f;
-  }
-  // columns [0, T): q and its gain below v on a live row (thread t holds frame t), 0 elsewhere
-  const int Tw = min(max(T, 0), a.ld);
-  for (int c = t; c < Tw; c += SPAN_THREADS) {
-    const bool on = status == AQ_LIVE && c < v;
-    if (a.incl) a.incl[row + c] = on ? q : 0.f;
-    if (a.gain) a.gain[row + c] = on ? g : 0.f;
-  }
-}
-
 namespace hual {
 
-int launch_al_query(const AlQueryArgs& a, hipStream_t s) {
-  HUAL_REQUIRE(a.s0 && a.e0 && a.vlen && a.tlen && a.ap_off && a.ap_idx && a.ap_pos, "al_query: null input");
-  HUAL_REQUIRE(a.query_point && a.query_gain && a.post_entropy && a.agree, "al_query: null output");
-  HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_query: need N > 0 and 2 <= ld <= 1024");
-  // per frame: two logits in, q and its gain out
-  HUAL_LAUNCH(0.0, (8.0 + (a.incl ? 4.0 : 0.0) + (a.gain ? 4.0 : 0.0)) * a.N * a.ld + 28.0 * a.N, al_query_kernel, dim3(a.N),
-              dim3(SPAN_THREADS), 0, s, a);
-  HUAL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
 int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s) {
-  HUAL_REQUIRE(a.s0 && a.e0 && a.vlen && a.tlen && a.ap_off, "al_score: null input");
+  HUAL_REQUIRE(a.s0 && a.e0 && a.set.vlen && a.set.tlen && a.set.ap_off, "al_score: null input");
   if (src == AL_SRC_PAIR) HUAL_REQUIRE(a.s1 && a.e1 && a.s2 && a.e2, "al_score: null input");
   if (src == AL_SRC_SPREAD) {
     HUAL_REQUIRE(a.stat == HUAL_AL_STAT_RANGE || a.stat == HUAL_AL_STAT_STD, "al_score: stat is HUAL_AL_STAT_RANGE or HUAL_AL_STAT_STD");
@@ -547,14 +392,14 @@ int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s) {
     HUAL_REQUIRE(a.ent[0] && a.ent[1], "al_score: null info->ent_s or info->ent_e");
   }
   HUAL_REQUIRE(a.sprob && a.eprob && a.uncert_frame && a.uncert_video && a.observe, "al_score: null output");
-  HUAL_REQUIRE(a.N > 0 && a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_score: need N > 0 and 2 <= ld <= 1024");
-  const dim3 grid(a.N), block(AL_THREADS);
-  const size_t lds = 2 * a.ld * sizeof(float);
+  HUAL_REQUIRE(a.set.N > 0 && a.set.ld >= 2 && a.set.ld <= HUAL_AL_MAX_T, "al_score: need N > 0 and 2 <= ld <= 1024");
+  const dim3 grid(a.set.N), block(AL_THREADS);
+  const size_t lds = 2 * a.set.ld * sizeof(float);
   // per frame: the pair form reads six logits, the bank forms up to eight (and may write the term)
   switch (src) {
-    case AL_SRC_PAIR: HUAL_LAUNCH(0.0, 40.0 * a.N * a.ld, al_score_kernel<AL_SRC_PAIR>, grid, block, lds, s, a); break;
-    case AL_SRC_SPREAD: HUAL_LAUNCH(0.0, 44.0 * a.N * a.ld, al_score_kernel<AL_SRC_SPREAD>, grid, block, lds, s, a); break;
-    case AL_SRC_INFO: HUAL_LAUNCH(0.0, 44.0 * a.N * a.ld, al_score_kernel<AL_SRC_INFO>, grid, block, lds, s, a); break;
+    case AL_SRC_PAIR: HUAL_LAUNCH(0.0, 40.0 * a.set.N * a.set.ld, al_score_kernel<AL_SRC_PAIR>, grid, block, lds, s, a); break;
+    case AL_SRC_SPREAD: HUAL_LAUNCH(0.0, 44.0 * a.set.N * a.set.ld, al_score_kernel<AL_SRC_SPREAD>, grid, block, lds, s, a); break;
+    case AL_SRC_INFO: HUAL_LAUNCH(0.0, 44.0 * a.set.N * a.set.ld, al_score_kernel<AL_SRC_INFO>, grid, block, lds, s, a); break;
   }
   HUAL_CHECK_HIP(hipGetLastError());
   return 0;
@@ -580,11 +425,11 @@ int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s) {
 }
 
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s) {
-  HUAL_REQUIRE(a.sprob && a.eprob && a.vlen && a.tlen && a.ap_off && a.old_idx && a.new_idx, "al_renew: null pointer");
-  HUAL_REQUIRE(a.ld >= 2 && a.ld <= HUAL_AL_MAX_T, "al_renew: need 2 <= ld <= 1024");
+  HUAL_REQUIRE(a.sprob && a.eprob && a.set.vlen && a.set.tlen && a.set.ap_off && a.old_idx && a.new_idx, "al_renew: null pointer");
+  HUAL_REQUIRE(a.set.ld >= 2 && a.set.ld <= HUAL_AL_MAX_T, "al_renew: need 2 <= ld <= 1024");
   if (nsel <= 0) return 0;
-  const int ldp = (a.ld + 1) & ~1;
-  HUAL_LAUNCH(0.0, 16.0 * nsel * a.ld, al_renew_kernel, dim3(nsel), dim3(AL_THREADS), 4 * ldp * sizeof(float) + 2 * ldp * sizeof(double),
+  const int ldp = (a.set.ld + 1) & ~1;
+  HUAL_LAUNCH(0.0, 16.0 * nsel * a.set.ld, al_renew_kernel, dim3(nsel), dim3(AL_THREADS), 4 * ldp * sizeof(float) + 2 * ldp * sizeof(double),
               s, a);
   HUAL_CHECK_HIP(hipGetLastError());
   return 0;
@@ -598,9 +443,7 @@ namespace {
 AlScoreArgs score_args(const hual_al_set* set, const float* s0, const float* e0, float coff_uncert, float* sprob, float* eprob,
                               double* uncert_frame, float* uncert_video, int32_t* observe_point) {
   AlScoreArgs a{};
-  a.ld = set->ld; a.N = set->N; a.vlen = set->vlen; a.tlen = set->tlen;
-  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos;
-  a.s0 = s0; a.e0 = e0; a.coff_uncert = coff_uncert;
+  a.set = *set; a.s0 = s0; a.e0 = e0; a.coff_uncert = coff_uncert;
   a.sprob = sprob; a.eprob = eprob; a.uncert_frame = uncert_frame; a.uncert_video = uncert_video; a.observe = observe_point;
   return a;
 }
@@ -677,23 +520,11 @@ int hual_al_mc_fold_info(const hual_al_bank* bank, const hual_al_info* info, con
   return fold(bank, info, ids, v_len, start_logits, end_logits, B, T_b, k, stream);
 }
 
-int hual_al_query(const hual_al_set* set, const float* s0, const float* e0, float* incl, float* gain, int32_t* query_point,
-                  float* query_gain, float* post_entropy, float* agree, void* stream) {
-  HUAL_REQUIRE(set, "hual_al_query: null set");
-  AlQueryArgs a{};
-  a.ld = set->ld; a.N = set->N; a.vlen = set->vlen; a.tlen = set->tlen;
-  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos;
-  a.s0 = s0; a.e0 = e0; a.incl = incl; a.gain = gain;
-  a.query_point = query_point; a.query_gain = query_gain; a.post_entropy = post_entropy; a.agree = agree;
-  return launch_al_query(a, (hipStream_t)stream);
-}
-
 int hual_al_renew(const hual_al_set* set, const int32_t* sel, int nsel, const float* sprob, const float* eprob,
                   const int32_t* old_idx, const double* coff6, int32_t* new_idx, void* stream) {
   HUAL_REQUIRE(set && coff6, "hual_al_renew: null pointer");
   AlRenewArgs a{};
-  a.sel = sel; a.sprob = sprob; a.eprob = eprob; a.ld = set->ld; a.vlen = set->vlen; a.tlen = set->tlen;
-  a.ap_off = set->ap_off; a.ap_idx = set->ap_idx; a.ap_pos = set->ap_pos; a.old_idx = old_idx; a.new_idx = new_idx;
+  a.sel = sel; a.sprob = sprob; a.eprob = eprob; a.set = *set; a.old_idx = old_idx; a.new_idx = new_idx;
   for (int k = 0; k < 6; ++k) a.coff[k] = coff6[k];
   return launch_al_renew(a, sel ? nsel : set->N, (hipStream_t)stream);
 }

@@ -14,9 +14,7 @@
 // adds terms of one sign in float64 in a fixed order (a lane takes every fourth term, the quad is folded by two shuffles): no difference
 // of prefix sums, no atomics, nothing grid wide.  At most v^3 / 2 additions for the full triangle.
 #pragma once
-#include "alpost.h"
-#include "common.h"
-#include "spanprob.h"
+#include "spanpost.h"
 
 constexpr int AM_QUAD = 4;      // lanes per frame
 
@@ -56,29 +54,5 @@ __device__ __forceinline__ void label_region(int sa, int ihi, int jlo, int sb, c
     }
     __syncthreads();                        // xh / xg are rewritten by the next step
     if (g <= e) H += (double)pe[e] * inv[e - g + 1];
-  }
-}
-
-// zf / za <- Z over the whole triangle and Z_A over the consistent set, the sums of al_query_kernel in its order: frame t's share is
-// p_e[t] times the sum of p_s over the frames <= t (of its segment); around a positive hull Z_A is the product of its start and end
-// masses.  Called by the whole workgroup; smd: 2 * SPAN_WAVES doubles of LDS scratch; its barriers publish what was written before it.
-__device__ __forceinline__ void posterior_masses(const int32_t* aidx, const int8_t* apos, int napn, int v, const ApHull& hull,
-                                                 const float* ps, const float* pe, double* smd, double& zf, double& za) {
-  const int t = threadIdx.x;
-  zf = 0.0; za = 0.0;
-  if (t < v) {
-    const ApSegment sg = ap_segment(aidx, apos, napn, v, t);
-    double below = 0.0, seg = 0.0;
-    for (int i = 0; i < sg.sa; ++i) below += (double)ps[i];
-    for (int i = sg.sa; i <= t; ++i) seg += (double)ps[i];
-    zf = (double)pe[t] * (below + seg);
-    za = sg.closed ? 0.0 : (double)pe[t] * seg;
-  }
-  block_reduce<BlockSumD, SPAN_WAVES>(zf, za, smd);
-  if (hull.npos > 0) {                      // starts in (negL, lo] x ends in [hi, negR)
-    double S = 0.0, E = 0.0;
-    for (int i = hull.negL + 1; i <= hull.lo; ++i) S += (double)ps[i];
-    for (int j = hull.hi; j < min(hull.negR, v); ++j) E += (double)pe[j];
-    za = hull.inside ? 0.0 : S * E;
   }
 }

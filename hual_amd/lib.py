@@ -365,6 +365,43 @@ def al_score(aset, s0, e0, coff_uncert, out, pair=None, bank=None, info=None, K=
 AL_QUERY_MAX_T = 256      # the span kernels' row length (csrc/spanprob.h)
 
 
+def _span_inputs(who, aset, s0, e0, tlen):
+    """the gate of every span-posterior launch: tlen, the set's row lengths on the HOST, none above AL_QUERY_MAX_T; s0 / e0, the
+    deterministic logits, contiguous f32 [N, ld] on one device -> (N, ld, that device)"""
+    import numpy as np
+    import torch
+    N, ld = int(aset.N), int(aset.ld)
+    tl = np.asarray(tlen)
+    if tl.size != N:
+        raise HualError('%s: tlen must hold N = %d row lengths' % (who, N))
+    if int(tl.max()) > AL_QUERY_MAX_T:
+        raise HualError('%s: a row of %d frames - the span posterior handles at most %d' % (who, int(tl.max()), AL_QUERY_MAX_T))
+    for x in (s0, e0):
+        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous() or x.device != s0.device:
+            raise HualError('%s: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d] on one device' % (who, N, ld))
+    return N, ld, s0.device
+
+
+def _span_sel(who, sel, dev):
+    """sel: device i32 [nsel] sample ids or None -> nsel, 0 without a list"""
+    import torch
+    if sel is None:
+        return 0
+    if sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < 1 or not sel.is_contiguous() or sel.device != dev:
+        raise HualError('%s: sel must be a contiguous, non-empty int32 [nsel] on the logits\' device' % who)
+    return int(sel.numel())
+
+
+def _span_out(who, out, spec, optional, dev):
+    """out: the caller's tuple of tensors to write into, against spec = [(name, shape, dtype)]; only the names in `optional` may be None"""
+    names = ', '.join(name for name, _, _ in spec)
+    if len(out) != len(spec) or any(o is None and name not in optional for o, (name, _, _) in zip(out, spec)):
+        raise HualError('%s: out is (%s)%s' % (who, names, '; only %s may be None' % ' / '.join(optional) if optional else ''))
+    for o, (name, shape, dt) in zip(out, spec):
+        if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
+            raise HualError('%s: %s must be a contiguous %s %s on the logits\' device' % (who, name, str(dt).replace('torch.', ''), list(shape)))
+
+
 def al_query(aset, s0, e0, tlen, frames=True, out=None):
     """the posterior over spans of every sample of the hual_al_set `aset` given its answered active points, and the frame whose answer
     carries most information about the span (hual_al_query), one launch enqueued on the current stream.  s0 / e0: the deterministic
@@ -373,29 +410,15 @@ def al_query(aset, s0, e0, tlen, frames=True, out=None):
     -> (incl, gain, query_point, query_gain, post_entropy, agree): f32 [N, ld] twice (None with frames=False: only the per-sample outputs
     are written), i32 [N], f32 [N] three times.  out: such a tuple of contiguous device tensors to write into instead (incl / gain may be
     None); columns beyond a row's tlen keep what they held (0 in tensors allocated here)."""
-    import numpy as np
     import torch
-    N, ld = int(aset.N), int(aset.ld)
-    tl = np.asarray(tlen)
-    if tl.size != N:
-        raise HualError('al_query: tlen must hold N = %d row lengths' % N)
-    if int(tl.max()) > AL_QUERY_MAX_T:
-        raise HualError('al_query: a row of %d frames - the span posterior handles at most %d' % (int(tl.max()), AL_QUERY_MAX_T))
-    for x in (s0, e0):
-        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous():
-            raise HualError('al_query: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d]' % (N, ld))
-    dev = s0.device
+    N, ld, dev = _span_inputs('al_query', aset, s0, e0, tlen)
     if out is None:
         out = (torch.zeros(N, ld, device=dev) if frames else None, torch.zeros(N, ld, device=dev) if frames else None,
                torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev))
     else:
-        if len(out) != 6 or any(o is None for o in out[2:]):
-            raise HualError('al_query: out is (incl, gain, query_point, query_gain, post_entropy, agree); only incl / gain may be None')
-        shapes = ((N, ld), (N, ld), (N,), (N,), (N,), (N,))
-        for i, (o, shape) in enumerate(zip(out, shapes)):
-            dt = torch.int32 if i == 2 else torch.float32
-            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
-                raise HualError('al_query: out tensors must be contiguous, on the logits\' device, f32 [N, ld] / [N] (query_point: i32 [N])')
+        f32 = torch.float32
+        _span_out('al_query', out, [('incl', (N, ld), f32), ('gain', (N, ld), f32), ('query_point', (N,), torch.int32),
+                                    ('query_gain', (N,), f32), ('post_entropy', (N,), f32), ('agree', (N,), f32)], ('incl', 'gain'), dev)
     check(load().hual_al_query(ctypes.byref(aset), ptr(s0), ptr(e0), *[ptr(o) for o in out], stream_ptr()))
     return tuple(out)
 
@@ -409,23 +432,9 @@ def al_mbr_label(aset, s0, e0, tlen, sel=None, old_idx=None, out=None):
     -> (new_idx i32 [N, 2], conf f32 [N], old_conf f32 [N] or None).  out: such a tuple of contiguous device tensors to write into
     instead (old_conf None exactly when old_idx is).  Only the rows of selected samples are written: the others keep what they held
     (-1 in tensors allocated here, the value of a row that gives no label)."""
-    import numpy as np
     import torch
-    N, ld = int(aset.N), int(aset.ld)
-    tl = np.asarray(tlen)
-    if tl.size != N:
-        raise HualError('al_mbr_label: tlen must hold N = %d row lengths' % N)
-    if int(tl.max()) > AL_QUERY_MAX_T:
-        raise HualError('al_mbr_label: a row of %d frames - the span posterior handles at most %d' % (int(tl.max()), AL_QUERY_MAX_T))
-    for x in (s0, e0):
-        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous() or x.device != s0.device:
-            raise HualError('al_mbr_label: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d] on one device' % (N, ld))
-    dev = s0.device
-    nsel = N
-    if sel is not None:
-        if sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < 1 or not sel.is_contiguous() or sel.device != dev:
-            raise HualError('al_mbr_label: sel must be a contiguous, non-empty int32 [nsel] on the logits\' device')
-        nsel = int(sel.numel())
+    N, ld, dev = _span_inputs('al_mbr_label', aset, s0, e0, tlen)
+    nsel = _span_sel('al_mbr_label', sel, dev) or N
     if old_idx is not None and (old_idx.dtype != torch.int32 or tuple(old_idx.shape) != (N, 2) or not old_idx.is_contiguous()
                                 or old_idx.device != dev):
         raise HualError('al_mbr_label: old_idx must be contiguous int32 [N, 2] on the logits\' device')
@@ -435,9 +444,8 @@ def al_mbr_label(aset, s0, e0, tlen, sel=None, old_idx=None, out=None):
     else:
         if len(out) != 3 or out[0] is None or out[1] is None or (out[2] is None) != (old_idx is None):
             raise HualError('al_mbr_label: out is (new_idx, conf, old_conf); old_conf is None exactly when old_idx is')
-        for o, shape, dt in zip(out, ((N, 2), (N,), (N,)), (torch.int32, torch.float32, torch.float32)):
-            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
-                raise HualError('al_mbr_label: out tensors must be contiguous, on the logits\' device, i32 [N, 2], f32 [N], f32 [N]')
+        _span_out('al_mbr_label', out, [('new_idx', (N, 2), torch.int32), ('conf', (N,), torch.float32), ('old_conf', (N,), torch.float32)],
+                  ('old_conf',), dev)
     check(load().hual_al_mbr_label(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, ptr(old_idx), ptr(out[0]), ptr(out[1]),
                                    ptr(out[2]), stream_ptr()))
     return tuple(out)
@@ -458,23 +466,9 @@ def al_label_gain(aset, s0, e0, tlen, sel=None, cand=None, frames=True, out=None
     contiguous device tensors to write into instead (gain may be None).  Only the rows of selected samples are written, and of gain only
     the columns below a row's tlen: the rest keeps what it held (gain 0, ask_point -1, ask_gain and value -1 in tensors allocated here -
     the values of a row that has no answer to give)."""
-    import numpy as np
     import torch
-    N, ld = int(aset.N), int(aset.ld)
-    tl = np.asarray(tlen)
-    if tl.size != N:
-        raise HualError('al_label_gain: tlen must hold N = %d row lengths' % N)
-    if int(tl.max()) > AL_QUERY_MAX_T:
-        raise HualError('al_label_gain: a row of %d frames - the span posterior handles at most %d' % (int(tl.max()), AL_QUERY_MAX_T))
-    for x in (s0, e0):
-        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous() or x.device != s0.device:
-            raise HualError('al_label_gain: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d] on one device' % (N, ld))
-    dev = s0.device
-    nsel = N
-    if sel is not None:
-        if sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < 1 or not sel.is_contiguous() or sel.device != dev:
-            raise HualError('al_label_gain: sel must be a contiguous, non-empty int32 [nsel] on the logits\' device')
-        nsel = int(sel.numel())
+    N, ld, dev = _span_inputs('al_label_gain', aset, s0, e0, tlen)
+    nsel = _span_sel('al_label_gain', sel, dev) or N
     M = 0
     if cand is not None:
         if (cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != N or not 1 <= cand.shape[1] <= AL_GAIN_MAX_CAND
@@ -485,11 +479,8 @@ def al_label_gain(aset, s0, e0, tlen, sel=None, cand=None, frames=True, out=None
         out = (torch.zeros(N, ld, device=dev) if frames else None, torch.full((N,), -1, dtype=torch.int32, device=dev),
                torch.full((N,), -1.0, device=dev), torch.full((N,), -1.0, device=dev))
     else:
-        if len(out) != 4 or any(o is None for o in out[1:]):
-            raise HualError('al_label_gain: out is (gain, ask_point, ask_gain, value); only gain may be None')
-        for o, shape, dt in zip(out, ((N, ld), (N,), (N,), (N,)), (torch.float32, torch.int32, torch.float32, torch.float32)):
-            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
-                raise HualError('al_label_gain: out tensors must be contiguous, on the logits\' device, f32 [N, ld], i32 [N], f32 [N], f32 [N]')
+        _span_out('al_label_gain', out, [('gain', (N, ld), torch.float32), ('ask_point', (N,), torch.int32), ('ask_gain', (N,), torch.float32),
+                                         ('value', (N,), torch.float32)], ('gain',), dev)
     check(load().hual_al_label_gain(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, ptr(cand), M, *[ptr(o) for o in out],
                                     stream_ptr()))
     return tuple(out)
@@ -503,25 +494,12 @@ def al_span_marginals(aset, s0, e0, tlen, out=None):
     -> (y_start f32 [N, ld], y_end f32 [N, ld], status i32 [N]): status 1 = a live row, 0 = a poisoned or contradictory one, whose
     columns are 0.  out: such a tuple of contiguous device tensors to write into instead; columns beyond a row's tlen keep what they
     held (0 in tensors allocated here)."""
-    import numpy as np
     import torch
-    N, ld = int(aset.N), int(aset.ld)
-    tl = np.asarray(tlen)
-    if tl.size != N:
-        raise HualError('al_span_marginals: tlen must hold N = %d row lengths' % N)
-    if int(tl.max()) > AL_QUERY_MAX_T:
-        raise HualError('al_span_marginals: a row of %d frames - the span posterior handles at most %d' % (int(tl.max()), AL_QUERY_MAX_T))
-    for x in (s0, e0):
-        if x.dtype != torch.float32 or tuple(x.shape) != (N, ld) or not x.is_contiguous() or x.device != s0.device:
-            raise HualError('al_span_marginals: s0 / e0 must be contiguous float32 [N, ld] = [%d, %d] on one device' % (N, ld))
-    dev = s0.device
+    N, ld, dev = _span_inputs('al_span_marginals', aset, s0, e0, tlen)
     if out is None:
         out = (torch.zeros(N, ld, device=dev), torch.zeros(N, ld, device=dev), torch.zeros(N, dtype=torch.int32, device=dev))
     else:
-        if len(out) != 3 or any(o is None for o in out):
-            raise HualError('al_span_marginals: out is (y_start, y_end, status)')
-        for o, shape, dt in zip(out, ((N, ld), (N, ld), (N,)), (torch.float32, torch.float32, torch.int32)):
-            if o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev:
-                raise HualError('al_span_marginals: out tensors must be contiguous, on the logits\' device, f32 [N, ld] twice and i32 [N]')
+        _span_out('al_span_marginals', out, [('y_start', (N, ld), torch.float32), ('y_end', (N, ld), torch.float32), ('status', (N,), torch.int32)],
+                  (), dev)
     check(load().hual_al_span_marginals(ctypes.byref(aset), ptr(s0), ptr(e0), *[ptr(o) for o in out], stream_ptr()))
     return tuple(out)
