@@ -167,7 +167,8 @@ def test_dual_attn_fwd_bwd(shape, layer):
 
 
 # csrc/cqwide.hip (queries of at most 32 words): clips of more than 128 frames (16 waves, two 128-column blocks: both full, a ragged
-# second block, three words / 32 words); the shapes beyond it - queries of more than 32 words - run the staged kernels of csrc/cq.hip
+# second block, three words / 32 words); T 64 with 40 words runs its 64-short-row form (`<8, 64>`); the shapes beyond both run the
+# global-operand kernels of csrc/cq.hip (which form serves which shape, and a case per form: test_gpu_cq_forms.py)
 CQ_WIDE_SHAPES = [dict(B=3, T=256, L=20, C=4, seed=21, max_vlen=256), dict(B=2, T=170, L=32, C=4, seed=22, max_vlen=192),
                   dict(B=9, T=129, L=3, C=4, seed=23, max_vlen=160), dict(B=5, T=100, L=30, C=4, seed=33, max_vlen=100),
                   dict(B=3, T=64, L=40, C=4, seed=24, max_vlen=64),

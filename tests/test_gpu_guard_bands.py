@@ -36,7 +36,11 @@ class Arena:
 
 
 SHAPES = [dict(B=3, T=20, L=6, C=5, vdim=64, max_vlen=32), dict(B=5, T=131, L=33, C=9, vdim=320, max_vlen=160), dict(B=2, T=256, L=20, C=8, vdim=64, max_vlen=256),
-          dict(B=7, T=17, L=3, C=4, vdim=64, max_vlen=32), dict(B=4, T=65, L=40, C=22, vdim=64, max_vlen=128), dict(B=1, T=5, L=3, C=4, vdim=64, max_vlen=16)]
+          dict(B=7, T=17, L=3, C=4, vdim=64, max_vlen=32), dict(B=4, T=65, L=40, C=22, vdim=64, max_vlen=128), dict(B=1, T=5, L=3, C=4, vdim=64, max_vlen=16),
+          # queries longer than the clip / beyond the wide context-query kernels: the staged form, and the float32 form with its score matrices in
+          # LDS on both passes, and in LDS forward / in global memory backward (tests/test_gpu_cq_forms.py)
+          dict(B=3, T=12, L=20, C=5, vdim=64, max_vlen=32), dict(B=2, T=64, L=96, C=5, vdim=64, max_vlen=96),
+          dict(B=2, T=100, L=70, C=5, vdim=64, max_vlen=100)]
 
 
 @pytest.mark.parametrize('variant', ['f32', 'bf16 feed', 'gumbel'])

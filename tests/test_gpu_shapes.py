@@ -131,8 +131,8 @@ def test_long_clips_with_long_queries():
 
 
 def test_long_queries():
-    """L = 40 words (> 32): the staged context-query kernels take their general softmax branches (rows / columns longer than
-    a 32-lane half) - T + L still within their 160 padded rows"""
+    """L = 40 words (> 32) against T = 64 frames: the 64-short-row wide context-query kernels (csrc/cqwide.hip `<8, 64>`; this shape ran the
+    staged kernels of csrc/cq.hip until those covered 33-64 words - the staged kernels' own cases are in test_gpu_cq_forms.py)"""
     case = pu.make_case(B=3, T=64, L=40, C=5, seed=47, max_vlen=64)
     _check_all(case, 0.2)
 
