@@ -55,6 +55,11 @@ hard pseudo-label alone but, for every sample with an answer, on its blend (weig
 posterior, this round's answers included (LabelUpdater.span_marginals, one hual_al_span_marginals launch over the whole set;
 update_labels(soft_out=) hands them out; DeviceDataset.set_soft_labels feeds them to the assembly launch).  Off by default: every
 launch, record and result is then what it was.
+
+An annotator who errs (the reference simulates a perfect one): update_labels(answer_noise=eps) reads all of the above from the span
+posterior under answers that are wrong with probability eps - the product form of logits tilted by the answers (LabelUpdater.tilt, one
+hual_al_noisy_tilt launch; the gain by hual_al_label_gain_noisy), on which no answer is a hard constraint and no sample contradictory;
+annotator_flip=(rate, rng) simulates such an annotator.  Off by default: every launch, record and result is then what it was.
 """
 import ctypes
 import math
@@ -467,6 +472,17 @@ def _round_half_even_index(t, duration, vlen):
     return round(t / duration * (vlen - 1))
 
 
+def check_noise(eps):
+    """the annotator's error probability as the launches take it: a float32 in (0, 0.5], returned widened to a python float"""
+    try:
+        e = float(np.float32(eps))
+    except (TypeError, ValueError):
+        e = float('nan')
+    if isinstance(eps, bool) or not 0.0 < e <= 0.5:
+        raise ValueError('the answer noise eps must lie in (0, 0.5]')
+    return e
+
+
 class LabelUpdater:
     """Device-side state of one update_label round: the logits of the results pkl as [N, ld] matrices, the active
     points as CSR.  score() and renew() are one launch each.
@@ -566,42 +582,97 @@ class LabelUpdater:
         p = lib.ptr
         self.set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, p(self.ap_off).value,
                                    p(self.ap_idx).value, p(self.ap_pos).value)
+        self.tilt_eps = None                                     # (a tilt holds the answers it was made with)
+
+    def tilt(self, eps):
+        """the set's answers folded into the deterministic logits under an annotator who errs with probability eps in (0, 0.5]
+        (hual_al_noisy_tilt, one launch over the whole set).  Leaves s_t, e_t (f32 [N, ld], the tilted rows), log_evidence (f32 [N]:
+        ln P(the answers | the model, eps), NaN on a poisoned row), free_set (a hual_al_set over the same vlen / tlen WITHOUT answers:
+        what the family's launches take beside the tilted rows) and tilt_eps; set_active_points invalidates them."""
+        eps = check_noise(eps)
+        self.s_t, self.e_t, self.log_evidence = lib.al_noisy_tilt(self.set, self._s0, self._e0, self.tlen_h, eps)
+        if getattr(self, '_free', None) is None:
+            self._free = (torch.zeros(self.N + 1, dtype=torch.int32, device=self.dev), torch.zeros(1, dtype=torch.int32, device=self.dev),
+                          torch.zeros(1, dtype=torch.int8, device=self.dev))
+        p = lib.ptr
+        self.free_set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, *[p(x).value for x in self._free])
+        self.tilt_eps = eps
+
+    def _rows(self, noise):
+        """(set, s, e) a launch of the family reads: the updater's own, or under noise = eps the set without answers and the rows
+        tilted by eps (tilted here unless they already are)"""
+        if noise is None:
+            return self.set, self._s0, self._e0
+        if self.tilt_eps != check_noise(noise):
+            self.tilt(noise)
+        return self.free_set, self.s_t, self.e_t
 
     def score(self, coff_uncert):
         lib.al_score(self.set, self._s0, self._e0, coff_uncert, (self.sprob, self.eprob, self.uncert_frame, self.uncert_video, self.observe),
                      pair=self.logits[2:] if self.logits is not None else None, bank=self.bank_c,
                      info=self.bank.info_c if self.bank is not None else None, K=self.K, stat=self.stat)
 
-    def query(self, frames=True):
+    def query(self, frames=True, noise=None):
         """the span posterior given the set's answered active points and the frame of most expected information gain (hual_al_query,
         one launch) on the updater's set and deterministic logits - of the records or of the bank.  Leaves incl, gain (f32 [N, ld];
-        None with frames=False), query_point (i32 [N]), query_gain, post_entropy and agree (f32 [N]) as device tensors."""
+        None with frames=False), query_point (i32 [N]), query_gain, post_entropy and agree (f32 [N]) as device tensors.
+        noise=eps: the posterior under an annotator who errs with probability eps - the same launch on the tilted rows (tilt()) and
+        the set without answers.  gain / query_gain are then the information a NOISY answer carries, h2(eps + (1 - 2 eps) q) - h2(eps)
+        bits, from incl in float64, stored as float32 (frames=True is needed); query_point stays the kernel's - the same maximiser,
+        q nearest 1/2 -; agree is None: log_evidence (tilt()) is the quantity to read."""
+        if noise is not None and not frames:
+            raise ValueError('query(noise=) computes the gain of a noisy answer from incl: it needs frames=True')
+        aset, s, e = self._rows(noise)
         (self.incl, self.gain, self.query_point, self.query_gain, self.post_entropy,
-         self.agree) = lib.al_query(self.set, self._s0, self._e0, self.tlen_h, frames=frames)
+         self.agree) = lib.al_query(aset, s, e, self.tlen_h, frames=frames)
+        if noise is not None:
+            eps = check_noise(noise)
 
-    def label_gain(self, frames=True, cand=None):
+            def h2(x):
+                x = x.clamp(1e-300, 1.0)
+                y = (1.0 - x).clamp(1e-300, 1.0)
+                return -(x * torch.log2(x) + y * torch.log2(y))
+            ch = (h2(eps + (1.0 - 2.0 * eps) * self.incl.double()) - h2(torch.tensor(eps, dtype=torch.float64, device=self.dev))).clamp_min(0.0)
+            live = self.query_point >= 0
+            at = ch.gather(1, self.query_point.clamp_min(0).long()[:, None])[:, 0]
+            self.gain = torch.where(live[:, None], ch, torch.zeros_like(ch)).float()
+            self.query_gain = torch.where(live, at, torch.full_like(at, -1.0)).float()
+            self.agree = None
+
+    def label_gain(self, frames=True, cand=None, noise=None):
         """per frame, the tIoU the minimum-Bayes-risk label is expected to gain from the frame's answer under the span posterior given
         the set's answered active points (hual_al_label_gain, one launch over the whole set) on the updater's set and deterministic
         logits - of the records or of the bank, as query().  cand: device i32 [N, M], the only frames to evaluate (None: every frame).
         Leaves gain (f32 [N, ld]; None with frames=False; in place of the row of bits query() leaves under that name), ask_point
-        (i32 [N]), ask_gain and label_value (f32 [N]) as device tensors."""
-        (self.gain, self.ask_point, self.ask_gain,
-         self.label_value) = lib.al_label_gain(self.set, self._s0, self._e0, self.tlen_h, cand=cand, frames=frames)
+        (i32 [N]), ask_gain and label_value (f32 [N]) as device tensors.
+        noise=eps: the gain from a NOISY answer (hual_al_label_gain_noisy, one launch) on the rows tilted by eps (tilt())."""
+        if noise is None:
+            out = lib.al_label_gain(self.set, self._s0, self._e0, self.tlen_h, cand=cand, frames=frames)
+        else:
+            aset, s, e = self._rows(noise)
+            out = lib.al_label_gain_noisy(aset, s, e, self.tlen_h, check_noise(noise), cand=cand, frames=frames)
+        self.gain, self.ask_point, self.ask_gain, self.label_value = out
 
-    def span_marginals(self):
+    def span_marginals(self, noise=None):
         """the start and end marginals of the span posterior given the set's answered active points (hual_al_span_marginals, one launch
         over the whole set) on the updater's set and deterministic logits - of the records or of the bank, as query().  Leaves y_start,
-        y_end (f32 [N, ld]) and marg_status (i32 [N]; 1 = live) as device tensors."""
-        self.y_start, self.y_end, self.marg_status = lib.al_span_marginals(self.set, self._s0, self._e0, self.tlen_h)
+        y_end (f32 [N, ld]) and marg_status (i32 [N]; 1 = live) as device tensors.
+        noise=eps: the marginals of the posterior under an annotator who errs with probability eps - the same launch on the rows
+        tilted by eps (tilt()) and the set without answers."""
+        aset, s, e = self._rows(noise)
+        self.y_start, self.y_end, self.marg_status = lib.al_span_marginals(aset, s, e, self.tlen_h)
 
-    def mbr_label(self, sel, old_idx):
+    def mbr_label(self, sel, old_idx, noise=None):
         """the minimum-Bayes-risk pseudo-label of the samples `sel` (sample ids, numpy) under the span posterior given the set's
         answered active points (hual_al_mbr_label, one launch) on the updater's set and deterministic logits - of the records or of the
         bank, as query().  old_idx: int [N, 2].  Returns numpy (new_idx i32 [N, 2], conf f32 [N], old_conf f32 [N]): the label, its
-        expected tIoU and the old span's; rows outside `sel`, and rows that give no label, hold -1."""
+        expected tIoU and the old span's; rows outside `sel`, and rows that give no label, hold -1.
+        noise=eps: the label under an annotator who errs with probability eps - the same launch on the rows tilted by eps (tilt())
+        and the set without answers: any span of the clip, and only a poisoned row gives none."""
         sel_d = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
         old_d = torch.from_numpy(np.ascontiguousarray(old_idx, dtype=np.int32)).to(self.dev)
-        new_d, conf, old_conf = lib.al_mbr_label(self.set, self._s0, self._e0, self.tlen_h, sel=sel_d, old_idx=old_d)
+        aset, s, e = self._rows(noise)
+        new_d, conf, old_conf = lib.al_mbr_label(aset, s, e, self.tlen_h, sel=sel_d, old_idx=old_d)
         return new_d.cpu().numpy(), conf.cpu().numpy(), old_conf.cpu().numpy()
 
     def renew(self, sel, old_idx, coff):
@@ -629,7 +700,8 @@ def span_risk(last_prop):
 
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
-                  rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None):
+                  rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
+                  answer_noise=None, annotator_flip=None):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -659,9 +731,35 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     that are not selected count too): 'y1', 'y2' (device f32 [N, ld], the start / end marginals), 'live' (numpy bool [N]: the row gave
     marginals) and 'answered' (numpy bool [N]: at least one active point with a frame inside [0, v_len)).  Nothing else about the call
     changes, with any combination of the other switches.
+    answer_noise: None, or eps in (0, 0.5] - the span posterior then takes every answer as wrong with probability eps instead of as a
+    hard constraint (LabelUpdater.tilt: one launch per state of the answers, before and after this round's), so a wrong click neither
+    makes a row contradictory nor deletes the true span for good.  It is handed as noise=eps to whichever of observe_by='info_gain',
+    acquire_by='label_gain', renew_by='posterior' and soft_out are on - at least one must be.  The fallbacks stay: a row that still
+    gives no label (now only a poisoned one) takes the reference's route.  The debug dict gains 'log_evidence' (float32 [N]: ln P(every
+    answer so far, this round's included | the model, eps)); under noise there is no 'agree'.
+    annotator_flip: None, or (rate, numpy Generator) - a simulated annotator who errs: every answer of the round is flipped with
+    probability rate (one draw per selected sample, in selection order) before append_AP; the debug dict gains 'flipped' (bool [N]).
+    Independent of answer_noise: without it the hard rule meets the wrong answers.
     """
     if soft_out is not None and not isinstance(soft_out, dict):
         raise ValueError('soft_out: None or a dict to receive y1, y2, live and answered')
+    noise = None
+    if answer_noise is not None:
+        try:
+            noise = check_noise(answer_noise)
+        except ValueError:
+            raise ValueError('answer_noise: None or an error probability in (0, 0.5]') from None
+        if observe_by != 'info_gain' and acquire_by != 'label_gain' and renew_by != 'posterior' and soft_out is None:
+            raise ValueError("answer_noise changes the span posterior: switch on one of its readers (observe_by='info_gain', "
+                             "acquire_by='label_gain', renew_by='posterior', soft_out)")
+    if annotator_flip is not None:
+        ok = isinstance(annotator_flip, (tuple, list)) and len(annotator_flip) == 2 and isinstance(annotator_flip[1], np.random.Generator)
+        try:
+            ok = ok and 0.0 <= float(annotator_flip[0]) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('annotator_flip: None or (rate in [0, 1], numpy.random.Generator)')
     if rank_by not in RANK_BY:
         raise ValueError("rank_by: 'uncert_video' or 'span_risk'")
     if observe_by not in OBSERVE_BY:
@@ -692,11 +790,11 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     observe = up.observe.cpu().numpy()
     ask = observe
     if observe_by == 'info_gain':
-        up.query(frames=return_debug)                            # (before set_active_points: on the answers of the earlier rounds)
+        up.query(frames=return_debug or noise is not None, noise=noise)      # (before set_active_points: on the answers of the earlier rounds)
         ask = np.where(up.query_gain.cpu().numpy() > 0, up.query_point.cpu().numpy(), observe)
     order = np.argsort(uv if risk is None else risk, kind='stable')      # sorted(key=uncert_video), ties in sample order
     if acquire_by == 'label_gain':
-        up.label_gain(frames=return_debug)                       # (before set_active_points: on the answers of the earlier rounds)
+        up.label_gain(frames=return_debug, noise=noise)          # (before set_active_points: on the answers of the earlier rounds)
         ask_gain = up.ask_gain.cpu().numpy()
         ask = np.where(ask_gain > 0, up.ask_point.cpu().numpy(), observe)
         order = np.argsort(-ask_gain, kind='stable')             # largest gain first, ties in sample order; rows at 0 and -1 last
@@ -705,18 +803,23 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     gt_idx = np.array([[_round_half_even_index(t, data_gt[i][1], int(vlen[i])) for t in data_gt[i][2]] for i in range(N)])
     old_idx = np.array([[_round_half_even_index(t, data_old[i][1], int(vlen[i])) for t in data_old[i][2]] for i in range(N)])
     # append_AP (utils_hual.py:133-139): the annotator answers "is the observed frame inside the ground-truth span?"
+    flipped = np.zeros(N, dtype=bool)
     for i in sel:
         p = int(ask[i])
         is_pos = gt_idx[i, 0] <= p <= gt_idx[i, 1]
+        if annotator_flip is not None and annotator_flip[1].random() < float(annotator_flip[0]):      # the simulated annotator errs
+            is_pos, flipped[i] = not is_pos, True
         data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
         aps[i].append((p, bool(is_pos)))
     up.set_active_points(aps)
+    if noise is not None:
+        up.tilt(noise)                                           # (this round's answers included: what the launches below read)
     if soft_out is not None:
-        up.span_marginals()
+        up.span_marginals(noise=noise)
         soft_out.update(y1=up.y_start, y2=up.y_end, live=up.marg_status.cpu().numpy() == 1,
                         answered=np.array([any(0 <= f < int(vlen[i]) for f, _ in aps[i]) for i in range(N)], dtype=bool))
     if renew_by == 'posterior':
-        new_idx, label_conf, old_conf = up.mbr_label(sel, old_idx)
+        new_idx, label_conf, old_conf = up.mbr_label(sel, old_idx, noise=noise)
         by_posterior = np.zeros(N, dtype=bool)
         by_posterior[sel] = new_idx[sel, 0] >= 0
         rest = sel[~by_posterior[sel]]                           # no label: the reference's renew for just those
@@ -735,11 +838,17 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
             dbg['span_risk'] = risk
         if observe_by == 'info_gain':
             dbg.update(query_point=up.query_point.cpu().numpy(), query_gain=up.query_gain.cpu().numpy(),
-                       post_entropy=up.post_entropy.cpu().numpy(), agree=up.agree.cpu().numpy(), observe_used=ask)
+                       post_entropy=up.post_entropy.cpu().numpy(), observe_used=ask)
+            if noise is None:
+                dbg['agree'] = up.agree.cpu().numpy()
         if acquire_by == 'label_gain':
             dbg.update(ask_point=up.ask_point.cpu().numpy(), ask_gain=ask_gain, label_value=up.label_value.cpu().numpy(), observe_used=ask)
         if renew_by == 'posterior':
             dbg.update(label_conf=label_conf, old_conf=old_conf, renewed_by_posterior=by_posterior)
+        if noise is not None:
+            dbg['log_evidence'] = up.log_evidence.cpu().numpy()
+        if annotator_flip is not None:
+            dbg['flipped'] = flipped
         return data_old, dbg
     return data_old
 
@@ -759,7 +868,8 @@ def labels_from_times(data, vlens):
 
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
-              observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None):
+              observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
+              annotator_flip=None):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -775,6 +885,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     observe_by: the frame the round's label update asks the annotator about (update_labels).
     renew_by: how the round's label update derives the new pseudo-labels (update_labels).
     acquire_by: how the round's label update chooses the samples and frames it asks about (update_labels).
+    answer_noise / annotator_flip: the error probability the round's span posterior grants the annotator, and a simulated annotator
+    who errs (update_labels).
     soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
     blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
     DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
@@ -799,7 +911,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     prev = bank if bank is not None and bank.K >= 2 else None
     new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
                              mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
-                             soft_out=soft) if rank == 0 else None
+                             soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip) if rank == 0 else None
     new_data = hdist.broadcast_object(new_data)
     if soft is not None:
         weighted = soft['live'] & soft['answered']

@@ -169,6 +169,8 @@ def load():
     lib.hual_assemble_batch.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_carry.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.hual_al_span_marginals.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp]
+    lib.hual_al_noisy_tilt.argtypes = [P(hual_al_set), vp, vp, f32, vp, vp, vp, vp]
+    lib.hual_al_label_gain_noisy.argtypes = [P(hual_al_set), vp, vp, f32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_soft.argtypes = lib.hual_assemble_batch_carry.argtypes[:-1] + [P(hual_soft_labels), vp]
     lib.hual_assemble_batch_cursor_soft.argtypes = lib.hual_assemble_batch_cursor.argtypes[:-1] + [P(hual_soft_labels), vp]
     _lib = lib
@@ -454,6 +456,17 @@ def al_mbr_label(aset, s0, e0, tlen, sel=None, old_idx=None, out=None):
 AL_GAIN_MAX_CAND = 256      # candidate frames per sample of hual_al_label_gain
 
 
+def _span_cand(who, cand, N, dev):
+    """cand: device i32 [N, M] candidate frames or None -> M, 0 without a list"""
+    import torch
+    if cand is None:
+        return 0
+    if (cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != N or not 1 <= cand.shape[1] <= AL_GAIN_MAX_CAND
+            or not cand.is_contiguous() or cand.device != dev):
+        raise HualError('%s: cand must be contiguous int32 [N, M], 1 <= M <= %d, on the logits\' device' % (who, AL_GAIN_MAX_CAND))
+    return int(cand.shape[1])
+
+
 def al_label_gain(aset, s0, e0, tlen, sel=None, cand=None, frames=True, out=None):
     """per frame, the temporal IoU the minimum-Bayes-risk label of the selected samples of the hual_al_set `aset` is expected to gain
     from the annotator's answer at that frame, under the span posterior given the answered active points (hual_al_label_gain), one
@@ -469,12 +482,7 @@ def al_label_gain(aset, s0, e0, tlen, sel=None, cand=None, frames=True, out=None
     import torch
     N, ld, dev = _span_inputs('al_label_gain', aset, s0, e0, tlen)
     nsel = _span_sel('al_label_gain', sel, dev) or N
-    M = 0
-    if cand is not None:
-        if (cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != N or not 1 <= cand.shape[1] <= AL_GAIN_MAX_CAND
-                or not cand.is_contiguous() or cand.device != dev):
-            raise HualError('al_label_gain: cand must be contiguous int32 [N, M], 1 <= M <= %d, on the logits\' device' % AL_GAIN_MAX_CAND)
-        M = int(cand.shape[1])
+    M = _span_cand('al_label_gain', cand, N, dev)
     if out is None:
         out = (torch.zeros(N, ld, device=dev) if frames else None, torch.full((N,), -1, dtype=torch.int32, device=dev),
                torch.full((N,), -1.0, device=dev), torch.full((N,), -1.0, device=dev))
@@ -502,4 +510,46 @@ def al_span_marginals(aset, s0, e0, tlen, out=None):
         _span_out('al_span_marginals', out, [('y_start', (N, ld), torch.float32), ('y_end', (N, ld), torch.float32), ('status', (N,), torch.int32)],
                   (), dev)
     check(load().hual_al_span_marginals(ctypes.byref(aset), ptr(s0), ptr(e0), *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)
+
+
+def al_noisy_tilt(aset, s0, e0, tlen, eps, out=None):
+    """the answers of the hual_al_set `aset` folded into its logits under an annotator who errs with probability eps in (0, 0.5]
+    (hual_al_noisy_tilt), one launch enqueued on the current stream: the span posterior given noisy answers is the product form of the
+    tilted rows on the whole triangle, so al_query, al_mbr_label, al_span_marginals (and al_label_gain_noisy) read it from them and a set
+    WITHOUT answers.  s0 / e0: the deterministic logits f32 [N, ld] on the device; tlen: the set's row lengths on the HOST - a row above
+    AL_QUERY_MAX_T frames is refused here, before the launch, as in al_query.
+    -> (s_t f32 [N, ld], e_t f32 [N, ld], log_evidence f32 [N]): the tilted logits and ln P(the answers | the model, eps), NaN on a
+    poisoned row (whose columns are raw copies).  out: such a tuple of contiguous device tensors to write into instead; columns beyond
+    a row's tlen keep what they held (0 in tensors allocated here)."""
+    import torch
+    N, ld, dev = _span_inputs('al_noisy_tilt', aset, s0, e0, tlen)
+    if out is None:
+        out = (torch.zeros(N, ld, device=dev), torch.zeros(N, ld, device=dev), torch.empty(N, device=dev))
+    else:
+        _span_out('al_noisy_tilt', out, [('s_t', (N, ld), torch.float32), ('e_t', (N, ld), torch.float32), ('log_evidence', (N,), torch.float32)],
+                  (), dev)
+    check(load().hual_al_noisy_tilt(ctypes.byref(aset), ptr(s0), ptr(e0), float(eps), *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)
+
+
+def al_label_gain_noisy(aset, s_t, e_t, tlen, eps, sel=None, cand=None, frames=True, out=None):
+    """al_label_gain under an annotator who errs with probability eps in (0, 0.5] (hual_al_label_gain_noisy), one launch enqueued on
+    the current stream: per frame, the temporal IoU the minimum-Bayes-risk label is expected to gain from a NOISY answer at that frame -
+    the answer re-weights the posterior instead of cutting it, and the label after it may be any span.  s_t / e_t: the TILTED logits of
+    al_noisy_tilt, f32 [N, ld] on the device; of `aset` only N, ld, vlen and tlen are read (the answers are in the rows); tlen, sel,
+    cand, frames, out and the returned (gain, ask_point, ask_gain, value) are al_label_gain's; value is al_mbr_label's conf on the same
+    rows and a set without answers."""
+    import torch
+    N, ld, dev = _span_inputs('al_label_gain_noisy', aset, s_t, e_t, tlen)
+    nsel = _span_sel('al_label_gain_noisy', sel, dev) or N
+    M = _span_cand('al_label_gain_noisy', cand, N, dev)
+    if out is None:
+        out = (torch.zeros(N, ld, device=dev) if frames else None, torch.full((N,), -1, dtype=torch.int32, device=dev),
+               torch.full((N,), -1.0, device=dev), torch.full((N,), -1.0, device=dev))
+    else:
+        _span_out('al_label_gain_noisy', out, [('gain', (N, ld), torch.float32), ('ask_point', (N,), torch.int32),
+                                               ('ask_gain', (N,), torch.float32), ('value', (N,), torch.float32)], ('gain',), dev)
+    check(load().hual_al_label_gain_noisy(ctypes.byref(aset), ptr(s_t), ptr(e_t), float(eps), ptr(sel), nsel, ptr(cand), M,
+                                          *[ptr(o) for o in out], stream_ptr()))
     return tuple(out)

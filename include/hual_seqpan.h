@@ -704,6 +704,54 @@ int hual_al_span_marginals(const hual_al_set* set, const float* s0, const float*
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same posterior under an annotator who errs (HUAL_ABI_VERSION unchanged: two new symbols, nothing else moved).  The launches above
+ * take every answer as a hard constraint: one wrong click makes a row contradictory, or silently deletes the true span from A.  Let every
+ * answer be wrong independently with probability eps, r = (1 - eps) / eps, and G(t) = (the positive answers at frames <= t) - (the
+ * negative answers at frames <= t), G(-1) = 0, duplicated answers counted once each (independent clicks).  The likelihood of the
+ * answers under the span (i, j) is eps^npos (1 - eps)^nneg r^(G(j) - G(i-1)), so
+ *   posterior(i, j)  ~  p_s(i) r^(-G(i-1)) * p_e(j) r^(G(j))  on the whole triangle i <= j < v:
+ * the product form of tilted logits with no constraint left.  hual_al_query, hual_al_mbr_label and hual_al_span_marginals read the noisy
+ * posterior from the tilted rows and a set without answers (ap_off all 0), as they are; no row is contradictory any more.
+ *
+ * hual_al_noisy_tilt: per sample n of the set, with T, v, p_s, p_e, w, Z and the ignored active points exactly as hual_al_query
+ * defines them and lam = (float)log((1.0 - (double)eps) / (double)eps) computed on the host:
+ *  - s_t f32 [N, ld]: s_t[n][i] = s0[n][i] - (float)G(i-1) * lam for i < v; e_t f32 [N, ld]: e_t[n][j] = e0[n][j] + (float)G(j) * lam
+ *    for j < v - one float32 product and one float32 subtraction / addition, each rounded on its own (no contraction); where the
+ *    count or lam is 0 the logit is copied (eps = 0.5 returns the input bit for bit).  Columns [v, T) are copied from the input,
+ *    columns [T, ld) are not touched.
+ *  - log_evidence f32 [N]: ln P(the answers | the model, eps) = ln(sum over i <= j < v of w(i,j) * prod_k lik_k(i,j)) - ln Z, lik_k =
+ *    1 - eps where answer k agrees with the span and eps where not, w and Z from the UNTILTED logits.  Float64, as sum_j b(j) sum_{i <=
+ *    j} a(i) with the powers of r carried as integer exponents against the row's maxima (64 answers at eps = 1e-6 do not overflow), sums
+ *    of terms of one sign in a fixed order, no atomics; stored as float32.  It takes the place of hual_al_query's agree as the measure
+ *    of how far the model and the annotator disagree, and its sum over a set is the likelihood a caller maximises to choose eps.
+ *  - a poisoned row (v < 1, a NaN logit at t < v, a Z that is not a positive finite number, or T > 256): columns [0, min(T, ld)) are
+ *    copied raw - the launches that read them poison the row again - and log_evidence is a quiet NaN.
+ * One launch over the whole set, one workgroup per sample.  Allocates nothing and does not synchronise: capturable in a hipGraph.
+ * Argument errors (a null pointer, N < 1, ld outside [2, 1024], eps outside (0, 0.5] or NaN) return HUAL_ERR_INVALID before any HIP
+ * call. */
+int hual_al_noisy_tilt(const hual_al_set* set, const float* s0, const float* e0, float eps, float* s_t, float* e_t, float* log_evidence,
+                       void* stream);
+
+/* hual_al_label_gain rebuilt for the noisy annotator: an answer re-weights the triangle instead of cutting it, and the label after it
+ * may be any span.  It reads N, ld, vlen and tlen of the set - the active points are NOT read: they are in the tilted rows s_t / e_t
+ * already - and p_s, p_e, w, Z of those rows as the family computes them.  Per selected sample and frame t in [0, v), with
+ *   F_in_t(c)  = the sum over the spans with i <= t <= j of w * IoU(c, .)      F_out_t(c) = the same over the other spans
+ * (the frame-count IoU of hual_al_mbr_label), c any span of the clip:
+ *  - M_yes(t) = max_c [(1 - eps) F_in_t(c) + eps F_out_t(c)];  M_no(t) = max_c [eps F_in_t(c) + (1 - eps) F_out_t(c)];
+ *    V0 = max_c (F_in_t(c) + F_out_t(c)) / Z, independent of t: the conf of hual_al_mbr_label on the same rows and a set without answers.
+ *  - gain(t) = (M_yes(t) + M_no(t)) / Z - V0, float64, clamped to [0, 1], stored as float32.  gain >= 0 is a theorem here - the
+ *    candidates are not restricted - and the clamp only absorbs rounding.
+ *  - sel / nsel, cand / M, gain f32 [N, ld], ask_point, ask_gain and value (= V0), the first-maximal-frame rule, the column ranges, the
+ *    flags of a poisoned row and an id outside [0, N) writing nothing are hual_al_label_gain's, word for word.  No row is contradictory.
+ * F_out_t is summed over the two triangles [0, t-1] and [t+1, v), F_in_t over the rectangle [0, t] x [t, v): the four prefix / suffix
+ * products of hual_al_mbr_label with the bounds clamped per region, a candidate lying in any region or straddling them.  Float64 sums of
+ * terms of one sign in a fixed order (no F - F_in), no atomics, nothing grid wide; about v^3 additions per evaluated frame, v^4 per clip
+ * with every frame.  One launch, one workgroup per selected sample.  Allocates nothing and does not synchronise: capturable in a hipGraph.
+ * Argument errors (those of hual_al_label_gain; eps outside (0, 0.5] or NaN) return HUAL_ERR_INVALID before any HIP call. */
+int hual_al_label_gain_noisy(const hual_al_set* set, const float* s_t, const float* e_t, float eps, const int32_t* sel, int nsel,
+                             const int32_t* cand, int M, float* gain, int32_t* ask_point, float* ask_gain, float* value, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
