@@ -572,6 +572,7 @@ class LabelUpdater:
 
     def set_active_points(self, aps):
         """aps: per sample (list of (frame, is_pos)) in annotation order"""
+        self.aps = aps                                           # (the caller's lists, by reference: session() reads them)
         off = np.zeros(self.N + 1, dtype=np.int32)
         off[1:] = np.cumsum([len(a) for a in aps])
         idx = np.array([f for a in aps for f, _ in a] + [0], dtype=np.int32)      # never empty: a valid pointer
@@ -639,6 +640,56 @@ class LabelUpdater:
             self.query_gain = torch.where(live, at, torch.full_like(at, -1.0)).float()
             self.agree = None
 
+    def session(self, gt_idx, max_questions, stop_entropy=None, min_gain=0.0, noise=None, flips=None, budget=None, sel=None):
+        """an annotation session per sample (hual_al_session, one launch): up to max_questions (1..16) questions, each the frame of
+        most expected information gain under the span posterior given every answer so far - query()'s frame on the grown list -,
+        answered from the ground-truth spans gt_idx (int [N, 2], frame indices, inclusive), until the posterior's entropy is at most
+        stop_entropy bits (None: never), the best gain is at most min_gain bits (0: only a collapsed posterior stops), the budget is
+        spent, or the row is contradictory or poisoned.  noise=eps: the posterior under an annotator who errs with probability eps
+        (tilt() + query() per step, in the kernel); flips: None or uint [N], bit k flips the k-th answer of the sample's session - the
+        simulated annotator's errors; budget: None or int [N], per-sample caps (clamped to [0, max_questions]); sel: None (every
+        sample) or the sample ids (numpy) to run.
+        Leaves asked (i32 [N, Q]), answers (i8 [N, Q]), q_asked, session_gain (f32 [N, Q]), entropy_path (f32 [N, Q + 1]), n_asked and
+        stop_reason (i32 [N]; lib.AL_STOP_REASONS) as device tensors - rows outside sel and unused slots hold -1 - and installs the
+        extended lists with set_active_points (which invalidates a tilt).  A sample whose answered points plus budget exceed
+        lib.AL_SESSION_MAX_POINTS is refused here, on the host, where the lists are known.
+        Returns numpy (asked, answers, n_asked)."""
+        Q = int(max_questions)
+        if not 1 <= Q <= lib.AL_SESSION_MAX_Q:
+            raise ValueError('session: max_questions must lie in [1, %d]' % lib.AL_SESSION_MAX_Q)
+        if not float(min_gain) >= 0.0:
+            raise ValueError('session: min_gain >= 0')
+        eps = 0.0 if noise is None else check_noise(noise)
+        gt = np.ascontiguousarray(gt_idx, dtype=np.int32)
+        if gt.shape != (self.N, 2):
+            raise ValueError('session: gt_idx must hold N = %d spans' % self.N)
+        rows = np.arange(self.N) if sel is None else np.asarray(sel, dtype=np.int64)
+        if rows.ndim != 1 or rows.size < 1 or rows.min() < 0 or rows.max() >= self.N:
+            raise ValueError('session: sel holds sample ids in [0, N)')
+        cap = np.full(self.N, Q, dtype=np.int64) if budget is None else np.clip(np.asarray(budget, dtype=np.int64), 0, Q)
+        if cap.shape != (self.N,):
+            raise ValueError('session: budget must hold N = %d caps' % self.N)
+        for i in rows:
+            if len(self.aps[i]) + int(cap[i]) > lib.AL_SESSION_MAX_POINTS:
+                raise ValueError('session: sample %d holds %d answered points: with a budget of %d that exceeds the %d a session keeps'
+                                 % (i, len(self.aps[i]), int(cap[i]), lib.AL_SESSION_MAX_POINTS))
+
+        def dev32(x):
+            return torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
+        flip_d = None if flips is None else dev32(np.asarray(flips, dtype=np.uint32).view(np.int32))
+        (self.asked, self.answers, self.q_asked, self.session_gain, self.entropy_path, self.n_asked,
+         self.stop_reason) = lib.al_session(self.set, self._s0, self._e0, self.tlen_h, dev32(gt), Q,
+                                            sel=None if sel is None else dev32(rows.astype(np.int32)),
+                                            budget=None if budget is None else dev32(cap.astype(np.int32)),
+                                            stop_entropy=-1.0 if stop_entropy is None else float(stop_entropy), min_gain=float(min_gain),
+                                            eps=eps, flip=flip_d)
+        asked, answers, n_asked = self.asked.cpu().numpy(), self.answers.cpu().numpy(), self.n_asked.cpu().numpy()
+        aps = list(self.aps)                                     # (a new outer list and new rows: the caller's lists are not touched)
+        for i in set(int(i) for i in rows):
+            aps[i] = list(aps[i]) + [(int(asked[i, k]), bool(answers[i, k])) for k in range(int(n_asked[i]))]
+        self.set_active_points(aps)
+        return asked, answers, n_asked
+
     def label_gain(self, frames=True, cand=None, noise=None):
         """per frame, the tIoU the minimum-Bayes-risk label is expected to gain from the frame's answer under the span posterior given
         the set's answered active points (hual_al_label_gain, one launch over the whole set) on the updater's set and deterministic
@@ -686,6 +737,29 @@ class LabelUpdater:
         return new_d.cpu().numpy()
 
 
+def check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by):
+    """the two session arguments of update_labels / run_round against the switches they depend on -> Q; raises ValueError"""
+    try:
+        Q = int(questions_per_clip)
+        ok = not isinstance(questions_per_clip, bool) and Q == questions_per_clip and 1 <= Q <= lib.AL_SESSION_MAX_Q
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('questions_per_clip: an integer in [1, %d]' % lib.AL_SESSION_MAX_Q)
+    if Q > 1 and acquire_by == 'label_gain':
+        raise ValueError("questions_per_clip > 1 with acquire_by='label_gain' is not offered: sessions ask by information gain")
+    if Q > 1 and observe_by != 'info_gain':
+        raise ValueError("questions_per_clip > 1 needs observe_by='info_gain': a session asks by expected information gain")
+    if stop_entropy is not None:
+        try:
+            ok = float(stop_entropy) >= 0.0 and Q > 1
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('stop_entropy: None, or bits >= 0 with questions_per_clip > 1')
+    return Q
+
+
 RANK_BY = ('uncert_video', 'span_risk')
 OBSERVE_BY = ('uncert_frame', 'info_gain')
 RENEW_BY = ('heuristic', 'posterior')
@@ -701,7 +775,7 @@ def span_risk(last_prop):
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
                   rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
-                  answer_noise=None, annotator_flip=None):
+                  answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -740,7 +814,24 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     annotator_flip: None, or (rate, numpy Generator) - a simulated annotator who errs: every answer of the round is flipped with
     probability rate (one draw per selected sample, in selection order) before append_AP; the debug dict gains 'flipped' (bool [N]).
     Independent of answer_noise: without it the hard rule meets the wrong answers.
+    questions_per_clip: 1 (the reference's one question per selected sample: every launch and result as without the argument), or
+    Q in 2..16 with observe_by='info_gain' - every selected sample whose first question has a positive gain then runs an annotation
+    session on the device (LabelUpdater.session, one launch for all of them): up to Q questions, each chosen after the previous
+    answer under the posterior given every answer so far (with the round's answer_noise), stopped early by a collapsed posterior, by
+    contradictory answers, or by stop_entropy (None, or bits: no further question once the posterior's entropy is at most that).  A
+    selected sample whose first question has no positive gain takes the reference's frame, one question, as today.  annotator_flip
+    then draws Q numbers per selected sample, in selection order, used or not: draw k decides the sample's k-th answer.  Ranking,
+    selection, renew (either renew_by), soft_out and the time conversion are unchanged and read the lists after the sessions;
+    pos_idx / neg_idx receive the session's points in order.  The debug dict gains 'asked', 'answers' (int [N, Q], -1 = unused),
+    'n_asked', 'entropy_path' (float32 [N, Q + 1], -1 = not read) and 'stop_reason' (int [N], lib.AL_STOP_REASONS; -1: no session).
+    acquire_by='label_gain' sessions are not offered.  Two corners: with stop_entropy a selected sample that has a gain may already
+    be at or below it before its first question - its session then asks nothing (n_asked 0, stop_reason 'entropy') and the sample gets
+    no question this round.  And under answer_noise "has a positive gain" is LabelUpdater.query(noise=)'s float64 gain of the noisy
+    answer, h2(eps + (1 - 2 eps) q) - h2(eps), while the kernel stops on the float32 h2(q) > 0: at the extremes of q (or eps = 0.5,
+    where a noisy answer carries nothing) the two can differ; a sample the first test rejects takes the reference's frame, one the
+    kernel rejects ends its session at n_asked 0 with stop_reason 'gain'.
     """
+    Q = check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by)
     if soft_out is not None and not isinstance(soft_out, dict):
         raise ValueError('soft_out: None or a dict to receive y1, y2, live and answered')
     noise = None
@@ -804,13 +895,41 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     old_idx = np.array([[_round_half_even_index(t, data_old[i][1], int(vlen[i])) for t in data_old[i][2]] for i in range(N)])
     # append_AP (utils_hual.py:133-139): the annotator answers "is the observed frame inside the ground-truth span?"
     flipped = np.zeros(N, dtype=bool)
-    for i in sel:
-        p = int(ask[i])
-        is_pos = gt_idx[i, 0] <= p <= gt_idx[i, 1]
-        if annotator_flip is not None and annotator_flip[1].random() < float(annotator_flip[0]):      # the simulated annotator errs
-            is_pos, flipped[i] = not is_pos, True
-        data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
-        aps[i].append((p, bool(is_pos)))
+    if Q == 1:
+        for i in sel:
+            p = int(ask[i])
+            is_pos = gt_idx[i, 0] <= p <= gt_idx[i, 1]
+            if annotator_flip is not None and annotator_flip[1].random() < float(annotator_flip[0]):      # the simulated annotator errs
+                is_pos, flipped[i] = not is_pos, True
+            data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
+            aps[i].append((p, bool(is_pos)))
+    else:
+        flips = np.zeros(N, dtype=np.uint32)                     # bit k: the sample's k-th answer is wrong
+        if annotator_flip is not None:
+            for i in sel:                                        # Q draws per selected sample, in selection order, used or not
+                for k in range(Q):
+                    if annotator_flip[1].random() < float(annotator_flip[0]):
+                        flips[i] |= np.uint32(1 << k)
+        has_gain = up.query_gain.cpu().numpy() > 0
+        in_session = np.array([i for i in sel if has_gain[i]], dtype=np.int64)
+        sess = dict(asked=np.full((N, Q), -1, dtype=np.int64), answers=np.full((N, Q), -1, dtype=np.int64), n_asked=np.zeros(N, dtype=np.int64),
+                    entropy_path=np.full((N, Q + 1), -1.0, dtype=np.float32), stop_reason=np.full(N, -1, dtype=np.int64))
+        if len(in_session):
+            asked, answers, n_asked = up.session(gt_idx, Q, stop_entropy=stop_entropy, noise=noise, flips=flips, sel=in_session)
+            sess['asked'][in_session], sess['answers'][in_session] = asked[in_session], answers[in_session]
+            sess['n_asked'][in_session] = n_asked[in_session]
+            sess['entropy_path'][in_session] = up.entropy_path.cpu().numpy()[in_session]
+            sess['stop_reason'][in_session] = up.stop_reason.cpu().numpy()[in_session]
+        for i in sel:
+            if not has_gain[i]:                                  # no positive gain: the reference's frame, one question, as today
+                p = int(ask[i])
+                sess['asked'][i, 0], sess['n_asked'][i] = p, 1
+                sess['answers'][i, 0] = int((gt_idx[i, 0] <= p <= gt_idx[i, 1]) != bool(flips[i] & 1))
+            for k in range(int(sess['n_asked'][i])):
+                p, is_pos = int(sess['asked'][i, k]), bool(sess['answers'][i, k])
+                flipped[i] |= bool((flips[i] >> k) & 1)
+                data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
+                aps[i].append((p, is_pos))
     up.set_active_points(aps)
     if noise is not None:
         up.tilt(noise)                                           # (this round's answers included: what the launches below read)
@@ -849,6 +968,8 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
             dbg['log_evidence'] = up.log_evidence.cpu().numpy()
         if annotator_flip is not None:
             dbg['flipped'] = flipped
+        if Q > 1:
+            dbg.update(sess)
         return data_old, dbg
     return data_old
 
@@ -869,7 +990,7 @@ def labels_from_times(data, vlens):
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
               observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
-              annotator_flip=None):
+              annotator_flip=None, questions_per_clip=1, stop_entropy=None):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -887,6 +1008,9 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     acquire_by: how the round's label update chooses the samples and frames it asks about (update_labels).
     answer_noise / annotator_flip: the error probability the round's span posterior grants the annotator, and a simulated annotator
     who errs (update_labels).
+    questions_per_clip / stop_entropy: the questions a selected sample may be asked in the round, as one session on the device, and the
+    posterior entropy at which a session stops (update_labels); with more than one, metrics['sessions'] holds the transcripts (asked,
+    answers, n_asked, entropy_path, stop_reason).
     soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
     blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
     DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
@@ -909,9 +1033,16 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         soft = {}
     t0 = time.perf_counter()
     prev = bank if bank is not None and bank.K >= 2 else None
-    new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
-                             mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
-                             soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip) if rank == 0 else None
+    Qn = check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by)      # (on every rank, before rank 0 goes its own way)
+    new_data = sessions = None
+    if rank == 0:
+        new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
+                                 mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
+                                 soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip,
+                                 questions_per_clip=Qn, stop_entropy=stop_entropy, return_debug=Qn > 1)
+        if Qn > 1:
+            new_data, dbg = new_data
+            sessions = {k: dbg[k] for k in ('asked', 'answers', 'n_asked', 'entropy_path', 'stop_reason')}
     new_data = hdist.broadcast_object(new_data)
     if soft is not None:
         weighted = soft['live'] & soft['answered']
@@ -953,6 +1084,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         m['mc_bank'] = bank
     if soft is not None:
         m['soft_rows'] = int(weighted.sum())
+    if sessions is not None:
+        m['sessions'] = sessions
     if log and rank == 0:
         log('round %d: update_label %.3f s | train %d steps %.3f s (%.0f clips/s) | infer_trainset %.3f s | pseudo-label '
             'R1@0.5 %.2f mIoU %.2f' % (I, m['update_s'], steps, m['train_s'], m['clips_per_s'], m['infer_s'], r5, mi))

@@ -95,6 +95,24 @@ struct AlMargArgs {
   int32_t* status;                            // [N] 1 = live, 0 = poisoned or contradictory
 };
 
+// hual_al_session (spansession.hip): several adaptive questions per selected sample, answered from the ground truth, in one launch
+struct AlSessionArgs {
+  AlSpanIn in;                                // the set with the answers of earlier rounds, the UNTILTED logits
+  const int32_t* gt;                          // [N, 2] the ground-truth frame span: the simulated annotator
+  const int32_t* sel;                         // [nsel] sample ids (NULL: all)
+  int qmax;                                   // 1..16 question slots per sample
+  const int32_t* budget;                      // [N] per-sample cap, clamped to [0, qmax] (NULL: qmax)
+  float stop_entropy, min_gain;               // bits; stop_entropy < 0: off
+  bool noisy;                                 // eps > 0: the noisy annotator's posterior (spannoisy.h) instead of the hard rule
+  float lam;                                  // (float)ln((1 - eps) / eps) under noisy
+  const uint32_t* flip;                       // [N] bit k flips the k-th answer of the session (NULL: none)
+  int32_t* asked;                             // [N, qmax]
+  int8_t* answer;                             // [N, qmax]
+  float *q_asked, *gain;                      // [N, qmax]
+  float* entropy;                             // [N, qmax + 1]
+  int32_t *n_asked, *stop_reason;             // [N]
+};
+
 // the null and N / ld requirements of an AlSpanIn, refused under the entry point's prefix `who`; between the two, in the order the
 // launches have always checked in, the launch's own requirements (`own`: null outputs, nsel, ... - returns 0 or the failure)
 template <class Own>
@@ -111,6 +129,7 @@ int launch_al_span_marginals(const AlMargArgs& a, hipStream_t s);
 int launch_al_label_gain(const AlGainArgs& a, int nsel, hipStream_t s);
 int launch_al_mbr_label(const AlLabelArgs& a, int nsel, hipStream_t s);
 int launch_al_query(const AlQueryArgs& a, hipStream_t s);
+int launch_al_session(const AlSessionArgs& a, int nsel, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);
 

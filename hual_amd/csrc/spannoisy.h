@@ -34,6 +34,16 @@ struct AlNoisyGainArgs {
 int launch_al_noisy_tilt(const AlTiltArgs& a, hipStream_t s);
 int launch_al_label_gain_noisy(const AlNoisyGainArgs& a, int nsel, hipStream_t s);
 
+// x + (float)g * lam: one float32 product and one float32 addition, each rounded on its own, as h2_bits (al.h) states such arithmetic.
+// (__fmul_rn / __fadd_rn are plain operators that carry the contraction flag of the header that defines them: the compiler fused the
+// pair into one v_pk_fma_f32 for both heads, which no pragma here reaches.)  g == 0 copies x, so that -0 stays -0
+__device__ __forceinline__ float tilt_logit(float x, int g, float lam) {
+#pragma clang fp contract(off)
+  if (g == 0) return x;
+  const float p = (float)g * lam;
+  return x + p;
+}
+
 }  // namespace hual
 
 // stage 1 of spanpost.h's opening for a row whose answers are already in its logits: the same T, v, status and probabilities, an

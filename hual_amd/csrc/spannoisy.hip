@@ -24,16 +24,6 @@ using namespace hual;
 
 namespace {
 
-// x + (float)g * lam: one float32 product and one float32 addition, each rounded on its own, as h2_bits (al.h) states such arithmetic.
-// (__fmul_rn / __fadd_rn are plain operators that carry the contraction flag of the header that defines them: the compiler fused the
-// pair into one v_pk_fma_f32 for both heads, which no pragma here reaches.)  g == 0 copies x, so that -0 stays -0
-__device__ __forceinline__ float tilt_logit(float x, int g, float lam) {
-#pragma clang fp contract(off)
-  if (g == 0) return x;
-  const float p = (float)g * lam;
-  return x + p;
-}
-
 __global__ __launch_bounds__(SPAN_THREADS) void al_noisy_tilt_kernel(AlTiltArgs a) {
   __shared__ SpanRowLds lds;
   __shared__ int gs[257];                   // gs[t + 1] = G(t), gs[0] = G(-1) = 0

@@ -1,5 +1,6 @@
 // The span posterior of one sample given its answered active points, as every launch of the family opens it (hual_al_query in
-// spanquery.hip, hual_al_mbr_label in spanlabel.hip, hual_al_label_gain in spangain.hip, hual_al_span_marginals in spanmarg.hip; the
+// spanquery.hip, hual_al_mbr_label in spanlabel.hip, hual_al_label_gain in spangain.hip, hual_al_span_marginals in spanmarg.hip,
+// every step of hual_al_session in spansession.hip; the
 // contract is in include/hual_seqpan.h): which rows are live, what the consistent set A is, and what Z and Z_A are.  One definition, so
 // all launches classify a row alike.
 //

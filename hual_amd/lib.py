@@ -171,6 +171,7 @@ def load():
     lib.hual_al_span_marginals.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp]
     lib.hual_al_noisy_tilt.argtypes = [P(hual_al_set), vp, vp, f32, vp, vp, vp, vp]
     lib.hual_al_label_gain_noisy.argtypes = [P(hual_al_set), vp, vp, f32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    lib.hual_al_session.argtypes = [P(hual_al_set), vp, vp, vp, vp, i32, i32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_soft.argtypes = lib.hual_assemble_batch_carry.argtypes[:-1] + [P(hual_soft_labels), vp]
     lib.hual_assemble_batch_cursor_soft.argtypes = lib.hual_assemble_batch_cursor.argtypes[:-1] + [P(hual_soft_labels), vp]
     _lib = lib
@@ -552,4 +553,44 @@ def al_label_gain_noisy(aset, s_t, e_t, tlen, eps, sel=None, cand=None, frames=T
                                                ('ask_gain', (N,), torch.float32), ('value', (N,), torch.float32)], ('gain',), dev)
     check(load().hual_al_label_gain_noisy(ctypes.byref(aset), ptr(s_t), ptr(e_t), float(eps), ptr(sel), nsel, ptr(cand), M,
                                           *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)
+
+
+AL_SESSION_MAX_Q = 16           # question slots per sample of hual_al_session
+AL_SESSION_MAX_POINTS = 64      # active points of one sample, the set's and the session's, that hual_al_session holds
+AL_STOP_REASONS = ('budget', 'entropy', 'gain', 'contradictory', 'poisoned', 'overflow')      # HUAL_AL_STOP_*, by value
+
+
+def al_session(aset, s0, e0, tlen, gt, qmax, sel=None, budget=None, stop_entropy=-1.0, min_gain=0.0, eps=0.0, flip=None, out=None):
+    """an annotation session per selected sample of the hual_al_set `aset` (hual_al_session), one launch enqueued on the current
+    stream: up to qmax questions, each the frame of most expected information gain under the span posterior given every answer so far,
+    answered from the ground-truth span, until a stop condition holds.  s0 / e0: the UNTILTED deterministic logits f32 [N, ld] on the
+    device; tlen: the set's row lengths on the HOST - a row above AL_QUERY_MAX_T frames is refused here, before the launch, as in
+    al_query; gt: device i32 [N, 2], the ground-truth frame spans; qmax in [1, 16]; sel: device i32 [nsel] sample ids (None: all);
+    budget: device i32 [N] per-sample caps (None: qmax); stop_entropy: bits, negative = off; min_gain: bits, >= 0; eps: 0 = the hard
+    rule, (0, 0.5] = the noisy annotator; flip: device i32 [N] (read as u32), bit k flips the session's k-th answer (None: no flip).
+    -> (asked i32 [N, qmax], answer i8 [N, qmax], q_asked f32 [N, qmax], gain f32 [N, qmax], entropy f32 [N, qmax + 1], n_asked i32 [N],
+    stop_reason i32 [N]; AL_STOP_REASONS names its values).  out: such a tuple of contiguous device tensors to write into instead.
+    Only the rows of selected samples are written: the others keep what they held (-1 in tensors allocated here, the value of an unused
+    slot)."""
+    import torch
+    N, ld, dev = _span_inputs('al_session', aset, s0, e0, tlen)
+    nsel = _span_sel('al_session', sel, dev) or N
+    qmax = int(qmax)
+    if not 1 <= qmax <= AL_SESSION_MAX_Q:
+        raise HualError('al_session: qmax must lie in [1, %d]' % AL_SESSION_MAX_Q)
+    for name, x, shape in (('gt', gt, (N, 2)), ('budget', budget, (N,)), ('flip', flip, (N,))):
+        if x is None and name != 'gt':
+            continue
+        if x is None or x.dtype != torch.int32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
+            raise HualError('al_session: %s must be a contiguous int32 %s on the logits\' device' % (name, list(shape)))
+    i32, f32 = torch.int32, torch.float32
+    spec = [('asked', (N, qmax), i32), ('answer', (N, qmax), torch.int8), ('q_asked', (N, qmax), f32), ('gain', (N, qmax), f32),
+            ('entropy', (N, qmax + 1), f32), ('n_asked', (N,), i32), ('stop_reason', (N,), i32)]
+    if out is None:
+        out = tuple(torch.full(shape, -1, dtype=dt, device=dev) for _, shape, dt in spec)
+    else:
+        _span_out('al_session', out, spec, (), dev)
+    check(load().hual_al_session(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(gt), ptr(sel), nsel, qmax, ptr(budget), float(stop_entropy),
+                                 float(min_gain), float(eps), ptr(flip), *[ptr(o) for o in out], stream_ptr()))
     return tuple(out)

@@ -752,6 +752,50 @@ int hual_al_label_gain_noisy(const hual_al_set* set, const float* s_t, const flo
                              const int32_t* cand, int M, float* gain, int32_t* ask_point, float* ask_gain, float* value, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Annotation sessions: several adaptive questions per clip in one launch (HUAL_ABI_VERSION unchanged: one new symbol, nothing else
+ * moved).  The posterior above conditions on the answers, not on a new forward pass: after the annotator has answered frame t, the best
+ * next frame is defined by the same logits.  hual_al_session spends up to qmax questions on every selected sample, each chosen after
+ * the previous answer, the annotator simulated from the ground-truth span (append_AP, utils_hual.py:133-139), and stops as soon as the
+ * posterior has collapsed far enough.  One workgroup per selected sample; the list of active points and the transcript live in LDS.
+ *
+ * Inputs: the set with the answers of earlier rounds; s0 / e0 f32 [N, ld], the UNTILTED deterministic logits; gt i32 [N, 2], the
+ * ground-truth frame span (inclusive); sel / nsel as in hual_al_mbr_label (sel NULL: all N samples; rows not listed are left untouched;
+ * an id outside [0, N) writes nothing; a repeated id writes the same values twice); qmax in [1, 16]; budget i32 [N] (may be NULL: qmax
+ * everywhere), the per-sample cap, clamped to [0, qmax]; stop_entropy in bits (negative: off); min_gain in bits, >= 0; eps: 0 selects
+ * the hard rule of hual_al_query, a value in (0, 0.5] the noisy annotator of hual_al_noisy_tilt; flip u32 [N] (may be NULL: no flip),
+ * bit k flips the k-th answer of this session.
+ *
+ * Per selected sample, with k = the questions asked so far, the list = the set's points followed by this session's:
+ *  1. the posterior on the list.  eps == 0: exactly hual_al_query on a set that holds the list (p_s, p_e and their log2f are computed
+ *     once; the hull, the segments and the segmented float64 sums per step).  eps > 0: exactly hual_al_noisy_tilt of the list applied
+ *     to s0 / e0 (never a tilt of a tilt), then hual_al_query on the tilted rows and a set without answers.
+ *  2. the frame: hual_al_query's query_point - q(t), h2((float)q(t)), the first frame of maximal gain - and its post_entropy.
+ *  3. the stop conditions, in this order: the row is poisoned (hual_al_query's rule; under eps > 0 also hual_al_noisy_tilt's)
+ *     -> HUAL_AL_STOP_POISONED; contradictory (eps == 0 only) -> _CONTRADICTORY; stop_entropy >= 0 and post_entropy <= stop_entropy ->
+ *     _ENTROPY; query_gain <= min_gain (a gain of 0 always stops) -> _GAIN; k == budget -> _BUDGET.
+ *  4. otherwise the answer is (gt[n][0] <= t <= gt[n][1]) XOR bit k of flip[n]; it joins the list and k grows.
+ * The list has room for 64 points: a sample whose points in the set plus its budget exceed that asks nothing and reports
+ * HUAL_AL_STOP_OVERFLOW (checked first, before the row is opened).
+ *
+ * Outputs, each written for every selected sample: asked i32 [N, qmax] the frames in order; answer i8 [N, qmax] 1 / 0 as appended;
+ * q_asked f32 [N, qmax] = incl of hual_al_query at the asked frame; gain f32 [N, qmax] = its query_gain; entropy f32 [N, qmax + 1] =
+ * post_entropy before each question and after the last (the pass that stopped the session), -1 where that pass found the row
+ * poisoned or contradictory; unused slots hold -1 in all five.  n_asked i32 [N]; stop_reason i32 [N].  Every stored float is bit for
+ * bit what the launches it replaces store (one shared body: csrc/spanstep.h).
+ * Allocates nothing and does not synchronise: capturable in a hipGraph.  Argument errors (a null pointer other than sel, budget and
+ * flip, N < 1, ld outside [2, 1024], nsel < 1 with sel, qmax outside [1, 16], min_gain < 0 or NaN, eps neither 0 nor in (0, 0.5])
+ * return HUAL_ERR_INVALID before any HIP call. */
+#define HUAL_AL_STOP_BUDGET 0
+#define HUAL_AL_STOP_ENTROPY 1
+#define HUAL_AL_STOP_GAIN 2
+#define HUAL_AL_STOP_CONTRADICTORY 3
+#define HUAL_AL_STOP_POISONED 4
+#define HUAL_AL_STOP_OVERFLOW 5
+int hual_al_session(const hual_al_set* set, const float* s0, const float* e0, const int32_t* gt, const int32_t* sel, int nsel, int qmax,
+                    const int32_t* budget, float stop_entropy, float min_gain, float eps, const uint32_t* flip, int32_t* asked,
+                    int8_t* answer, float* q_asked, float* gain, float* entropy, int32_t* n_asked, int32_t* stop_reason, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
