@@ -60,6 +60,12 @@ An annotator who errs (the reference simulates a perfect one): update_labels(ans
 posterior under answers that are wrong with probability eps - the product form of logits tilted by the answers (LabelUpdater.tilt, one
 hual_al_noisy_tilt launch; the gain by hual_al_label_gain_noisy), on which no answer is a hard constraint and no sample contradictory;
 annotator_flip=(rate, rng) simulates such an annotator.  Off by default: every launch, record and result is then what it was.
+
+Calibration (all of the above take the model's softmaxes at face value and eps from the caller): update_labels(calibrate='evidence')
+first fits a temperature tau and the error rate eps to the answers of the earlier rounds by their evidence, the sum over the clips of
+ln P(answers | softmax(logits / tau), eps) (LabelUpdater.calibrate: hual_al_evidence_grid on a coarse grid and two zooms), and the
+round's posterior readers use the fitted pair (LabelUpdater.set_temperature; temperature= hands one in).  Off by default: every launch,
+record and result is then what it was.
 """
 import ctypes
 import math
@@ -483,6 +489,42 @@ def check_noise(eps):
     return e
 
 
+CALIB_TAUS = tuple(2.0 ** (k / 4.0) for k in range(-8, 9))      # the coarse grid of LabelUpdater.calibrate: 1/4 .. 4, tau = 1 in the middle
+CALIB_EPS = (0.005, 0.01, 0.02, 0.05, 0.1, 0.15, 0.2, 0.3, 0.4, 0.5)
+CALIB_MIN_EPS = 1e-6                                             # where a zoom towards eps = 0 stops
+
+
+def _zoom_axis(x, i, n, lo, hi):
+    """n points, geometric, from x[i - 1] to x[i + 1] of the ascending positive axis x - where x[i] is its first or last point, one
+    step of the neighbouring ratio past it -, clamped to [lo, hi] (lo = 0: no clamp below)"""
+    x = np.asarray(x, dtype=np.float64)
+    step = x[1] / x[0] if i == 0 else x[i] / x[i - 1]
+    left = x[i - 1] if i > 0 else x[i] / step
+    right = x[i + 1] if i + 1 < x.size else x[i] * (x[i] / x[i - 1])
+    left, right = (max(left, lo) if lo > 0 else left), min(right, hi)
+    return np.geomspace(left, right, n) if right > left else np.array([left])
+
+
+def check_calibration(temperature, calibrate, observe_by, acquire_by, renew_by, soft_out):
+    """the two calibration arguments of update_labels / run_round against the switches they depend on -> the temperature as a float or
+    None; raises ValueError"""
+    if calibrate not in CALIBRATE:
+        raise ValueError("calibrate: None or 'evidence'")
+    if temperature is not None:
+        try:
+            ok = not isinstance(temperature, bool) and 0.0 < float(np.float32(1.0 / float(temperature))) < float('inf')
+        except (TypeError, ValueError, ZeroDivisionError):
+            ok = False
+        if not ok:
+            raise ValueError('temperature: None or a finite temperature > 0')
+        temperature = float(temperature)
+    if (temperature is not None or calibrate is not None) and observe_by != 'info_gain' and acquire_by != 'label_gain' \
+            and renew_by != 'posterior' and soft_out is None:
+        raise ValueError("%s changes the span posterior: switch on one of its readers (observe_by='info_gain', "
+                         "acquire_by='label_gain', renew_by='posterior', soft_out)" % ('calibrate' if calibrate is not None else 'temperature'))
+    return temperature
+
+
 class LabelUpdater:
     """Device-side state of one update_label round: the logits of the results pkl as [N, ld] matrices, the active
     points as CSR.  score() and renew() are one launch each.
@@ -568,6 +610,7 @@ class LabelUpdater:
         self.uncert_frame = torch.zeros(N, ld, device=self.dev, dtype=torch.float64)
         self.uncert_video = torch.zeros(N, device=self.dev)
         self.observe = torch.zeros(N, device=self.dev, dtype=torch.int32)
+        self.temperature, self._inv_tau, self._scaled, self._last_eps = None, None, None, None
         self.set_active_points(aps)
 
     def set_active_points(self, aps):
@@ -584,6 +627,116 @@ class LabelUpdater:
         self.set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, p(self.ap_off).value,
                                    p(self.ap_idx).value, p(self.ap_pos).value)
         self.tilt_eps = None                                     # (a tilt holds the answers it was made with)
+        self._scaled = None                                      # (and the scaled rows go with it: both are rebuilt on demand)
+
+    def set_temperature(self, tau):
+        """the temperature of the span posterior: None or 1.0 (the default) - _rows, tilt and session read the deterministic logits
+        themselves, the very same tensors, so every launch and stored bit is what it is without this call -, or tau > 0: they read
+        s0 * float32(1 / tau) and e0 * float32(1 / tau), one float32 product per logit (the row hual_al_evidence_grid evaluates at that
+        tau), computed once and dropped with the tilt.  score() and renew() restate the reference's heuristic and keep reading the
+        unscaled logits.  calibrate() fits tau."""
+        if tau is not None:
+            try:
+                tau = float('nan') if isinstance(tau, bool) else float(tau)
+            except (TypeError, ValueError):
+                tau = float('nan')
+            if not 0.0 < tau < float('inf'):
+                raise ValueError('the temperature must be None or a finite number > 0')
+        inv = None if tau is None or tau == 1.0 else np.float32(1.0 / tau)
+        if inv is not None and not 0.0 < float(inv) < float('inf'):
+            raise ValueError('the temperature must be None or a finite number > 0')
+        if inv != self._inv_tau:
+            self.tilt_eps, self._scaled = None, None
+        self.temperature, self._inv_tau = (None if inv is None else tau), inv
+
+    def _logits(self):
+        """(s, e) the posterior's launches read: the deterministic logits, or under a temperature their float32 products with 1 / tau"""
+        if self._inv_tau is None:
+            return self._s0, self._e0
+        if self._scaled is None:
+            k = float(self._inv_tau)                             # (a python scalar: torch multiplies in float32, by float32(1 / tau))
+            self._scaled = ((self._s0 * k).contiguous(), (self._e0 * k).contiguous())
+        return self._scaled
+
+    def evidence_grid(self, taus, eps, sel=None):
+        """ln P(the set's answers | softmax(s0 / tau), softmax(e0 / tau), eps) per sample on the grid taus x eps and its sum over the
+        set (hual_al_evidence_grid, lib.al_evidence_grid) on the updater's set and UNSCALED deterministic logits, whatever
+        set_temperature holds.  taus: 1 to 32 temperatures > 0, handed on as float32(1 / tau); eps: 1 to 16 error rates in (0, 0.5];
+        sel: None or the sample ids (numpy).  Leaves and returns (ev_table f64 [N, A * B], ev_status i32 [N], ev_total f64 [A * B],
+        ev_counts i32 [4]) as device tensors."""
+        inv = np.array([np.float32(1.0 / float(t)) for t in np.asarray(taus, dtype=np.float64).reshape(-1)], dtype=np.float32)
+        sel_d = None if sel is None else torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
+        self.ev_table, self.ev_status, self.ev_total, self.ev_counts = lib.al_evidence_grid(
+            self.set, self._s0, self._e0, self.tlen_h, inv, np.asarray(eps, dtype=np.float32).reshape(-1), sel=sel_d)
+        return self.ev_table, self.ev_status, self.ev_total, self.ev_counts
+
+    def calibrate(self, taus=None, eps=None, refine=2, sel=None, min_answers=32, at_eps=None):
+        """fit the temperature and the annotator's error rate to the set's answers by their evidence: the pair that maximises
+        L(tau, eps) = the sum over the samples of ln P(the answers | softmax(s0 / tau), softmax(e0 / tau), eps) on a grid, then on
+        `refine` finer grids around the best cell - one evidence_grid() launch each.
+        taus / eps: the coarse grid (None: CALIB_TAUS, 2^(k/4) for k = -8..8, and CALIB_EPS); an axis of one value stays fixed.  Every
+        zoom grid is geometric in tau and in the odds eps / (1 - eps), spans the best cell's neighbours on both axes (one step past
+        the edge where the best cell lies on it), is clamped to tau > 0 and eps in [CALIB_MIN_EPS, 0.5], and holds the best cell
+        itself: the best total never decreases from grid to grid.  sel: None or the sample ids (numpy) to fit on.
+        at_eps: the error rate of the uncalibrated posterior the fit is compared with (None: the eps of the tilt the updater holds or
+        last held); the cell (tau = 1, at_eps) is part of the coarse grid.
+        -> None with fewer than min_answers answers inside their clips (on the host, before any launch; and again among the rows the
+        launch summed): nothing is extrapolated from three clicks.  Else a dict: tau, eps (python floats; eps a float32 widened, as
+        check_noise returns it), log_evidence (the best total of the last grid), per_answer = exp(log_evidence / answers), the
+        geometric-mean likelihood of an answer, at_default = the total at (1, at_eps) (None without an at_eps), rows, answers,
+        excluded (of the last grid: a row poisoned at one of a grid's temperatures is left out of that whole grid), and grids = every
+        launched (taus, eps, totals [A, B]) as numpy arrays."""
+        rows = np.arange(self.N) if sel is None else np.asarray(sel, dtype=np.int64)
+        if rows.ndim != 1 or rows.size < 1 or rows.min() < 0 or rows.max() >= self.N:
+            raise ValueError('calibrate: sel holds sample ids in [0, N)')
+        refine = int(refine)
+        if refine < 0:
+            raise ValueError('calibrate: refine >= 0')
+        if at_eps is None:
+            at_eps = self.tilt_eps if self.tilt_eps is not None else self._last_eps
+        at_eps = None if at_eps is None else check_noise(at_eps)
+        tg = np.unique(np.asarray(CALIB_TAUS if taus is None else taus, dtype=np.float64).reshape(-1))
+        eg = np.unique(np.array([check_noise(e) for e in np.asarray(CALIB_EPS if eps is None else eps).reshape(-1)], dtype=np.float64))
+        if tg.size < 1 or not (np.isfinite(tg).all() and (tg > 0).all()):
+            raise ValueError('calibrate: the temperatures must be finite and > 0')
+        fixed_tau, fixed_eps = tg.size == 1, eg.size == 1
+        nt, ne = min(max(tg.size, 3), lib.AL_GRID_MAX_TAU - 1), min(max(eg.size, 3), lib.AL_GRID_MAX_EPS - 1)
+        own_t, own_e = tg, eg                                    # the cells the fit may choose: the caller's
+        if at_eps is not None:                                   # the uncalibrated cell rides in the coarse grid
+            tg, eg = np.unique(np.append(tg, 1.0)), np.unique(np.append(eg, at_eps))
+        if tg.size > lib.AL_GRID_MAX_TAU or eg.size > lib.AL_GRID_MAX_EPS:
+            raise ValueError('calibrate: at most %d temperatures and %d error rates per grid (the uncalibrated cell included)'
+                             % (lib.AL_GRID_MAX_TAU, lib.AL_GRID_MAX_EPS))
+        inside = sum(1 for i in rows for f, _ in self.aps[i] if 0 <= f < min(int(self.vlen_h[i]), int(self.tlen_h[i])))
+        if inside < int(min_answers):
+            return None
+        grids, at_default = [], None
+        for level in range(refine + 1):
+            _, _, total, counts = self.evidence_grid(tg, eg, sel=None if sel is None else rows)
+            tot, cnt = total.cpu().numpy().reshape(tg.size, eg.size), counts.cpu().numpy()
+            grids.append((tg.copy(), eg.copy(), tot))
+            if cnt[0] < 1 or cnt[1] < int(min_answers):
+                return None
+            # the first cell of maximal total, the launch's own rule (counts[3]) - among the caller's cells where the uncalibrated
+            # cell brought a row or a column of its own into the coarse grid
+            own = np.isin(tg, own_t)[:, None] & np.isin(eg, own_e)[None, :] if level == 0 else np.ones(tot.shape, dtype=bool)
+            ia, ib = divmod(int(np.argmax(np.where(own, tot, -np.inf))), eg.size)
+            if level == 0 and at_eps is not None:
+                at_default = float(tot[int(np.searchsorted(tg, 1.0)), int(np.searchsorted(eg, at_eps))])
+            if level == refine:
+                break
+            if fixed_tau:
+                tg = tg[ia:ia + 1]
+            else:
+                tg = np.unique(np.append(_zoom_axis(tg, ia, nt, 0.0, float('inf')), tg[ia]))
+            if fixed_eps:
+                eg = eg[ib:ib + 1]
+            else:
+                odds = _zoom_axis(eg / (1.0 - eg), ib, ne, CALIB_MIN_EPS / (1.0 - CALIB_MIN_EPS), 1.0)
+                eg = np.unique(np.array([check_noise(min(o / (1.0 + o), 0.5)) for o in odds] + [eg[ib]], dtype=np.float64))
+        best = float(tot[ia, ib])
+        return dict(tau=float(tg[ia]), eps=float(eg[ib]), log_evidence=best, per_answer=float(np.exp(best / int(cnt[1]))),
+                    at_default=at_default, rows=int(cnt[0]), answers=int(cnt[1]), excluded=int(cnt[2]), grids=grids)
 
     def tilt(self, eps):
         """the set's answers folded into the deterministic logits under an annotator who errs with probability eps in (0, 0.5]
@@ -591,19 +744,19 @@ class LabelUpdater:
         ln P(the answers | the model, eps), NaN on a poisoned row), free_set (a hual_al_set over the same vlen / tlen WITHOUT answers:
         what the family's launches take beside the tilted rows) and tilt_eps; set_active_points invalidates them."""
         eps = check_noise(eps)
-        self.s_t, self.e_t, self.log_evidence = lib.al_noisy_tilt(self.set, self._s0, self._e0, self.tlen_h, eps)
+        self.s_t, self.e_t, self.log_evidence = lib.al_noisy_tilt(self.set, *self._logits(), self.tlen_h, eps)
         if getattr(self, '_free', None) is None:
             self._free = (torch.zeros(self.N + 1, dtype=torch.int32, device=self.dev), torch.zeros(1, dtype=torch.int32, device=self.dev),
                           torch.zeros(1, dtype=torch.int8, device=self.dev))
         p = lib.ptr
         self.free_set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, *[p(x).value for x in self._free])
-        self.tilt_eps = eps
+        self.tilt_eps = self._last_eps = eps
 
     def _rows(self, noise):
         """(set, s, e) a launch of the family reads: the updater's own, or under noise = eps the set without answers and the rows
         tilted by eps (tilted here unless they already are)"""
         if noise is None:
-            return self.set, self._s0, self._e0
+            return (self.set,) + tuple(self._logits())
         if self.tilt_eps != check_noise(noise):
             self.tilt(noise)
         return self.free_set, self.s_t, self.e_t
@@ -678,7 +831,7 @@ class LabelUpdater:
             return torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
         flip_d = None if flips is None else dev32(np.asarray(flips, dtype=np.uint32).view(np.int32))
         (self.asked, self.answers, self.q_asked, self.session_gain, self.entropy_path, self.n_asked,
-         self.stop_reason) = lib.al_session(self.set, self._s0, self._e0, self.tlen_h, dev32(gt), Q,
+         self.stop_reason) = lib.al_session(self.set, *self._logits(), self.tlen_h, dev32(gt), Q,
                                             sel=None if sel is None else dev32(rows.astype(np.int32)),
                                             budget=None if budget is None else dev32(cap.astype(np.int32)),
                                             stop_entropy=-1.0 if stop_entropy is None else float(stop_entropy), min_gain=float(min_gain),
@@ -698,7 +851,7 @@ class LabelUpdater:
         (i32 [N]), ask_gain and label_value (f32 [N]) as device tensors.
         noise=eps: the gain from a NOISY answer (hual_al_label_gain_noisy, one launch) on the rows tilted by eps (tilt())."""
         if noise is None:
-            out = lib.al_label_gain(self.set, self._s0, self._e0, self.tlen_h, cand=cand, frames=frames)
+            out = lib.al_label_gain(*self._rows(None), self.tlen_h, cand=cand, frames=frames)
         else:
             aset, s, e = self._rows(noise)
             out = lib.al_label_gain_noisy(aset, s, e, self.tlen_h, check_noise(noise), cand=cand, frames=frames)
@@ -764,6 +917,7 @@ RANK_BY = ('uncert_video', 'span_risk')
 OBSERVE_BY = ('uncert_frame', 'info_gain')
 RENEW_BY = ('heuristic', 'posterior')
 ACQUIRE_BY = (None, 'label_gain')
+CALIBRATE = (None, 'evidence')
 
 
 def span_risk(last_prop):
@@ -775,7 +929,7 @@ def span_risk(last_prop):
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
                   rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
-                  answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None):
+                  answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -830,6 +984,13 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     answer, h2(eps + (1 - 2 eps) q) - h2(eps), while the kernel stops on the float32 h2(q) > 0: at the extremes of q (or eps = 0.5,
     where a noisy answer carries nothing) the two can differ; a sample the first test rejects takes the reference's frame, one the
     kernel rejects ends its session at n_asked 0 with stop_reason 'gain'.
+    temperature: None, or tau > 0 - the posterior's readers (observe_by='info_gain', acquire_by='label_gain', renew_by='posterior',
+    soft_out, the sessions; at least one must be on) read softmax(logits / tau) instead of the softmax itself
+    (LabelUpdater.set_temperature); the reference's score and renew keep the unscaled logits.
+    calibrate: None, or 'evidence' - the answers data_old already holds are fitted first (LabelUpdater.calibrate: the temperature and
+    error rate of maximal evidence, three launches of hual_al_evidence_grid); where the fit exists (at least 32 answers) its tau and
+    eps take the place of temperature and answer_noise for the round's posterior readers, otherwise the given values stand.  The same
+    readers must be on.  The debug dict gains 'calibration' (the fit's dict, or None).  With both arguments off nothing changes.
     """
     Q = check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by)
     if soft_out is not None and not isinstance(soft_out, dict):
@@ -843,6 +1004,7 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         if observe_by != 'info_gain' and acquire_by != 'label_gain' and renew_by != 'posterior' and soft_out is None:
             raise ValueError("answer_noise changes the span posterior: switch on one of its readers (observe_by='info_gain', "
                              "acquire_by='label_gain', renew_by='posterior', soft_out)")
+    temperature = check_calibration(temperature, calibrate, observe_by, acquire_by, renew_by, soft_out)
     if annotator_flip is not None:
         ok = isinstance(annotator_flip, (tuple, list)) and len(annotator_flip) == 2 and isinstance(annotator_flip[1], np.random.Generator)
         try:
@@ -877,6 +1039,12 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     else:
         up = LabelUpdater(last_prop, aps, device=device)
     up.score(coff[6])
+    fit = None
+    if calibrate == 'evidence':                                  # on the answers of the earlier rounds
+        fit = up.calibrate(at_eps=noise)
+        if fit is not None:
+            temperature, noise = fit['tau'], fit['eps']
+    up.set_temperature(temperature)
     uv = up.uncert_video.cpu().numpy()
     observe = up.observe.cpu().numpy()
     ask = observe
@@ -970,6 +1138,8 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
             dbg['flipped'] = flipped
         if Q > 1:
             dbg.update(sess)
+        if calibrate is not None:
+            dbg['calibration'] = fit
         return data_old, dbg
     return data_old
 
@@ -990,7 +1160,7 @@ def labels_from_times(data, vlens):
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
               observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
-              annotator_flip=None, questions_per_clip=1, stop_entropy=None):
+              annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -1011,6 +1181,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     questions_per_clip / stop_entropy: the questions a selected sample may be asked in the round, as one session on the device, and the
     posterior entropy at which a session stops (update_labels); with more than one, metrics['sessions'] holds the transcripts (asked,
     answers, n_asked, entropy_path, stop_reason).
+    temperature / calibrate: the temperature of the round's span posterior, and its fit - with the annotator's error rate - to the
+    answers of the earlier rounds by their evidence (update_labels); metrics['calibration'] holds the fit under calibrate.
     soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
     blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
     DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
@@ -1034,14 +1206,18 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     t0 = time.perf_counter()
     prev = bank if bank is not None and bank.K >= 2 else None
     Qn = check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by)      # (on every rank, before rank 0 goes its own way)
-    new_data = sessions = None
+    check_calibration(temperature, calibrate, observe_by, acquire_by, renew_by, soft)
+    new_data = sessions = calibration = None
     if rank == 0:
         new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
                                  mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
                                  soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip,
-                                 questions_per_clip=Qn, stop_entropy=stop_entropy, return_debug=Qn > 1)
-        if Qn > 1:
+                                 questions_per_clip=Qn, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate,
+                                 return_debug=Qn > 1 or calibrate is not None)
+        if Qn > 1 or calibrate is not None:
             new_data, dbg = new_data
+            calibration = dbg.get('calibration')
+        if Qn > 1:
             sessions = {k: dbg[k] for k in ('asked', 'answers', 'n_asked', 'entropy_path', 'stop_reason')}
     new_data = hdist.broadcast_object(new_data)
     if soft is not None:
@@ -1086,6 +1262,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         m['soft_rows'] = int(weighted.sum())
     if sessions is not None:
         m['sessions'] = sessions
+    if calibrate is not None:
+        m['calibration'] = calibration
     if log and rank == 0:
         log('round %d: update_label %.3f s | train %d steps %.3f s (%.0f clips/s) | infer_trainset %.3f s | pseudo-label '
             'R1@0.5 %.2f mIoU %.2f' % (I, m['update_s'], steps, m['train_s'], m['clips_per_s'], m['infer_s'], r5, mi))

@@ -16,17 +16,20 @@ __device__ __forceinline__ int span_row_poisoned(const float* __restrict__ zs_, 
   return __syncthreads_or(t < v && (zs_[row + t] != zs_[row + t] || ze_[row + t] != ze_[row + t]));
 }
 
-// ps / pe [256] (LDS) <- softmax of the masked logits of the clip at `row`, 1 <= v <= T <= 256; smf [2 * SPAN_WAVES] floats and smd
-// [2 * SPAN_WAVES] doubles of LDS scratch.  Called by all SPAN_THREADS threads; ends on a barrier, after which ps / pe are readable.
+// ps / pe [256] (LDS) <- softmax of the masked logits of one clip, 1 <= v <= T <= 256, thread t's start / end logit given by start() /
+// end() (called at t < v only): read from memory by span_probabilities below, a register's value scaled by 1 / tau in
+// hual_al_evidence_grid (spancalib.hip) - one body, so the same logits give the same bits.  smf [2 * SPAN_WAVES] floats and smd
+// [2 * SPAN_WAVES] doubles of LDS scratch, FRESH: a caller that has read them, or ps / pe, puts a barrier in front.  Called by all
+// SPAN_THREADS threads; ends on a barrier, after which ps / pe are readable.
 // heads_kernel's span stage (mask_logits, reproducible softmax; oracle/seqpan_ref.py::softmax_cr)
-__device__ __forceinline__ void span_probabilities(const float* __restrict__ zs_, const float* __restrict__ ze_, size_t row, int T, int v,
-                                                   float* ps, float* pe, float* smf, double* smd) {
+template <class Start, class End>
+__device__ __forceinline__ void span_probabilities_of(Start start, End end, int T, int v, float* ps, float* pe, float* smf, double* smd) {
   const int t = threadIdx.x;
   const bool in = t < T;
   float zs = -INFINITY, ze = -INFINITY;
   if (in) {
-    zs = t < v ? zs_[row + t] : HUAL_MASK_VALUE;      // (= x * 0 + HUAL_MASK_VALUE for a finite padding logit, never read here)
-    ze = t < v ? ze_[row + t] : HUAL_MASK_VALUE;
+    zs = t < v ? start() : HUAL_MASK_VALUE;           // (= x * 0 + HUAL_MASK_VALUE for a finite padding logit, never read here)
+    ze = t < v ? end() : HUAL_MASK_VALUE;
   }
   // (smf / smd are fresh: no barrier in front.  Waves 4.. contribute -inf and exact zeros, as waves 4 - 7 of heads_kernel do)
   float mxs = zs, mxe = ze;
@@ -40,4 +43,11 @@ __device__ __forceinline__ void span_probabilities(const float* __restrict__ zs_
     pe[t] = __fdiv_rn(xe, (float)dse);
   }
   __syncthreads();
+}
+
+// the same of the logits of the clip at `row` of zs_ / ze_
+__device__ __forceinline__ void span_probabilities(const float* __restrict__ zs_, const float* __restrict__ ze_, size_t row, int T, int v,
+                                                   float* ps, float* pe, float* smf, double* smd) {
+  const int t = threadIdx.x;
+  span_probabilities_of([&] { return zs_[row + t]; }, [&] { return ze_[row + t]; }, T, v, ps, pe, smf, smd);
 }

@@ -172,6 +172,7 @@ def load():
     lib.hual_al_noisy_tilt.argtypes = [P(hual_al_set), vp, vp, f32, vp, vp, vp, vp]
     lib.hual_al_label_gain_noisy.argtypes = [P(hual_al_set), vp, vp, f32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_al_session.argtypes = [P(hual_al_set), vp, vp, vp, vp, i32, i32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.hual_al_evidence_grid.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_soft.argtypes = lib.hual_assemble_batch_carry.argtypes[:-1] + [P(hual_soft_labels), vp]
     lib.hual_assemble_batch_cursor_soft.argtypes = lib.hual_assemble_batch_cursor.argtypes[:-1] + [P(hual_soft_labels), vp]
     _lib = lib
@@ -553,6 +554,41 @@ def al_label_gain_noisy(aset, s_t, e_t, tlen, eps, sel=None, cand=None, frames=T
                                                ('ask_gain', (N,), torch.float32), ('value', (N,), torch.float32)], ('gain',), dev)
     check(load().hual_al_label_gain_noisy(ctypes.byref(aset), ptr(s_t), ptr(e_t), float(eps), ptr(sel), nsel, ptr(cand), M,
                                           *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)
+
+
+AL_GRID_MAX_TAU = 32      # temperatures per hual_al_evidence_grid launch
+AL_GRID_MAX_EPS = 16      # error rates per launch (csrc/spancalib.h)
+
+
+def al_evidence_grid(aset, s0, e0, tlen, inv_tau, eps, sel=None, out=None):
+    """ln P(the answers | softmax(s0 * inv_tau[a]), softmax(e0 * inv_tau[a]), eps[b]) of every selected sample of the hual_al_set `aset`
+    on the grid of A reciprocal temperatures x B error rates, and its sum over the set per cell (hual_al_evidence_grid), enqueued on the
+    current stream: the likelihood that calibrates the span posterior.  s0 / e0: the UNTILTED deterministic logits f32 [N, ld] on the
+    device; tlen: the set's row lengths on the HOST - a row above AL_QUERY_MAX_T frames is refused here, before the launch, as in
+    al_query; inv_tau: 1 to 32 host floats, finite and > 0 (read as float32: the row is the float32 product s0 * inv_tau[a]); eps: 1 to
+    16 host floats in (0, 0.5] (read as float32); sel: device i32 [nsel] sample ids (None: all).
+    -> (table f64 [N, A * B], status i32 [N], total f64 [A * B], counts i32 [4]): cell c = a * B + b; a poisoned cell is NaN; status 1 = every
+    cell of the row is finite; total sums the selected rows of status 1; counts = rows summed, answers summed, rows left out, the first
+    cell of maximal total (-1: no row was summed).  out: such a tuple of contiguous device tensors to write into instead.  Only the rows
+    of selected samples are written in table and status: the others keep what they held (NaN and -1 in tensors allocated here)."""
+    import numpy as np
+    import torch
+    N, ld, dev = _span_inputs('al_evidence_grid', aset, s0, e0, tlen)
+    nsel = _span_sel('al_evidence_grid', sel, dev) or N
+    it = np.ascontiguousarray(np.asarray(inv_tau, dtype=np.float32).reshape(-1))
+    ep = np.ascontiguousarray(np.asarray(eps, dtype=np.float32).reshape(-1))
+    A, B = int(it.size), int(ep.size)
+    if not 1 <= A <= AL_GRID_MAX_TAU or not 1 <= B <= AL_GRID_MAX_EPS:
+        raise HualError('al_evidence_grid: 1 to %d temperatures and 1 to %d error rates per launch' % (AL_GRID_MAX_TAU, AL_GRID_MAX_EPS))
+    spec = [('table', (N, A * B), torch.float64), ('status', (N,), torch.int32), ('total', (A * B,), torch.float64), ('counts', (4,), torch.int32)]
+    if out is None:
+        out = (torch.full((N, A * B), float('nan'), dtype=torch.float64, device=dev), torch.full((N,), -1, dtype=torch.int32, device=dev),
+               torch.empty(A * B, dtype=torch.float64, device=dev), torch.empty(4, dtype=torch.int32, device=dev))
+    else:
+        _span_out('al_evidence_grid', out, spec, (), dev)
+    check(load().hual_al_evidence_grid(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, it.ctypes.data_as(ctypes.c_void_p), A,
+                                       ep.ctypes.data_as(ctypes.c_void_p), B, *[ptr(o) for o in out], stream_ptr()))
     return tuple(out)
 
 

@@ -796,6 +796,44 @@ int hual_al_session(const hual_al_set* set, const float* s0, const float* e0, co
                     int8_t* answer, float* q_asked, float* gain, float* entropy, int32_t* n_asked, int32_t* stop_reason, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Calibrating the span posterior by the evidence of the answers (HUAL_ABI_VERSION unchanged: one new symbol, nothing else moved).  Every
+ * launch above takes the softmaxes of s0 / e0 at face value and eps as the caller's number.  With a temperature tau,
+ *   L(tau, eps) = sum over the samples n of ln P(the answers of n | softmax(s0[n] / tau), softmax(e0[n] / tau), eps)
+ * is a proper likelihood of the pair (the policy that chose the questions depended on the answers only through earlier data: it drops
+ * out); hual_al_evidence_grid evaluates it on a grid of A x B pairs in one call, for the caller to maximise.
+ *
+ * Inputs: the set with its answers; s0 / e0 f32 [N, ld], the UNTILTED, unscaled deterministic logits; sel / nsel as in
+ * hual_al_mbr_label (sel NULL: all N samples, nsel >= 1 all the same; an id outside [0, N) writes nothing and is not summed; a repeated
+ * id writes the same values twice and is summed twice); inv_tau HOST f32 [A], 1 <= A <= 32, the reciprocal temperatures, each finite and
+ * > 0; eps HOST f32 [B], 1 <= B <= 16, each in (0, 0.5].  Both arrays are read before the call returns.
+ *
+ * Per selected sample n and cell c = a * B + b: the row is x_s[i] = s0[n][i] * inv_tau[a], x_e[j] = e0[n][j] * inv_tau[a] - one float32
+ * product, rounded on its own (never fused with the softmax's subtraction behind it): the row `s0 * inv_tau` of a float32 tensor
+ * library.  T, v, p_s, p_e (bit for bit the family's softmaxes of that row), w, Z, the ignored active points, G(t), r = (1 - eps[b]) /
+ * eps[b] and the poison rule are hual_al_noisy_tilt's on that row and that eps.
+ *  - table f64 [N, A * B]: table[n][c] = hual_al_noisy_tilt's log_evidence of that row, ln(sum over i <= j < v of w(i,j) * prod_k
+ *    lik_k(i,j)) - ln Z, in float64 and NOT rounded to float32.  It is computed as sum_j p_e[j] r^G(j) sum_{i <= j} p_s[i] r^-G(i-1) with
+ *    every partial sum held as a pair (mantissa, integer exponent of r) against the larger exponent of its two operands - a term of
+ *    mantissa 0 carries no exponent -, the inner sum a prefix scan: O(v + answers) float64 operations per cell, no exponential per
+ *    (start, end) pair, and 64 answers at eps = 1e-6 neither overflow nor underflow the spans that carry the sum.  ln eps, ln(1 - eps)
+ *    and ln r are the host's float64 values of the float32 eps widened.
+ *  - a poisoned cell - v < 1, a NaN logit at t < v, T > 256, or at THIS temperature a Z that is not a positive finite number (a
+ *    scaled softmax that went one-hot with the start behind the end; a product that overflowed) - is a quiet NaN.
+ *  - status i32 [N]: 1 if every one of the row's A * B cells is finite, else 0.
+ *  - a sample without an answer inside [0, v) is live, and every cell that is not poisoned is exactly 0.
+ *  - rows of samples that are not selected are not written, in table or status.
+ * Then, on the same stream: total f64 [A * B], total[c] = the float64 sum of table[sel[k]][c] over the entries k = 0 .. nsel - 1 whose id
+ * lies in [0, N) and whose status is 1 - a row with one poisoned cell is left out of EVERY cell, so that all totals sum the same rows
+ * and their differences are likelihood ratios - in a fixed order: two calls give the same bits.  counts i32 [4]: the rows summed; the
+ * answers inside [0, v) of those rows; the entries with an id in [0, N) left out; the first cell of maximal total, -1 if no row was
+ * summed.
+ * Three launches (one workgroup per selected sample; one per cell; one wave).  Allocates nothing and does not synchronise: capturable
+ * in a hipGraph.  Argument errors (a null pointer other than sel, N < 1, nsel < 1, ld outside [2, 1024], A outside [1, 32], B outside
+ * [1, 16], an inv_tau that is not finite and > 0, an eps outside (0, 0.5] or NaN) return HUAL_ERR_INVALID before any HIP call. */
+int hual_al_evidence_grid(const hual_al_set* set, const float* s0, const float* e0, const int32_t* sel, int nsel, const float* inv_tau,
+                          int A, const float* eps, int B, double* table, int32_t* status, double* total, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
