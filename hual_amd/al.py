@@ -101,16 +101,40 @@ def get_coff(task, I):
 STAT_NAMES = "the statistic is 'range' or 'std', or - from a McBank with info=True - 'bald', 'entropy' or 'expected_entropy'"
 
 
+def check_passes(passes):
+    """McBank's passes argument -> Kmax, 0 for None; raises ValueError"""
+    if passes is None:
+        return 0
+    try:
+        ok = not isinstance(passes, bool) and int(passes) == passes and 1 <= int(passes) <= lib.AL_ENS_MAX_K
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('McBank: passes is None or an integer in [1, %d]' % lib.AL_ENS_MAX_K)
+    return int(passes)
+
+
+def check_part_passes(part, Kmax):
+    """the rows of McBank.export_rows against the bank that imports them: both keep the passes, as many, or neither does"""
+    have = int(part['pass_s'].shape[0]) if 'pass_s' in part else 0
+    if have != Kmax:
+        raise lib.HualError('McBank.import_rows: the rows keep passes=%s and the bank passes=%s - build both banks with the same passes='
+                            % (have or None, Kmax or None))
+
+
 class McBank:
     """Per-sample statistics of K stochastic forwards over a training set of N samples, resident on the device (hual_al_bank):
     tlen i32 [N]; the deterministic logits s0 / e0 f32 [N, ld]; per head (0 = start, 1 = end) the minimum, maximum, Welford mean and
     sum of squared deviations of the per-frame probabilities, stats f32 [2, 4, N, ld] = [head, (lo, hi, mean, m2)].
     K: the number of stochastic passes folded so far (the largest k seen since the last k = 1).
     info=True adds ent f32 [2, N, ld] (hual_al_info): per head the running mean of the passes' binary entropy h2(p_k) in bits, folded by
-    the same launch (hual_al_mc_fold_info) - what the statistics 'bald', 'entropy' and 'expected_entropy' are read from."""
+    the same launch (hual_al_mc_fold_info) - what the statistics 'bald', 'entropy' and 'expected_entropy' are read from.
+    passes=Kmax (1..16; None: no such buffer, every launch and bit as without the argument) keeps the passes themselves beside their
+    statistics: pass_s / pass_e f32 [Kmax, N, ld], plane k - 1 the raw logits of stochastic pass k - what the span posterior's model
+    average reads (hual_al_ensemble_query / hual_al_ensemble_label, LabelUpdater.set_ensemble)."""
     FIELDS = ('lo', 'hi', 'mean', 'm2')
 
-    def __init__(self, N, ld, device='cuda:0', info=False):
+    def __init__(self, N, ld, device='cuda:0', info=False, passes=None):
         if not torch.cuda.is_available():
             raise lib.HualError('McBank needs a GPU: the HIP path has no CPU fallback')
         if N < 1 or not 2 <= ld <= 1024:
@@ -123,12 +147,15 @@ class McBank:
         self.e0 = torch.zeros(N, ld, device=self.dev)
         self.stats = torch.zeros(2, 4, N, ld, device=self.dev)
         self.ent = torch.zeros(2, N, ld, device=self.dev) if info else None
+        self.Kmax = check_passes(passes)
+        self.pass_s = torch.zeros(self.Kmax, N, ld, device=self.dev) if self.Kmax else None
+        self.pass_e = torch.zeros(self.Kmax, N, ld, device=self.dev) if self.Kmax else None
         self._bind()
 
     @classmethod
-    def for_dataset(cls, dataset, device='cuda:0', info=False):
+    def for_dataset(cls, dataset, device='cuda:0', info=False, passes=None):
         """a bank over a DeviceDataset: one row per sample, as wide as its longest clip"""
-        return cls(len(dataset), max(2, int(np.max(dataset.vlen_h))), device=device, info=info)
+        return cls(len(dataset), max(2, int(np.max(dataset.vlen_h))), device=device, info=info, passes=passes)
 
     def _bind(self):
         a, st = lib._addr, self.stats
@@ -165,7 +192,10 @@ class McBank:
 
     def fold(self, ids, v_len, start_logits, end_logits, k, _checked=False):
         """one forward's logits f32 [B, T_b] (device) into the rows `ids` (host array, list or tensor); k = 0: the deterministic pass,
-        k = 1..K: the stochastic ones, in order.  Enqueued on the current stream."""
+        k = 1..K: the stochastic ones, in order.  Enqueued on the current stream.  A bank with passes=Kmax also keeps the logits of
+        pass k >= 1 in plane k - 1 (rows ids, columns [0, T_b)); k > Kmax raises before anything is folded."""
+        if self.pass_s is not None and int(k) > self.Kmax:
+            raise lib.HualError('McBank.fold: pass %d of a bank that keeps passes=%d' % (int(k), self.Kmax))
         if not _checked:
             ids = self.rows(ids)
         s, e = start_logits, end_logits
@@ -184,6 +214,10 @@ class McBank:
                                                 lib.stream_ptr()))
         if k >= 1:
             self.K = int(k) if k == 1 else max(self.K, int(k))
+            if self.pass_s is not None:                          # (plumbing: one indexed copy per head)
+                rows = ids.long()
+                self.pass_s[int(k) - 1, rows, :T] = s
+                self.pass_e[int(k) - 1, rows, :T] = e
 
     def uncert(self, K=None, stat='range'):
         """the model-uncertainty term f32 [N, ld] of every frame as hual_al_score_mc ('range', 'std') or hual_al_score_info ('bald',
@@ -217,12 +251,15 @@ class McBank:
                     e0=self.e0[i].cpu().numpy(), stats=self.stats[:, :, i].cpu().numpy(), K=self.K)
         if self.ent is not None:
             part['ent'] = self.ent[:, i].cpu().numpy()
+        if self.pass_s is not None:
+            part['pass_s'], part['pass_e'] = self.pass_s[:, i].cpu().numpy(), self.pass_e[:, i].cpu().numpy()
         return part
 
     def import_rows(self, part):
         if ('ent' in part) != (self.ent is not None):
             raise lib.HualError("McBank.import_rows: the rows %s 'ent' and the bank %s - build both banks with the same info="
                                 % (('hold', 'has none') if 'ent' in part else ('lack', 'folds it')))
+        check_part_passes(part, self.Kmax)
         if len(part['ids']) == 0:
             return
         i = torch.from_numpy(part['ids']).to(self.dev)
@@ -232,6 +269,9 @@ class McBank:
         self.stats[:, :, i] = torch.from_numpy(part['stats']).to(self.dev)
         if self.ent is not None:
             self.ent[:, i] = torch.from_numpy(part['ent']).to(self.dev)
+        if self.pass_s is not None:
+            self.pass_s[:, i] = torch.from_numpy(part['pass_s']).to(self.dev)
+            self.pass_e[:, i] = torch.from_numpy(part['pass_e']).to(self.dev)
         self.K = max(self.K, int(part['K']))
 
 
@@ -525,6 +565,38 @@ def check_calibration(temperature, calibrate, observe_by, acquire_by, renew_by, 
     return temperature
 
 
+def check_bank_planes(bank, K=None):
+    """raises unless `bank` keeps the logits of its K (default: bank.K) stochastic passes"""
+    K = int(getattr(bank, 'K', 0) if K is None else K)
+    if bank is None or getattr(bank, 'pass_s', None) is None:
+        raise ValueError("the ensemble posterior needs a McBank that keeps its passes: build the bank with passes=K")
+    if not 1 <= K <= bank.Kmax or K > bank.K:
+        raise ValueError('the ensemble posterior needs 1 <= mc_samples <= the passes the bank holds (K = %d, passes = %d)' % (bank.K, bank.Kmax))
+
+
+POSTERIOR = ('deterministic', 'ensemble')
+
+
+def check_posterior(posterior, bank, mc_samples, rank_by, observe_by, renew_by, acquire_by, soft_out, questions_per_clip, calibrate):
+    """the posterior argument of update_labels / run_round against the switches it depends on; raises ValueError"""
+    if posterior not in POSTERIOR:
+        raise ValueError("posterior: 'deterministic' or 'ensemble'")
+    if posterior != 'ensemble':
+        if rank_by == 'span_bald':
+            raise ValueError("rank_by='span_bald' is the ensemble's score: it needs posterior='ensemble'")
+        return
+    check_bank_planes(bank, mc_samples)
+    if acquire_by == 'label_gain':
+        raise ValueError("posterior='ensemble' with acquire_by='label_gain' is not offered: the label gain has no ensemble form")
+    if questions_per_clip != 1:
+        raise ValueError("posterior='ensemble' with questions_per_clip > 1 is not offered: sessions have no ensemble form")
+    if calibrate is not None:
+        raise ValueError("posterior='ensemble' with calibrate is not offered: the evidence grid has no ensemble form")
+    if observe_by != 'info_gain' and renew_by != 'posterior' and soft_out is None and rank_by != 'span_bald':
+        raise ValueError("posterior='ensemble' changes the span posterior: switch on one of its readers (observe_by='info_gain', "
+                         "renew_by='posterior', soft_out, rank_by='span_bald')")
+
+
 class LabelUpdater:
     """Device-side state of one update_label round: the logits of the results pkl as [N, ld] matrices, the active
     points as CSR.  score() and renew() are one launch each.
@@ -577,11 +649,14 @@ class LabelUpdater:
         self._finish(N, ld, tlen, vlen, torch.from_numpy(tlen).to(self.dev), aps)
 
     @classmethod
-    def from_bank(cls, bank, vlen, aps, K=None, stat='range'):
+    def from_bank(cls, bank, vlen, aps, K=None, stat='range', ensemble=False):
         """score straight from a McBank (no upload, no logits matrix).  vlen: host [N] valid frames; K: the stochastic passes the bank
         holds (default: bank.K); stat: 'range' or 'std' (hual_al_score_mc), or 'bald', 'entropy' or 'expected_entropy' (hual_al_score_info;
-        the bank was built with info=True)."""
+        the bank was built with info=True).  ensemble=True: the span posterior's launches read the model average over the bank's K
+        kept passes (set_ensemble on its planes; the bank was built with passes >= K)."""
         bank.check_stat(stat)
+        if ensemble:
+            check_bank_planes(bank, K)
         self = cls.__new__(cls)
         self._lib = lib.load()
         self.dev = bank.dev
@@ -592,8 +667,13 @@ class LabelUpdater:
         self._s0, self._e0, self.bank_c = bank.s0, bank.e0, bank.c
         self._source(None, bank, int(bank.K if K is None else K), stat)
         if self.K < (1 if stat in ('entropy', 'expected_entropy') else 2):
+            if ensemble and self.K == 1:
+                raise ValueError("the ensemble posterior itself runs on K = 1 pass, but the round's score reads the statistic '%s', which "
+                                 "needs two: use 'entropy' or 'expected_entropy' (a bank with info=True), or K >= 2" % stat)
             raise ValueError('the bank holds K = %d stochastic passes: a spread needs two' % self.K)
         self._finish(bank.N, bank.ld, tlen, vlen, bank.tlen, aps)
+        if ensemble:
+            self.set_ensemble(bank.pass_s[:self.K], bank.pass_e[:self.K])
         return self
 
     def _source(self, logits, bank, K, stat):
@@ -611,6 +691,7 @@ class LabelUpdater:
         self.uncert_video = torch.zeros(N, device=self.dev)
         self.observe = torch.zeros(N, device=self.dev, dtype=torch.int32)
         self.temperature, self._inv_tau, self._scaled, self._last_eps = None, None, None, None
+        self._ens, self._ens_scaled, self._ens_tilt = None, None, None
         self.set_active_points(aps)
 
     def set_active_points(self, aps):
@@ -628,6 +709,7 @@ class LabelUpdater:
                                    p(self.ap_idx).value, p(self.ap_pos).value)
         self.tilt_eps = None                                     # (a tilt holds the answers it was made with)
         self._scaled = None                                      # (and the scaled rows go with it: both are rebuilt on demand)
+        self._ens_tilt = None
 
     def set_temperature(self, tau):
         """the temperature of the span posterior: None or 1.0 (the default) - _rows, tilt and session read the deterministic logits
@@ -647,6 +729,7 @@ class LabelUpdater:
             raise ValueError('the temperature must be None or a finite number > 0')
         if inv != self._inv_tau:
             self.tilt_eps, self._scaled = None, None
+            self._ens_scaled, self._ens_tilt = None, None
         self.temperature, self._inv_tau = (None if inv is None else tau), inv
 
     def _logits(self):
@@ -658,12 +741,69 @@ class LabelUpdater:
             self._scaled = ((self._s0 * k).contiguous(), (self._e0 * k).contiguous())
         return self._scaled
 
+    def set_ensemble(self, pass_s, pass_e):
+        """the span posterior as a Bayesian model average: pass_s / pass_e f32 [K, N, ld] on the updater's device, 1 <= K <= 16, the
+        logits of K stochastic passes (a McBank's planes).  While set, query(), span_marginals() and mbr_label() read the mixture of
+        the passes' posteriors, each weighted by its evidence of the answers (hual_al_ensemble_query / hual_al_ensemble_label) -
+        under noise=eps behind one hual_al_noisy_tilt per plane -, set_temperature scales the planes as it scales the deterministic
+        logits, and label_gain(), session(), calibrate() and evidence_grid() raise: they have no ensemble form.  None (both): off
+        again - every launch and bit as it was.  score() and renew() never read it."""
+        if (pass_s is None) != (pass_e is None):
+            raise ValueError('set_ensemble: pass_s and pass_e are both tensors or both None')
+        if pass_s is not None:
+            ok = (torch.is_tensor(pass_s) and torch.is_tensor(pass_e) and pass_s.dtype == torch.float32 and pass_e.dtype == torch.float32
+                  and pass_s.dim() == 3 and pass_e.shape == pass_s.shape and tuple(pass_s.shape[1:]) == (self.N, self.ld)
+                  and 1 <= pass_s.shape[0] <= lib.AL_ENS_MAX_K and pass_s.is_contiguous() and pass_e.is_contiguous()
+                  and pass_s.device == self.dev and pass_e.device == self.dev)
+            if not ok:
+                raise lib.HualError('set_ensemble: pass_s / pass_e must be contiguous float32 [K, N, ld] = [1..%d, %d, %d] on the updater\'s device'
+                                    % (lib.AL_ENS_MAX_K, self.N, self.ld))
+        self._ens = None if pass_s is None else (pass_s, pass_e)
+        self._ens_scaled, self._ens_tilt = None, None
+
+    def _no_ensemble(self, what):
+        if self._ens is not None:
+            raise lib.HualError('%s has no ensemble form: call set_ensemble(None, None) first' % what)
+
+    def _free_set(self):
+        """a hual_al_set over the same vlen / tlen WITHOUT answers: what the family's launches take beside tilted rows"""
+        if getattr(self, '_free', None) is None:
+            self._free = (torch.zeros(self.N + 1, dtype=torch.int32, device=self.dev), torch.zeros(1, dtype=torch.int32, device=self.dev),
+                          torch.zeros(1, dtype=torch.int8, device=self.dev))
+        p = lib.ptr
+        self.free_set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, *[p(x).value for x in self._free])
+        return self.free_set
+
+    def _ens_rows(self, noise):
+        """(set, pass_s, pass_e, logw) an ensemble launch reads: the updater's set and the planes (under a temperature their float32
+        products with 1 / tau) and no prior weight; or under noise = eps the set without answers, every plane tilted by eps
+        (hual_al_noisy_tilt, one launch per plane) and the planes' log_evidence rows [K, N] as the weights' logarithms - pass k's
+        evidence of the noisy answers is exactly its weight"""
+        ps, pe = self._ens
+        if self._inv_tau is not None:
+            if self._ens_scaled is None:
+                k = float(self._inv_tau)
+                self._ens_scaled = ((ps * k).contiguous(), (pe * k).contiguous())
+            ps, pe = self._ens_scaled
+        if noise is None:
+            return self.set, ps, pe, None
+        eps = check_noise(noise)
+        if self._ens_tilt is None or self._ens_tilt[0] != eps:
+            K = ps.shape[0]
+            st, et, lev = torch.zeros_like(ps), torch.zeros_like(pe), torch.empty(K, self.N, device=self.dev)
+            for k in range(K):
+                lib.al_noisy_tilt(self.set, ps[k], pe[k], self.tlen_h, eps, out=(st[k], et[k], lev[k]))
+            self._ens_tilt = (eps, st, et, lev)
+            self._last_eps = eps
+        return (self._free_set(),) + self._ens_tilt[1:]
+
     def evidence_grid(self, taus, eps, sel=None):
         """ln P(the set's answers | softmax(s0 / tau), softmax(e0 / tau), eps) per sample on the grid taus x eps and its sum over the
         set (hual_al_evidence_grid, lib.al_evidence_grid) on the updater's set and UNSCALED deterministic logits, whatever
         set_temperature holds.  taus: 1 to 32 temperatures > 0, handed on as float32(1 / tau); eps: 1 to 16 error rates in (0, 0.5];
         sel: None or the sample ids (numpy).  Leaves and returns (ev_table f64 [N, A * B], ev_status i32 [N], ev_total f64 [A * B],
         ev_counts i32 [4]) as device tensors."""
+        self._no_ensemble('evidence_grid()')
         inv = np.array([np.float32(1.0 / float(t)) for t in np.asarray(taus, dtype=np.float64).reshape(-1)], dtype=np.float32)
         sel_d = None if sel is None else torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
         self.ev_table, self.ev_status, self.ev_total, self.ev_counts = lib.al_evidence_grid(
@@ -686,6 +826,7 @@ class LabelUpdater:
         geometric-mean likelihood of an answer, at_default = the total at (1, at_eps) (None without an at_eps), rows, answers,
         excluded (of the last grid: a row poisoned at one of a grid's temperatures is left out of that whole grid), and grids = every
         launched (taus, eps, totals [A, B]) as numpy arrays."""
+        self._no_ensemble('calibrate()')
         rows = np.arange(self.N) if sel is None else np.asarray(sel, dtype=np.int64)
         if rows.ndim != 1 or rows.size < 1 or rows.min() < 0 or rows.max() >= self.N:
             raise ValueError('calibrate: sel holds sample ids in [0, N)')
@@ -745,11 +886,7 @@ class LabelUpdater:
         what the family's launches take beside the tilted rows) and tilt_eps; set_active_points invalidates them."""
         eps = check_noise(eps)
         self.s_t, self.e_t, self.log_evidence = lib.al_noisy_tilt(self.set, *self._logits(), self.tlen_h, eps)
-        if getattr(self, '_free', None) is None:
-            self._free = (torch.zeros(self.N + 1, dtype=torch.int32, device=self.dev), torch.zeros(1, dtype=torch.int32, device=self.dev),
-                          torch.zeros(1, dtype=torch.int8, device=self.dev))
-        p = lib.ptr
-        self.free_set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, *[p(x).value for x in self._free])
+        self._free_set()
         self.tilt_eps = self._last_eps = eps
 
     def _rows(self, noise):
@@ -773,12 +910,26 @@ class LabelUpdater:
         noise=eps: the posterior under an annotator who errs with probability eps - the same launch on the tilted rows (tilt()) and
         the set without answers.  gain / query_gain are then the information a NOISY answer carries, h2(eps + (1 - 2 eps) q) - h2(eps)
         bits, from incl in float64, stored as float32 (frames=True is needed); query_point stays the kernel's - the same maximiser,
-        q nearest 1/2 -; agree is None: log_evidence (tilt()) is the quantity to read."""
+        q nearest 1/2 -; agree is None: log_evidence (tilt()) is the quantity to read.
+        With an ensemble set (set_ensemble) the same fields are read from the model average over the passes (hual_al_ensemble_query,
+        one launch; under noise behind one tilt per plane): post_entropy is the mixture's, agree is None, and the call also leaves and
+        returns - as a dict - weight (f32 [N, K]), log_evidence (f32 [N], ln P(the answers | the ensemble); the attribute is
+        ens_log_evidence), expected_entropy and span_bald (f32 [N], bits).  Without one it returns None."""
         if noise is not None and not frames:
             raise ValueError('query(noise=) computes the gain of a noisy answer from incl: it needs frames=True')
-        aset, s, e = self._rows(noise)
-        (self.incl, self.gain, self.query_point, self.query_gain, self.post_entropy,
-         self.agree) = lib.al_query(aset, s, e, self.tlen_h, frames=frames)
+        ens = None
+        if self._ens is not None:
+            aset, ps, pe, logw = self._ens_rows(noise)
+            (self.weight, self.ens_log_evidence, self.incl, self.gain, self.query_point, self.query_gain, _, _, self.post_entropy,
+             self.expected_entropy, self.span_bald, self.ens_status) = lib.al_ensemble_query(aset, ps, pe, self.tlen_h, logw=logw,
+                                                                                             frames=frames, marginals=False)
+            self.agree = None
+            ens = dict(weight=self.weight, log_evidence=self.ens_log_evidence, expected_entropy=self.expected_entropy,
+                       span_bald=self.span_bald)
+        else:
+            aset, s, e = self._rows(noise)
+            (self.incl, self.gain, self.query_point, self.query_gain, self.post_entropy,
+             self.agree) = lib.al_query(aset, s, e, self.tlen_h, frames=frames)
         if noise is not None:
             eps = check_noise(noise)
 
@@ -792,6 +943,7 @@ class LabelUpdater:
             self.gain = torch.where(live[:, None], ch, torch.zeros_like(ch)).float()
             self.query_gain = torch.where(live, at, torch.full_like(at, -1.0)).float()
             self.agree = None
+        return ens
 
     def session(self, gt_idx, max_questions, stop_entropy=None, min_gain=0.0, noise=None, flips=None, budget=None, sel=None):
         """an annotation session per sample (hual_al_session, one launch): up to max_questions (1..16) questions, each the frame of
@@ -807,6 +959,7 @@ class LabelUpdater:
         extended lists with set_active_points (which invalidates a tilt).  A sample whose answered points plus budget exceed
         lib.AL_SESSION_MAX_POINTS is refused here, on the host, where the lists are known.
         Returns numpy (asked, answers, n_asked)."""
+        self._no_ensemble('session()')
         Q = int(max_questions)
         if not 1 <= Q <= lib.AL_SESSION_MAX_Q:
             raise ValueError('session: max_questions must lie in [1, %d]' % lib.AL_SESSION_MAX_Q)
@@ -850,6 +1003,7 @@ class LabelUpdater:
         Leaves gain (f32 [N, ld]; None with frames=False; in place of the row of bits query() leaves under that name), ask_point
         (i32 [N]), ask_gain and label_value (f32 [N]) as device tensors.
         noise=eps: the gain from a NOISY answer (hual_al_label_gain_noisy, one launch) on the rows tilted by eps (tilt())."""
+        self._no_ensemble('label_gain()')
         if noise is None:
             out = lib.al_label_gain(*self._rows(None), self.tlen_h, cand=cand, frames=frames)
         else:
@@ -862,7 +1016,13 @@ class LabelUpdater:
         over the whole set) on the updater's set and deterministic logits - of the records or of the bank, as query().  Leaves y_start,
         y_end (f32 [N, ld]) and marg_status (i32 [N]; 1 = live) as device tensors.
         noise=eps: the marginals of the posterior under an annotator who errs with probability eps - the same launch on the rows
-        tilted by eps (tilt()) and the set without answers."""
+        tilted by eps (tilt()) and the set without answers.
+        With an ensemble set: the marginals of the model average, sum_k w_k of the passes' (hual_al_ensemble_query, one launch)."""
+        if self._ens is not None:
+            aset, ps, pe, logw = self._ens_rows(noise)
+            o = lib.al_ensemble_query(aset, ps, pe, self.tlen_h, logw=logw, frames=False, marginals=True)
+            self.y_start, self.y_end, self.marg_status = o[6], o[7], o[11]
+            return
         aset, s, e = self._rows(noise)
         self.y_start, self.y_end, self.marg_status = lib.al_span_marginals(aset, s, e, self.tlen_h)
 
@@ -872,9 +1032,14 @@ class LabelUpdater:
         bank, as query().  old_idx: int [N, 2].  Returns numpy (new_idx i32 [N, 2], conf f32 [N], old_conf f32 [N]): the label, its
         expected tIoU and the old span's; rows outside `sel`, and rows that give no label, hold -1.
         noise=eps: the label under an annotator who errs with probability eps - the same launch on the rows tilted by eps (tilt())
-        and the set without answers: any span of the clip, and only a poisoned row gives none."""
+        and the set without answers: any span of the clip, and only a poisoned row gives none.
+        With an ensemble set: the label of maximal expected tIoU under the model average (hual_al_ensemble_label, one launch)."""
         sel_d = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
         old_d = torch.from_numpy(np.ascontiguousarray(old_idx, dtype=np.int32)).to(self.dev)
+        if self._ens is not None:
+            aset, ps, pe, logw = self._ens_rows(noise)
+            new_d, conf, old_conf = lib.al_ensemble_label(aset, ps, pe, self.tlen_h, logw=logw, sel=sel_d, old_idx=old_d)
+            return new_d.cpu().numpy(), conf.cpu().numpy(), old_conf.cpu().numpy()
         aset, s, e = self._rows(noise)
         new_d, conf, old_conf = lib.al_mbr_label(aset, s, e, self.tlen_h, sel=sel_d, old_idx=old_d)
         return new_d.cpu().numpy(), conf.cpu().numpy(), old_conf.cpu().numpy()
@@ -914,6 +1079,7 @@ def check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by):
 
 
 RANK_BY = ('uncert_video', 'span_risk')
+RANK_BY_ENSEMBLE = ('span_bald',)      # with posterior='ensemble' only (check_posterior)
 OBSERVE_BY = ('uncert_frame', 'info_gain')
 RENEW_BY = ('heuristic', 'posterior')
 ACQUIRE_BY = (None, 'label_gain')
@@ -929,7 +1095,8 @@ def span_risk(last_prop):
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
                   rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
-                  answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None):
+                  answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None,
+                  posterior='deterministic'):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -991,7 +1158,19 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     error rate of maximal evidence, three launches of hual_al_evidence_grid); where the fit exists (at least 32 answers) its tau and
     eps take the place of temperature and answer_noise for the round's posterior readers, otherwise the given values stand.  The same
     readers must be on.  The debug dict gains 'calibration' (the fit's dict, or None).  With both arguments off nothing changes.
+    posterior: 'deterministic' (the span posterior of the one deterministic forward: nothing changes), or 'ensemble' - the posterior's
+    readers (observe_by='info_gain', renew_by='posterior', soft_out; at least one must be on, or rank_by='span_bald') then read the
+    Bayesian model average over the K stochastic passes `bank` keeps (a McBank built with passes >= K, K = mc_samples >= 1, default
+    bank.K), every pass weighted by its evidence of the answers (LabelUpdater.set_ensemble: hual_al_ensemble_query /
+    hual_al_ensemble_label in place of hual_al_query, hual_al_span_marginals and hual_al_mbr_label; with answer_noise behind one tilt
+    per pass; temperature scales the passes too).  rank_by='span_bald' (ensemble only) ranks the samples by span_bald - the mutual
+    information between the span and the dropout mask under the answers so far, bits -, largest first, the same stable argsort, the same
+    half selected; rows that give none come last.  acquire_by='label_gain', questions_per_clip > 1 and calibrate have no ensemble form
+    and are refused.  Under answer_noise the deterministic logits are not tilted and the debug dict has no 'log_evidence'.  The debug
+    dict gains 'weight' (float32 [N, K]), 'ens_log_evidence', 'expected_entropy' and 'span_bald' (float32
+    [N]) as the query left them: on the answers of the earlier rounds.
     """
+    check_posterior(posterior, bank, mc_samples, rank_by, observe_by, renew_by, acquire_by, soft_out, questions_per_clip, calibrate)
     Q = check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by)
     if soft_out is not None and not isinstance(soft_out, dict):
         raise ValueError('soft_out: None or a dict to receive y1, y2, live and answered')
@@ -1013,8 +1192,8 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
             ok = False
         if not ok:
             raise ValueError('annotator_flip: None or (rate in [0, 1], numpy.random.Generator)')
-    if rank_by not in RANK_BY:
-        raise ValueError("rank_by: 'uncert_video' or 'span_risk'")
+    if rank_by not in RANK_BY and not (posterior == 'ensemble' and rank_by in RANK_BY_ENSEMBLE):
+        raise ValueError("rank_by: 'uncert_video' or 'span_risk' ('span_bald' with posterior='ensemble')")
     if observe_by not in OBSERVE_BY:
         raise ValueError("observe_by: 'uncert_frame' or 'info_gain'")
     if renew_by not in RENEW_BY:
@@ -1035,7 +1214,8 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     # of each, so the relative order between the two kinds does not matter
     aps = [[(f, True) for f in r[4]['pos_idx']] + [(f, False) for f in r[4]['neg_idx']] for r in data_old]
     if bank is not None:
-        up = LabelUpdater.from_bank(bank, [p['v_len'] for p in last_prop], aps, K=mc_samples, stat=mc_stat)
+        up = LabelUpdater.from_bank(bank, [p['v_len'] for p in last_prop], aps, K=mc_samples, stat=mc_stat,
+                                    **(dict(ensemble=True) if posterior == 'ensemble' else {}))
     else:
         up = LabelUpdater(last_prop, aps, device=device)
     up.score(coff[6])
@@ -1048,10 +1228,13 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     uv = up.uncert_video.cpu().numpy()
     observe = up.observe.cpu().numpy()
     ask = observe
-    if observe_by == 'info_gain':
+    if observe_by == 'info_gain' or rank_by == 'span_bald':
         up.query(frames=return_debug or noise is not None, noise=noise)      # (before set_active_points: on the answers of the earlier rounds)
+    if observe_by == 'info_gain':
         ask = np.where(up.query_gain.cpu().numpy() > 0, up.query_point.cpu().numpy(), observe)
     order = np.argsort(uv if risk is None else risk, kind='stable')      # sorted(key=uncert_video), ties in sample order
+    if rank_by == 'span_bald':
+        order = np.argsort(-up.span_bald.cpu().numpy(), kind='stable')      # largest first, ties in sample order; rows at -1 last
     if acquire_by == 'label_gain':
         up.label_gain(frames=return_debug, noise=noise)          # (before set_active_points: on the answers of the earlier rounds)
         ask_gain = up.ask_gain.cpu().numpy()
@@ -1099,7 +1282,7 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
                 data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
                 aps[i].append((p, is_pos))
     up.set_active_points(aps)
-    if noise is not None:
+    if noise is not None and posterior != 'ensemble':            # (the ensemble's readers tilt the passes themselves, on demand)
         up.tilt(noise)                                           # (this round's answers included: what the launches below read)
     if soft_out is not None:
         up.span_marginals(noise=noise)
@@ -1126,13 +1309,13 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
         if observe_by == 'info_gain':
             dbg.update(query_point=up.query_point.cpu().numpy(), query_gain=up.query_gain.cpu().numpy(),
                        post_entropy=up.post_entropy.cpu().numpy(), observe_used=ask)
-            if noise is None:
+            if noise is None and up.agree is not None:               # (the ensemble has no agree: its ens_log_evidence is below)
                 dbg['agree'] = up.agree.cpu().numpy()
         if acquire_by == 'label_gain':
             dbg.update(ask_point=up.ask_point.cpu().numpy(), ask_gain=ask_gain, label_value=up.label_value.cpu().numpy(), observe_used=ask)
         if renew_by == 'posterior':
             dbg.update(label_conf=label_conf, old_conf=old_conf, renewed_by_posterior=by_posterior)
-        if noise is not None:
+        if noise is not None and posterior != 'ensemble':        # (the ensemble's own is 'ens_log_evidence')
             dbg['log_evidence'] = up.log_evidence.cpu().numpy()
         if annotator_flip is not None:
             dbg['flipped'] = flipped
@@ -1140,6 +1323,9 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
             dbg.update(sess)
         if calibrate is not None:
             dbg['calibration'] = fit
+        if posterior == 'ensemble' and (observe_by == 'info_gain' or rank_by == 'span_bald'):
+            dbg.update(weight=up.weight.cpu().numpy(), ens_log_evidence=up.ens_log_evidence.cpu().numpy(),
+                       expected_entropy=up.expected_entropy.cpu().numpy(), span_bald=up.span_bald.cpu().numpy())
         return data_old, dbg
     return data_old
 
@@ -1160,7 +1346,8 @@ def labels_from_times(data, vlens):
 def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, batch_size, lr, drop_rate, mc_dropout=0.5,
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
               observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
-              annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None):
+              annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None, posterior='deterministic',
+              rank_by='uncert_video'):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -1183,6 +1370,11 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     answers, n_asked, entropy_path, stop_reason).
     temperature / calibrate: the temperature of the round's span posterior, and its fit - with the annotator's error rate - to the
     answers of the earlier rounds by their evidence (update_labels); metrics['calibration'] holds the fit under calibrate.
+    posterior / rank_by: 'ensemble' reads the round's span posterior as the model average over the passes `bank` holds from the
+    PREVIOUS round's inference (update_labels), and rank_by='span_bald' ranks the samples by it.  It needs such a bank: build
+    McBank.for_dataset(dataset, passes=K) once, hand it with mc_samples=K to a first round under the default posterior (or to
+    infer_trainset), which fills it, and to every later round with posterior='ensemble'; without a filled bank that keeps its passes
+    the call raises ValueError before anything is touched.
     soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
     blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
     DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
@@ -1204,15 +1396,17 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
             raise ValueError("soft_labels: a record's v_len differs from the dataset's clip length")
         soft = {}
     t0 = time.perf_counter()
-    prev = bank if bank is not None and bank.K >= 2 else None
+    prev = bank if bank is not None and bank.K >= (1 if posterior == 'ensemble' else 2) else None
     Qn = check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by)      # (on every rank, before rank 0 goes its own way)
     check_calibration(temperature, calibrate, observe_by, acquire_by, renew_by, soft)
+    check_posterior(posterior, prev if posterior == 'ensemble' else None, None, rank_by, observe_by, renew_by, acquire_by, soft, Qn, calibrate)
     new_data = sessions = calibration = None
     if rank == 0:
         new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
                                  mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
                                  soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip,
                                  questions_per_clip=Qn, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate,
+                                 **(dict(posterior=posterior, rank_by=rank_by) if posterior == 'ensemble' else dict(rank_by=rank_by)),
                                  return_debug=Qn > 1 or calibrate is not None)
         if Qn > 1 or calibrate is not None:
             new_data, dbg = new_data

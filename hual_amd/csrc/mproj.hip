@@ -100,7 +100,10 @@ __device__ __forceinline__ void mproj_body(const MProjArgs& a, const DropCfg& dr
       if (F & MPF_A2) {      // no factor: the operand itself is read once more (a hit) and not used
         const float* p2 = st.A2 ? st.A2 : reinterpret_cast<const float*>(st.A);
         const int ld2 = st.A2 ? st.lda2 : st.lda;
-        n2[u] = ld4(p2 + row * ld2 + kc);
+        // (a bfloat16 operand has half the bytes that float32 offset assumes - rows of the upper half would be read behind the end
+        //  of the tensor -: its unused read goes to the weight image instead, 16 bytes per lane that always exist)
+        const bool half = (F & MPF_BF16) && st.a_bf16 && !st.A2;
+        n2[u] = ld4(half ? st.wimg + 4 * lane : p2 + row * ld2 + kc);
       }
     }
   };

@@ -173,6 +173,8 @@ def load():
     lib.hual_al_label_gain_noisy.argtypes = [P(hual_al_set), vp, vp, f32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_al_session.argtypes = [P(hual_al_set), vp, vp, vp, vp, i32, i32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_al_evidence_grid.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    lib.hual_al_ensemble_query.argtypes = [P(hual_al_set), vp, vp, i32, vp] + [vp] * 12 + [vp]
+    lib.hual_al_ensemble_label.argtypes = [P(hual_al_set), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_soft.argtypes = lib.hual_assemble_batch_carry.argtypes[:-1] + [P(hual_soft_labels), vp]
     lib.hual_assemble_batch_cursor_soft.argtypes = lib.hual_assemble_batch_cursor.argtypes[:-1] + [P(hual_soft_labels), vp]
     _lib = lib
@@ -554,6 +556,84 @@ def al_label_gain_noisy(aset, s_t, e_t, tlen, eps, sel=None, cand=None, frames=T
                                                ('ask_gain', (N,), torch.float32), ('value', (N,), torch.float32)], ('gain',), dev)
     check(load().hual_al_label_gain_noisy(ctypes.byref(aset), ptr(s_t), ptr(e_t), float(eps), ptr(sel), nsel, ptr(cand), M,
                                           *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)
+
+
+AL_ENS_MAX_K = 16      # passes per hual_al_ensemble_query / hual_al_ensemble_label launch
+
+
+def _ens_inputs(who, aset, pass_s, pass_e, tlen, logw):
+    """the gate of the two ensemble launches: _span_inputs' on every plane of pass_s / pass_e, contiguous f32 [K, N, ld] on one device,
+    1 <= K <= AL_ENS_MAX_K; logw None or contiguous f32 [K, N] there -> (K, N, ld, that device)"""
+    import torch
+    if pass_s.dim() != 3 or pass_e.shape != pass_s.shape or not 1 <= pass_s.shape[0] <= AL_ENS_MAX_K:
+        raise HualError('%s: pass_s / pass_e must both be [K, N, ld] with 1 <= K <= %d' % (who, AL_ENS_MAX_K))
+    if not pass_s.is_contiguous() or not pass_e.is_contiguous():
+        raise HualError('%s: pass_s / pass_e must be contiguous (plane stride N * ld)' % who)
+    K = int(pass_s.shape[0])
+    N, ld, dev = _span_inputs(who, aset, pass_s[0], pass_e[0], tlen)
+    if pass_e.device != dev:
+        raise HualError('%s: pass_s / pass_e must lie on one device' % who)
+    if logw is not None and (logw.dtype != torch.float32 or tuple(logw.shape) != (K, N) or not logw.is_contiguous() or logw.device != dev):
+        raise HualError('%s: logw must be a contiguous float32 [K, N] = [%d, %d] on the logits\' device' % (who, K, N))
+    return K, N, ld, dev
+
+
+AL_ENS_QUERY_OUT = ('weight', 'log_evidence', 'incl', 'gain', 'query_point', 'query_gain', 'y_start', 'y_end', 'post_entropy',
+                    'expected_entropy', 'span_bald', 'status')
+
+
+def al_ensemble_query(aset, pass_s, pass_e, tlen, logw=None, frames=True, marginals=True, out=None):
+    """the span posterior of every sample of the hual_al_set `aset` as the Bayesian model average over K stochastic passes, each
+    weighted by its evidence of the answered active points (hual_al_ensemble_query), one launch enqueued on the current stream.
+    pass_s / pass_e: the passes' logits f32 [K, N, ld] on the device, 1 <= K <= 16; tlen: the set's row lengths on the HOST - a row above
+    AL_QUERY_MAX_T frames is refused here, before the launch, as in al_query; logw: None or device f32 [K, N], a log prior weight per
+    pass and row (the K log_evidence rows of al_noisy_tilt, with the tilted planes and a set without answers: the noisy ensemble).
+    -> the tuple AL_ENS_QUERY_OUT names: weight f32 [N, K], log_evidence f32 [N], incl, gain f32 [N, ld] (None with frames=False),
+    query_point i32 [N], query_gain f32 [N], y_start, y_end f32 [N, ld] (None with marginals=False), post_entropy (of the mixture),
+    expected_entropy (the weighted mean of the passes') and span_bald (their difference: the mutual information between the span and
+    the dropout mask, bits) f32 [N], status i32 [N] (1 = live).  out: such a tuple of contiguous device tensors to write into instead
+    (incl / gain may be None, y_start / y_end both or neither); columns beyond a row's tlen keep what they held (0 in tensors allocated
+    here)."""
+    import torch
+    K, N, ld, dev = _ens_inputs('al_ensemble_query', aset, pass_s, pass_e, tlen, logw)
+    f32, i32 = torch.float32, torch.int32
+    spec = [('weight', (N, K), f32), ('log_evidence', (N,), f32), ('incl', (N, ld), f32), ('gain', (N, ld), f32), ('query_point', (N,), i32),
+            ('query_gain', (N,), f32), ('y_start', (N, ld), f32), ('y_end', (N, ld), f32), ('post_entropy', (N,), f32),
+            ('expected_entropy', (N,), f32), ('span_bald', (N,), f32), ('status', (N,), i32)]
+    if out is None:
+        off = (() if frames else ('incl', 'gain')) + (() if marginals else ('y_start', 'y_end'))
+        out = tuple(None if name in off else (torch.zeros if len(shape) == 2 and name != 'weight' else torch.empty)(shape, dtype=dt, device=dev)
+                    for name, shape, dt in spec)
+    else:
+        _span_out('al_ensemble_query', out, spec, ('incl', 'gain', 'y_start', 'y_end'), dev)
+        if (out[6] is None) != (out[7] is None):
+            raise HualError('al_ensemble_query: y_start and y_end are both given or both None')
+    check(load().hual_al_ensemble_query(ctypes.byref(aset), ptr(pass_s), ptr(pass_e), K, ptr(logw), *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)
+
+
+def al_ensemble_label(aset, pass_s, pass_e, tlen, logw=None, sel=None, old_idx=None, out=None):
+    """al_mbr_label under the same model average (hual_al_ensemble_label), one launch enqueued on the current stream: the span of
+    the consistent set of maximal expected temporal IoU R(a, e) = sum_k w_k R_k(a, e), the passes' values weighted as in
+    al_ensemble_query.  pass_s / pass_e, tlen and logw are al_ensemble_query's; sel, old_idx, out and the returned (new_idx i32 [N, 2],
+    conf f32 [N], old_conf f32 [N] or None) are al_mbr_label's."""
+    import torch
+    K, N, ld, dev = _ens_inputs('al_ensemble_label', aset, pass_s, pass_e, tlen, logw)
+    nsel = _span_sel('al_ensemble_label', sel, dev) or N
+    if old_idx is not None and (old_idx.dtype != torch.int32 or tuple(old_idx.shape) != (N, 2) or not old_idx.is_contiguous()
+                                or old_idx.device != dev):
+        raise HualError('al_ensemble_label: old_idx must be contiguous int32 [N, 2] on the logits\' device')
+    if out is None:
+        out = (torch.full((N, 2), -1, dtype=torch.int32, device=dev), torch.full((N,), -1.0, device=dev),
+               torch.full((N,), -1.0, device=dev) if old_idx is not None else None)
+    else:
+        if len(out) != 3 or out[0] is None or out[1] is None or (out[2] is None) != (old_idx is None):
+            raise HualError('al_ensemble_label: out is (new_idx, conf, old_conf); old_conf is None exactly when old_idx is')
+        _span_out('al_ensemble_label', out, [('new_idx', (N, 2), torch.int32), ('conf', (N,), torch.float32), ('old_conf', (N,), torch.float32)],
+                  ('old_conf',), dev)
+    check(load().hual_al_ensemble_label(ctypes.byref(aset), ptr(pass_s), ptr(pass_e), K, ptr(logw), ptr(sel), nsel, ptr(old_idx),
+                                        ptr(out[0]), ptr(out[1]), ptr(out[2]), stream_ptr()))
     return tuple(out)
 
 

@@ -834,6 +834,72 @@ int hual_al_evidence_grid(const hual_al_set* set, const float* s0, const float* 
                           int A, const float* eps, int B, double* table, int32_t* status, double* total, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The span posterior as a Bayesian model average over K stochastic passes (HUAL_ABI_VERSION unchanged: two new symbols, nothing else
+ * moved).  The launches above read the softmax of ONE deterministic forward at face value; a temperature (hual_al_evidence_grid) is
+ * one scalar for the whole set.  With K MC-dropout passes the predictive distribution over spans is the mixture P(i,j) = (1/K) sum_k
+ * P_k(i,j), every P_k the product form above, and conditioning on the answers keeps it a mixture: P(i,j | answers) = sum_k w_k
+ * P_k(i,j | answers), w_k proportional to pass k's evidence of the answers - a pass the annotator contradicts is down-weighted, which
+ * no scalar temperature can do.
+ *
+ * hual_al_ensemble_query: pass_s / pass_e f32 [K, N, ld], plane stride N * ld, 1 <= K <= 16 (a McBank's kept passes); logw f32 [K, N]
+ * (may be NULL: 0), a finite log prior weight per pass and row, widened to float64.  Per sample n of the set and pass k, with T, v,
+ * p_s,k, p_e,k, w, Z_k, the ignored active points, A and Z_A,k exactly as hual_al_query defines them on plane k (A depends on the
+ * answers and v only: the passes share it):
+ *  - u_k = ln(Z_A,k / Z_k) + logw[k][n]; a pass whose Z_A,k is not positive (or whose u_k is not finite) has w_k = 0; weight f32 [N, K]:
+ *    weight[n][k] = w_k = exp(u_k - max u) / sum_k exp(u_k - max u), float64, stored as float32; log_evidence f32 [N] = max u +
+ *    ln(sum_k exp(u_k - max u)) - ln K: ln P(the answers | the ensemble) with logw NULL.
+ *  - incl [N, ld] (may be NULL): sum_k w_k q_k(t), q_k hual_al_query's q of pass k before its rounding, float64, clamped to [0, 1],
+ *    stored as float32; gain [N, ld] (may be NULL): h2((float)incl); query_point / query_gain [N]: the first t < v of maximal gain and
+ *    that gain.  Columns [0, T) are written, 0 at t >= v; columns [T, ld) are not touched.
+ *  - y_start / y_end f32 [N, ld] (both, or both NULL): sum_k w_k of pass k's marginals as hual_al_span_marginals defines them; columns
+ *    as incl.
+ *  - expected_entropy f32 [N]: sum_k w_k H_k, H_k hual_al_query's post_entropy of pass k (its closed form, clamped at >= 0) in float64.
+ *    post_entropy f32 [N]: the entropy in bits of the mixture m(i,j) = sum_k (w_k / Z_A,k) p_s,k[i] p_e,k[j] over A, -sum m log2 m,
+ *    terms with m == 0 skipped, clamped at >= 0.  span_bald f32 [N] = max(0, post_entropy - expected_entropy), formed in float64
+ *    before rounding: the mutual information between the span and the dropout mask given the answers - BALD in the span's own
+ *    currency, a clip-level epistemic score.
+ *  - every sum over the passes is taken in ascending k, passes without weight skipped.  With K = 1 and logw NULL w_1 is exactly 1 and
+ *    incl, gain, query_point, query_gain, y_start, y_end and expected_entropy are the single-pass launches' outputs bit for bit.
+ *  - status i32 [N]: 1 for a live row, 0 otherwise.  A poisoned row - ANY of its K passes poisoned by hual_al_query's rule (v < 1, a
+ *    NaN logit at t < v, a Z_k that is not a positive finite number, T > 256) -: query_point = -1, query_gain = post_entropy =
+ *    expected_entropy = span_bald = -1.0f, log_evidence a quiet NaN, weight 0, the written columns [0, min(T, ld)) 0.  A contradictory
+ *    row - no pass has weight -: the same flags with log_evidence = -inf (the logarithm of an evidence of 0, as hual_al_query's agree
+ *    is 0).  A collapsed posterior is not an error: every gain is 0, expected_entropy is the passes' closed form
+ *    (0 within hual_al_query's rounding), post_entropy is 0 up to the float64 rounding of sum_k w_k (1e-15 bits) and span_bald is 0.
+ * The mixture has no product form, so its entropy is a walk over the pairs of A: all K pairs of factor rows sit in LDS (K * 2 * 256
+ * floats, 32 KB at K = 16), the four lanes of start i stride over the ends A allows it, float64 accumulation in a fixed order, one
+ * block sum, no atomics: at most K v^2 / 2 multiply-adds and v^2 / 2 logarithms per clip.  Everything else is the family's per-pass
+ * arithmetic (no walk).  One launch over the whole set, one workgroup per sample.  Allocates nothing and does not synchronise:
+ * capturable in a hipGraph.
+ * Argument errors (a null pointer other than logw, incl, gain and the y_start / y_end pair; exactly one of y_start and y_end null; K
+ * outside [1, 16]; N < 1; ld outside [2, 1024]) return HUAL_ERR_INVALID before any HIP call.
+ *
+ * The noisy annotator needs nothing new: run hual_al_noisy_tilt once per plane (a plane is a valid [N, ld] tensor), and pass the tilted
+ * planes, a set without answers (ap_off all 0) and the K log_evidence rows [K, N] as logw.  That IS the noisy ensemble posterior: on
+ * the tilted rows Z_A,k = Z_k, so u_k = log_evidence_k = ln P(the answers | pass k, eps) - pass k's evidence of the answers is exactly
+ * its weight -, the tilted product form is pass k's posterior given the noisy answers, and log_evidence is ln P(the answers | the
+ * ensemble, eps).  (A logw that is not finite only takes its pass's weight away.  A row hual_al_noisy_tilt poisoned has a NaN logw
+ * AND raw copies of the rows that made it poison: it is those rows, by hual_al_query's rule, that poison the row again here - a caller
+ * who hands in a NaN logw beside sound rows gets a pass without weight, and a contradictory row if no pass is left.) */
+int hual_al_ensemble_query(const hual_al_set* set, const float* pass_s, const float* pass_e, int K, const float* logw, float* weight,
+                           float* log_evidence, float* incl, float* gain, int32_t* query_point, float* query_gain, float* y_start,
+                           float* y_end, float* post_entropy, float* expected_entropy, float* span_bald, int32_t* status, void* stream);
+
+/* hual_al_mbr_label under the same model average.  set, pass_s, pass_e, K, logw, the weights w_k and the poisoned / contradictory rules
+ * are hual_al_ensemble_query's (one device function opens the row for both launches); sel / nsel, old_idx / old_conf, the flags of a
+ * row that gives no label (new_idx = (-1, -1), conf = old_conf = -1.0f) and the tie rule (the first maximal member of A in row-major
+ * order) are hual_al_mbr_label's.
+ *  - R(a, e) = sum_k w_k R_k(a, e), R_k hual_al_mbr_label's expected tIoU under pass k, float64, the passes in ascending k; new_idx
+ *    i32 [N, 2]: the member of A of maximal R; conf f32 [N]: that R, clamped to [0, 1]; old_conf f32 [N]: R of the old span.
+ * Per pass the IoU-weighted mass of a candidate is hual_al_mbr_label's four products of prefix and suffix sums; the walk over the
+ * ends e is shared and the passes are summed per candidate before the argmax: K times that launch's additions, one barrier per (e,
+ * pass).  One launch, one workgroup per selected sample.  Allocates nothing and does not synchronise: capturable in a hipGraph.
+ * Argument errors (a null pointer other than logw, sel, old_idx and old_conf; exactly one of old_idx and old_conf null; nsel < 1; K
+ * outside [1, 16]; N < 1; ld outside [2, 1024]) return HUAL_ERR_INVALID before any HIP call. */
+int hual_al_ensemble_label(const hual_al_set* set, const float* pass_s, const float* pass_e, int K, const float* logw, const int32_t* sel,
+                           int nsel, const int32_t* old_idx, int32_t* new_idx, float* conf, float* old_conf, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
