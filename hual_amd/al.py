@@ -67,6 +67,7 @@ ln P(answers | softmax(logits / tau), eps) (LabelUpdater.calibrate: hual_al_evid
 round's posterior readers use the fitted pair (LabelUpdater.set_temperature; temperature= hands one in).  Off by default: every launch,
 record and result is then what it was.
 """
+import collections
 import ctypes
 import math
 
@@ -545,26 +546,6 @@ def _zoom_axis(x, i, n, lo, hi):
     return np.geomspace(left, right, n) if right > left else np.array([left])
 
 
-def check_calibration(temperature, calibrate, observe_by, acquire_by, renew_by, soft_out):
-    """the two calibration arguments of update_labels / run_round against the switches they depend on -> the temperature as a float or
-    None; raises ValueError"""
-    if calibrate not in CALIBRATE:
-        raise ValueError("calibrate: None or 'evidence'")
-    if temperature is not None:
-        try:
-            ok = not isinstance(temperature, bool) and 0.0 < float(np.float32(1.0 / float(temperature))) < float('inf')
-        except (TypeError, ValueError, ZeroDivisionError):
-            ok = False
-        if not ok:
-            raise ValueError('temperature: None or a finite temperature > 0')
-        temperature = float(temperature)
-    if (temperature is not None or calibrate is not None) and observe_by != 'info_gain' and acquire_by != 'label_gain' \
-            and renew_by != 'posterior' and soft_out is None:
-        raise ValueError("%s changes the span posterior: switch on one of its readers (observe_by='info_gain', "
-                         "acquire_by='label_gain', renew_by='posterior', soft_out)" % ('calibrate' if calibrate is not None else 'temperature'))
-    return temperature
-
-
 def check_bank_planes(bank, K=None):
     """raises unless `bank` keeps the logits of its K (default: bank.K) stochastic passes"""
     K = int(getattr(bank, 'K', 0) if K is None else K)
@@ -572,29 +553,6 @@ def check_bank_planes(bank, K=None):
         raise ValueError("the ensemble posterior needs a McBank that keeps its passes: build the bank with passes=K")
     if not 1 <= K <= bank.Kmax or K > bank.K:
         raise ValueError('the ensemble posterior needs 1 <= mc_samples <= the passes the bank holds (K = %d, passes = %d)' % (bank.K, bank.Kmax))
-
-
-POSTERIOR = ('deterministic', 'ensemble')
-
-
-def check_posterior(posterior, bank, mc_samples, rank_by, observe_by, renew_by, acquire_by, soft_out, questions_per_clip, calibrate):
-    """the posterior argument of update_labels / run_round against the switches it depends on; raises ValueError"""
-    if posterior not in POSTERIOR:
-        raise ValueError("posterior: 'deterministic' or 'ensemble'")
-    if posterior != 'ensemble':
-        if rank_by == 'span_bald':
-            raise ValueError("rank_by='span_bald' is the ensemble's score: it needs posterior='ensemble'")
-        return
-    check_bank_planes(bank, mc_samples)
-    if acquire_by == 'label_gain':
-        raise ValueError("posterior='ensemble' with acquire_by='label_gain' is not offered: the label gain has no ensemble form")
-    if questions_per_clip != 1:
-        raise ValueError("posterior='ensemble' with questions_per_clip > 1 is not offered: sessions have no ensemble form")
-    if calibrate is not None:
-        raise ValueError("posterior='ensemble' with calibrate is not offered: the evidence grid has no ensemble form")
-    if observe_by != 'info_gain' and renew_by != 'posterior' and soft_out is None and rank_by != 'span_bald':
-        raise ValueError("posterior='ensemble' changes the span posterior: switch on one of its readers (observe_by='info_gain', "
-                         "renew_by='posterior', soft_out, rank_by='span_bald')")
 
 
 class LabelUpdater:
@@ -690,8 +648,8 @@ class LabelUpdater:
         self.uncert_frame = torch.zeros(N, ld, device=self.dev, dtype=torch.float64)
         self.uncert_video = torch.zeros(N, device=self.dev)
         self.observe = torch.zeros(N, device=self.dev, dtype=torch.int32)
-        self.temperature, self._inv_tau, self._scaled, self._last_eps = None, None, None, None
-        self._ens, self._ens_scaled, self._ens_tilt = None, None, None
+        self.temperature, self._inv_tau, self._last_eps = None, None, None
+        self._det, self._chain = (self._s0, self._e0), {}        # (the deterministic logits: the chain's source unless it holds another)
         self.set_active_points(aps)
 
     def set_active_points(self, aps):
@@ -707,16 +665,30 @@ class LabelUpdater:
         p = lib.ptr
         self.set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, p(self.ap_off).value,
                                    p(self.ap_idx).value, p(self.ap_pos).value)
-        self.tilt_eps = None                                     # (a tilt holds the answers it was made with)
-        self._scaled = None                                      # (and the scaled rows go with it: both are rebuilt on demand)
-        self._ens_tilt = None
+        self._drop('tilted')                                     # (a tilt holds the answers it was made with)
+
+    # What a launch of the span posterior reads is the last stage of one chain: 'source' - an ensemble's passes [K, N, ld]; without
+    # an entry the deterministic logits [N, ld] - -> 'scaled' by float32(1 / tau) -> 'tilted' by the answers under eps.  The two
+    # later stages are made on demand and kept in _chain beside what they were made from; _drop is the one place that forgets.
+    # One slot per stage: tilt() and _logits() always work on the deterministic logits, so beside an ensemble they and the
+    # ensemble's readers take the 'scaled' and 'tilted' slots from each other, and each remakes what it finds made from other rows.
+    CHAIN = ('source', 'scaled', 'tilted')
+
+    def _posterior_source(self):
+        return self._chain.get('source', self._det)
+
+    def _drop(self, stage):
+        """forget `stage` of the chain and every stage made from it"""
+        for name in self.CHAIN[self.CHAIN.index(stage):]:
+            self._chain.pop(name, None)
+        self.tilt_eps = None
 
     def set_temperature(self, tau):
-        """the temperature of the span posterior: None or 1.0 (the default) - _rows, tilt and session read the deterministic logits
-        themselves, the very same tensors, so every launch and stored bit is what it is without this call -, or tau > 0: they read
-        s0 * float32(1 / tau) and e0 * float32(1 / tau), one float32 product per logit (the row hual_al_evidence_grid evaluates at that
-        tau), computed once and dropped with the tilt.  score() and renew() restate the reference's heuristic and keep reading the
-        unscaled logits.  calibrate() fits tau."""
+        """the temperature of the span posterior: None or 1.0 (the default) - the posterior's launches, tilt and session read the
+        source's logits themselves, the very same memory, so every launch and stored bit is what it is without this call -, or
+        tau > 0: they read s0 * float32(1 / tau) and e0 * float32(1 / tau), one float32 product per logit (the row
+        hual_al_evidence_grid evaluates at that tau), computed once and kept until the temperature or the source changes.  score() and renew() restate the
+        reference's heuristic and keep reading the unscaled logits.  calibrate() fits tau."""
         if tau is not None:
             try:
                 tau = float('nan') if isinstance(tau, bool) else float(tau)
@@ -728,18 +700,8 @@ class LabelUpdater:
         if inv is not None and not 0.0 < float(inv) < float('inf'):
             raise ValueError('the temperature must be None or a finite number > 0')
         if inv != self._inv_tau:
-            self.tilt_eps, self._scaled = None, None
-            self._ens_scaled, self._ens_tilt = None, None
+            self._drop('scaled')
         self.temperature, self._inv_tau = (None if inv is None else tau), inv
-
-    def _logits(self):
-        """(s, e) the posterior's launches read: the deterministic logits, or under a temperature their float32 products with 1 / tau"""
-        if self._inv_tau is None:
-            return self._s0, self._e0
-        if self._scaled is None:
-            k = float(self._inv_tau)                             # (a python scalar: torch multiplies in float32, by float32(1 / tau))
-            self._scaled = ((self._s0 * k).contiguous(), (self._e0 * k).contiguous())
-        return self._scaled
 
     def set_ensemble(self, pass_s, pass_e):
         """the span posterior as a Bayesian model average: pass_s / pass_e f32 [K, N, ld] on the updater's device, 1 <= K <= 16, the
@@ -747,7 +709,10 @@ class LabelUpdater:
         the passes' posteriors, each weighted by its evidence of the answers (hual_al_ensemble_query / hual_al_ensemble_label) -
         under noise=eps behind one hual_al_noisy_tilt per plane -, set_temperature scales the planes as it scales the deterministic
         logits, and label_gain(), session(), calibrate() and evidence_grid() raise: they have no ensemble form.  None (both): off
-        again - every launch and bit as it was.  score() and renew() never read it."""
+        again - every launch and bit as it was.  score() and renew() never read it; tilt() keeps tilting the deterministic logits.
+        Either way the call forgets the scaled rows and the tilt the updater holds (tilt_eps is None after it), and while an
+        ensemble is set a tilt() between two of its noisy readers makes the second tilt the passes again: the chain has one slot
+        per stage."""
         if (pass_s is None) != (pass_e is None):
             raise ValueError('set_ensemble: pass_s and pass_e are both tensors or both None')
         if pass_s is not None:
@@ -758,44 +723,81 @@ class LabelUpdater:
             if not ok:
                 raise lib.HualError('set_ensemble: pass_s / pass_e must be contiguous float32 [K, N, ld] = [1..%d, %d, %d] on the updater\'s device'
                                     % (lib.AL_ENS_MAX_K, self.N, self.ld))
-        self._ens = None if pass_s is None else (pass_s, pass_e)
-        self._ens_scaled, self._ens_tilt = None, None
+        self._drop('source')
+        if pass_s is not None:
+            self._chain['source'] = (pass_s, pass_e)
 
     def _no_ensemble(self, what):
-        if self._ens is not None:
+        if self._posterior_source() is not self._det:
             raise lib.HualError('%s has no ensemble form: call set_ensemble(None, None) first' % what)
 
     def _free_set(self):
         """a hual_al_set over the same vlen / tlen WITHOUT answers: what the family's launches take beside tilted rows"""
-        if getattr(self, '_free', None) is None:
+        if getattr(self, '_free', None) is None:                 # (made once: vlen and tlen are the updater's for good)
             self._free = (torch.zeros(self.N + 1, dtype=torch.int32, device=self.dev), torch.zeros(1, dtype=torch.int32, device=self.dev),
                           torch.zeros(1, dtype=torch.int8, device=self.dev))
-        p = lib.ptr
-        self.free_set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, *[p(x).value for x in self._free])
+            p = lib.ptr
+            self.free_set = lib.hual_al_set(self.N, self.ld, p(self.vlen).value, p(self.tlen).value, *[p(x).value for x in self._free])
         return self.free_set
 
-    def _ens_rows(self, noise):
-        """(set, pass_s, pass_e, logw) an ensemble launch reads: the updater's set and the planes (under a temperature their float32
-        products with 1 / tau) and no prior weight; or under noise = eps the set without answers, every plane tilted by eps
-        (hual_al_noisy_tilt, one launch per plane) and the planes' log_evidence rows [K, N] as the weights' logarithms - pass k's
-        evidence of the noisy answers is exactly its weight"""
-        ps, pe = self._ens
-        if self._inv_tau is not None:
-            if self._ens_scaled is None:
-                k = float(self._inv_tau)
-                self._ens_scaled = ((ps * k).contiguous(), (pe * k).contiguous())
-            ps, pe = self._ens_scaled
-        if noise is None:
-            return self.set, ps, pe, None
-        eps = check_noise(noise)
-        if self._ens_tilt is None or self._ens_tilt[0] != eps:
-            K = ps.shape[0]
-            st, et, lev = torch.zeros_like(ps), torch.zeros_like(pe), torch.empty(K, self.N, device=self.dev)
-            for k in range(K):
-                lib.al_noisy_tilt(self.set, ps[k], pe[k], self.tlen_h, eps, out=(st[k], et[k], lev[k]))
-            self._ens_tilt = (eps, st, et, lev)
+    def _scaled(self, src):
+        """(s, e) of `src` as the launches read them: the very same tensors, or under a temperature their float32 products with 1 / tau"""
+        made = self._chain.get('scaled')
+        if made is None or made[0] is not src:
+            s, e = src
+            if self._inv_tau is not None:
+                k = float(self._inv_tau)                         # (a python scalar: torch multiplies in float32, by float32(1 / tau))
+                s, e = (s * k).contiguous(), (e * k).contiguous()
+            made = self._chain['scaled'] = (src, s, e)
+        return made[1:]
+
+    def _tilted(self, src, eps, fresh=False):
+        """(s_t, e_t, log_evidence) of the scaled `src` tilted by the set's answers under eps, shaped as `src` is ([N, ld] and [N], or
+        [K, N, ld] and [K, N]): hual_al_noisy_tilt, one launch per plane - launched only where the chain holds none from these rows at
+        this eps, or with fresh"""
+        s, e = self._scaled(src)
+        made = self._chain.get('tilted')
+        if fresh or made is None or made[0] is not s or made[1] != eps:
+            if s.dim() == 2:
+                st, et, lev = lib.al_noisy_tilt(self.set, s, e, self.tlen_h, eps)
+            else:                                                # (the same launch per plane, into one tensor per output)
+                st, et, lev = torch.zeros_like(s), torch.zeros_like(e), torch.empty(s.shape[:-1], device=self.dev)
+                for k in range(s.shape[0]):
+                    lib.al_noisy_tilt(self.set, s[k], e[k], self.tlen_h, eps, out=(st[k], et[k], lev[k]))
+            made = self._chain['tilted'] = (s, eps, st, et, lev)
             self._last_eps = eps
-        return (self._free_set(),) + self._ens_tilt[1:]
+            if src is self._det:
+                self.s_t, self.e_t, self.log_evidence, self.tilt_eps = st, et, lev, eps
+        return made[2:]
+
+    def _logits(self):
+        """(s, e) the deterministic posterior's launches read: the deterministic logits, or under a temperature their float32 products
+        with 1 / tau"""
+        return self._scaled(self._det)
+
+    def _reads(self, noise):
+        """(set, s, e, logw) a launch of the span posterior takes: the updater's set, the scaled source and no prior weight; or under
+        noise = eps the set without answers, the source tilted by eps (tilted here unless it already is) and its log_evidence - for
+        an ensemble [K, N], the logarithms of the passes' weights: pass k's evidence of the noisy answers is exactly its weight"""
+        if noise is None:
+            return (self.set,) + self._scaled(self._posterior_source()) + (None,)
+        return (self._free_set(),) + self._tilted(self._posterior_source(), check_noise(noise))
+
+    def _launch(self, what, noise, **kw):
+        """one launch of the span posterior on what _reads(noise) gives - `what` = 'query', 'marginals' or 'label': lib's wrapper on the
+        deterministic rows, or its ensemble twin on the passes' planes and weights -> (the plain wrapper's tuple, whichever ran - the
+        ensemble has no agree -; what only the ensemble query leaves: (weight, log_evidence, expected_entropy, span_bald, status), else
+        None)"""
+        aset, s, e, logw = self._reads(noise)
+        if self._posterior_source() is self._det:
+            plain = lib.al_query if what == 'query' else lib.al_span_marginals if what == 'marginals' else lib.al_mbr_label
+            return plain(aset, s, e, self.tlen_h, **kw), None
+        if what == 'label':
+            return lib.al_ensemble_label(aset, s, e, self.tlen_h, logw=logw, **kw), None
+        o = lib.al_ensemble_query(aset, s, e, self.tlen_h, logw=logw, frames=kw.get('frames', False), marginals=what == 'marginals')
+        if what == 'marginals':
+            return (o[6], o[7], o[11]), None
+        return (o[2], o[3], o[4], o[5], o[8], None), (o[0], o[1], o[9], o[10], o[11])
 
     def evidence_grid(self, taus, eps, sel=None):
         """ln P(the set's answers | softmax(s0 / tau), softmax(e0 / tau), eps) per sample on the grid taus x eps and its sum over the
@@ -884,19 +886,8 @@ class LabelUpdater:
         (hual_al_noisy_tilt, one launch over the whole set).  Leaves s_t, e_t (f32 [N, ld], the tilted rows), log_evidence (f32 [N]:
         ln P(the answers | the model, eps), NaN on a poisoned row), free_set (a hual_al_set over the same vlen / tlen WITHOUT answers:
         what the family's launches take beside the tilted rows) and tilt_eps; set_active_points invalidates them."""
-        eps = check_noise(eps)
-        self.s_t, self.e_t, self.log_evidence = lib.al_noisy_tilt(self.set, *self._logits(), self.tlen_h, eps)
+        self._tilted(self._det, check_noise(eps), fresh=True)
         self._free_set()
-        self.tilt_eps = self._last_eps = eps
-
-    def _rows(self, noise):
-        """(set, s, e) a launch of the family reads: the updater's own, or under noise = eps the set without answers and the rows
-        tilted by eps (tilted here unless they already are)"""
-        if noise is None:
-            return (self.set,) + tuple(self._logits())
-        if self.tilt_eps != check_noise(noise):
-            self.tilt(noise)
-        return self.free_set, self.s_t, self.e_t
 
     def score(self, coff_uncert):
         lib.al_score(self.set, self._s0, self._e0, coff_uncert, (self.sprob, self.eprob, self.uncert_frame, self.uncert_video, self.observe),
@@ -917,19 +908,11 @@ class LabelUpdater:
         ens_log_evidence), expected_entropy and span_bald (f32 [N], bits).  Without one it returns None."""
         if noise is not None and not frames:
             raise ValueError('query(noise=) computes the gain of a noisy answer from incl: it needs frames=True')
-        ens = None
-        if self._ens is not None:
-            aset, ps, pe, logw = self._ens_rows(noise)
-            (self.weight, self.ens_log_evidence, self.incl, self.gain, self.query_point, self.query_gain, _, _, self.post_entropy,
-             self.expected_entropy, self.span_bald, self.ens_status) = lib.al_ensemble_query(aset, ps, pe, self.tlen_h, logw=logw,
-                                                                                             frames=frames, marginals=False)
-            self.agree = None
+        (self.incl, self.gain, self.query_point, self.query_gain, self.post_entropy, self.agree), ens = self._launch('query', noise, frames=frames)
+        if ens is not None:
+            self.weight, self.ens_log_evidence, self.expected_entropy, self.span_bald, self.ens_status = ens
             ens = dict(weight=self.weight, log_evidence=self.ens_log_evidence, expected_entropy=self.expected_entropy,
                        span_bald=self.span_bald)
-        else:
-            aset, s, e = self._rows(noise)
-            (self.incl, self.gain, self.query_point, self.query_gain, self.post_entropy,
-             self.agree) = lib.al_query(aset, s, e, self.tlen_h, frames=frames)
         if noise is not None:
             eps = check_noise(noise)
 
@@ -1004,10 +987,10 @@ class LabelUpdater:
         (i32 [N]), ask_gain and label_value (f32 [N]) as device tensors.
         noise=eps: the gain from a NOISY answer (hual_al_label_gain_noisy, one launch) on the rows tilted by eps (tilt())."""
         self._no_ensemble('label_gain()')
+        aset, s, e, _ = self._reads(noise)
         if noise is None:
-            out = lib.al_label_gain(*self._rows(None), self.tlen_h, cand=cand, frames=frames)
+            out = lib.al_label_gain(aset, s, e, self.tlen_h, cand=cand, frames=frames)
         else:
-            aset, s, e = self._rows(noise)
             out = lib.al_label_gain_noisy(aset, s, e, self.tlen_h, check_noise(noise), cand=cand, frames=frames)
         self.gain, self.ask_point, self.ask_gain, self.label_value = out
 
@@ -1018,13 +1001,7 @@ class LabelUpdater:
         noise=eps: the marginals of the posterior under an annotator who errs with probability eps - the same launch on the rows
         tilted by eps (tilt()) and the set without answers.
         With an ensemble set: the marginals of the model average, sum_k w_k of the passes' (hual_al_ensemble_query, one launch)."""
-        if self._ens is not None:
-            aset, ps, pe, logw = self._ens_rows(noise)
-            o = lib.al_ensemble_query(aset, ps, pe, self.tlen_h, logw=logw, frames=False, marginals=True)
-            self.y_start, self.y_end, self.marg_status = o[6], o[7], o[11]
-            return
-        aset, s, e = self._rows(noise)
-        self.y_start, self.y_end, self.marg_status = lib.al_span_marginals(aset, s, e, self.tlen_h)
+        (self.y_start, self.y_end, self.marg_status), _ = self._launch('marginals', noise)
 
     def mbr_label(self, sel, old_idx, noise=None):
         """the minimum-Bayes-risk pseudo-label of the samples `sel` (sample ids, numpy) under the span posterior given the set's
@@ -1036,12 +1013,7 @@ class LabelUpdater:
         With an ensemble set: the label of maximal expected tIoU under the model average (hual_al_ensemble_label, one launch)."""
         sel_d = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
         old_d = torch.from_numpy(np.ascontiguousarray(old_idx, dtype=np.int32)).to(self.dev)
-        if self._ens is not None:
-            aset, ps, pe, logw = self._ens_rows(noise)
-            new_d, conf, old_conf = lib.al_ensemble_label(aset, ps, pe, self.tlen_h, logw=logw, sel=sel_d, old_idx=old_d)
-            return new_d.cpu().numpy(), conf.cpu().numpy(), old_conf.cpu().numpy()
-        aset, s, e = self._rows(noise)
-        new_d, conf, old_conf = lib.al_mbr_label(aset, s, e, self.tlen_h, sel=sel_d, old_idx=old_d)
+        (new_d, conf, old_conf), _ = self._launch('label', noise, sel=sel_d, old_idx=old_d)
         return new_d.cpu().numpy(), conf.cpu().numpy(), old_conf.cpu().numpy()
 
     def renew(self, sel, old_idx, coff):
@@ -1055,35 +1027,102 @@ class LabelUpdater:
         return new_d.cpu().numpy()
 
 
-def check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by):
-    """the two session arguments of update_labels / run_round against the switches they depend on -> Q; raises ValueError"""
-    try:
-        Q = int(questions_per_clip)
-        ok = not isinstance(questions_per_clip, bool) and Q == questions_per_clip and 1 <= Q <= lib.AL_SESSION_MAX_Q
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError('questions_per_clip: an integer in [1, %d]' % lib.AL_SESSION_MAX_Q)
-    if Q > 1 and acquire_by == 'label_gain':
-        raise ValueError("questions_per_clip > 1 with acquire_by='label_gain' is not offered: sessions ask by information gain")
-    if Q > 1 and observe_by != 'info_gain':
-        raise ValueError("questions_per_clip > 1 needs observe_by='info_gain': a session asks by expected information gain")
-    if stop_entropy is not None:
-        try:
-            ok = float(stop_entropy) >= 0.0 and Q > 1
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError('stop_entropy: None, or bits >= 0 with questions_per_clip > 1')
-    return Q
-
-
+POSTERIOR = ('deterministic', 'ensemble')
 RANK_BY = ('uncert_video', 'span_risk')
-RANK_BY_ENSEMBLE = ('span_bald',)      # with posterior='ensemble' only (check_posterior)
+RANK_BY_ENSEMBLE = ('span_bald',)      # with posterior='ensemble' only (check_round)
 OBSERVE_BY = ('uncert_frame', 'info_gain')
 RENEW_BY = ('heuristic', 'posterior')
 ACQUIRE_BY = (None, 'label_gain')
 CALIBRATE = (None, 'evidence')
+
+# check_round's result: the switches of a round as update_labels works from them - the enumerations as given; Q, the questions per
+# clip, an int; stop_entropy, noise and temperature floats or None; flip None or (rate, Generator); reads_posterior: one of the span
+# posterior's readers is on
+RoundPolicy = collections.namedtuple('RoundPolicy', 'posterior rank_by observe_by renew_by acquire_by Q stop_entropy noise temperature '
+                                                    'calibrate flip reads_posterior')
+
+
+def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='uncert_video', observe_by='uncert_frame',
+                renew_by='heuristic', acquire_by=None, soft_out=None, answer_noise=None, annotator_flip=None, questions_per_clip=1,
+                stop_entropy=None, temperature=None, calibrate=None):
+    """every rule between the switches of update_labels / run_round (their docstrings say what each switch does) -> RoundPolicy;
+    raises ValueError, and touches nothing"""
+    readers = {"observe_by='info_gain'": observe_by == 'info_gain', "acquire_by='label_gain'": acquire_by == 'label_gain',
+               "renew_by='posterior'": renew_by == 'posterior', 'soft_out': soft_out is not None, "rank_by='span_bald'": rank_by == 'span_bald'}
+
+    def needs_reader(who, but):
+        """`who` changes the span posterior, which is idle work unless something reads it: all of `readers` count but the one that
+        `who` is not offered with"""
+        if not any(on and r != but for r, on in readers.items()):
+            raise ValueError('%s changes the span posterior: switch on one of its readers (%s)' % (who, ', '.join(r for r in readers if r != but)))
+
+    def number(x, ok):
+        """ok(x), False where x is no number at all"""
+        try:
+            return bool(ok(x))
+        except (TypeError, ValueError, ZeroDivisionError):
+            return False
+
+    # the posterior: the ensemble needs its passes, has no label gain, no sessions and no evidence grid, and is the only one with span_bald
+    if posterior not in POSTERIOR:
+        raise ValueError("posterior: 'deterministic' or 'ensemble'")
+    if posterior != 'ensemble':
+        if rank_by == 'span_bald':
+            raise ValueError("rank_by='span_bald' is the ensemble's score: it needs posterior='ensemble'")
+    else:
+        check_bank_planes(bank, mc_samples)
+        if acquire_by == 'label_gain':
+            raise ValueError("posterior='ensemble' with acquire_by='label_gain' is not offered: the label gain has no ensemble form")
+        if questions_per_clip != 1:
+            raise ValueError("posterior='ensemble' with questions_per_clip > 1 is not offered: sessions have no ensemble form")
+        if calibrate is not None:
+            raise ValueError("posterior='ensemble' with calibrate is not offered: the evidence grid has no ensemble form")
+        needs_reader("posterior='ensemble'", but="acquire_by='label_gain'")
+    # sessions: Q questions per clip, asked by information gain, stopped at stop_entropy bits
+    if not number(questions_per_clip, lambda q: not isinstance(q, bool) and int(q) == q and 1 <= int(q) <= lib.AL_SESSION_MAX_Q):
+        raise ValueError('questions_per_clip: an integer in [1, %d]' % lib.AL_SESSION_MAX_Q)
+    Q = int(questions_per_clip)
+    if Q > 1 and acquire_by == 'label_gain':
+        raise ValueError("questions_per_clip > 1 with acquire_by='label_gain' is not offered: sessions ask by information gain")
+    if Q > 1 and observe_by != 'info_gain':
+        raise ValueError("questions_per_clip > 1 needs observe_by='info_gain': a session asks by expected information gain")
+    if stop_entropy is not None and not (Q > 1 and number(stop_entropy, lambda h: float(h) >= 0.0)):
+        raise ValueError('stop_entropy: None, or bits >= 0 with questions_per_clip > 1')
+    if soft_out is not None and not isinstance(soft_out, dict):
+        raise ValueError('soft_out: None or a dict to receive y1, y2, live and answered')
+    # the noisy annotator, the temperature and their fit change what the posterior's readers see
+    noise = None
+    if answer_noise is not None:
+        try:
+            noise = check_noise(answer_noise)
+        except ValueError:
+            raise ValueError('answer_noise: None or an error probability in (0, 0.5]') from None
+        needs_reader('answer_noise', but="rank_by='span_bald'")
+    if calibrate not in CALIBRATE:
+        raise ValueError("calibrate: None or 'evidence'")
+    if temperature is not None and not number(temperature, lambda t: not isinstance(t, bool) and 0.0 < float(np.float32(1.0 / float(t))) < float('inf')):
+        raise ValueError('temperature: None or a finite temperature > 0')
+    if temperature is not None or calibrate is not None:
+        needs_reader('calibrate' if calibrate is not None else 'temperature', but="rank_by='span_bald'")
+    if annotator_flip is not None:
+        if not (isinstance(annotator_flip, (tuple, list)) and len(annotator_flip) == 2 and isinstance(annotator_flip[1], np.random.Generator)
+                and number(annotator_flip[0], lambda r: 0.0 <= float(r) <= 1.0)):
+            raise ValueError('annotator_flip: None or (rate in [0, 1], numpy.random.Generator)')
+        annotator_flip = (float(annotator_flip[0]), annotator_flip[1])
+    # ranking and the question: acquire_by decides both
+    if rank_by not in RANK_BY and not (posterior == 'ensemble' and rank_by in RANK_BY_ENSEMBLE):
+        raise ValueError("rank_by: 'uncert_video' or 'span_risk' ('span_bald' with posterior='ensemble')")
+    if observe_by not in OBSERVE_BY:
+        raise ValueError("observe_by: 'uncert_frame' or 'info_gain'")
+    if renew_by not in RENEW_BY:
+        raise ValueError("renew_by: 'heuristic' or 'posterior'")
+    if acquire_by not in ACQUIRE_BY:
+        raise ValueError("acquire_by: None or 'label_gain'")
+    if acquire_by is not None and (rank_by != RANK_BY[0] or observe_by != OBSERVE_BY[0]):
+        raise ValueError("acquire_by='%s' chooses the samples and the frames itself: leave rank_by and observe_by at their defaults"
+                         % acquire_by)
+    return RoundPolicy(posterior, rank_by, observe_by, renew_by, acquire_by, Q, None if stop_entropy is None else float(stop_entropy), noise,
+                       None if temperature is None else float(temperature), calibrate, annotator_flip, any(readers.values()))
 
 
 def span_risk(last_prop):
@@ -1091,6 +1130,141 @@ def span_risk(last_prop):
     if not all('prop_conf' in p for p in last_prop):
         raise ValueError("rank_by='span_risk' needs records that hold 'prop_conf': run infer_trainset(span_conf=True)")
     return 1.0 - np.array([float(p['prop_conf']) for p in last_prop], dtype=np.float64)
+
+
+# The phases of update_labels, in its order.  Each returns what the next ones need and, last, the entries it has for the debug dict:
+# device tensors as they are, fetched only if the dict is asked for.
+def _round_score(pol, last_prop, aps, coff, device, bank, mc_samples, mc_stat):
+    """the round's LabelUpdater, scored"""
+    if bank is not None:
+        up = LabelUpdater.from_bank(bank, [p['v_len'] for p in last_prop], aps, K=mc_samples, stat=mc_stat, ensemble=pol.posterior == 'ensemble')
+    else:
+        up = LabelUpdater(last_prop, aps, device=device)
+    up.score(coff[6])
+    return up, dict(uncert_frame=up.uncert_frame, sprob=up.sprob, eprob=up.eprob, updater=up)
+
+
+def _round_calibrate(up, pol):
+    """the temperature and error rate the round's posterior readers use: the policy's, or their fit to the answers of the earlier
+    rounds where calibrate asks for it and the fit exists -> noise"""
+    tau, noise, dbg = pol.temperature, pol.noise, {}
+    if pol.calibrate == 'evidence':
+        fit = dbg['calibration'] = up.calibrate(at_eps=noise)
+        if fit is not None:
+            tau, noise = fit['tau'], fit['eps']
+    up.set_temperature(tau)
+    return noise, dbg
+
+
+def _round_choose(up, pol, noise, risk, frames):
+    """whom to ask and where, on the answers of the earlier rounds (before set_active_points) -> (order, the ranking of the samples;
+    ask, every sample's frame)"""
+    uv, observe = up.uncert_video.cpu().numpy(), up.observe.cpu().numpy()
+    ask, dbg = observe, dict(uncert_video=uv, observe=observe)
+    order = np.argsort(uv if risk is None else risk, kind='stable')      # sorted(key=uncert_video), ties in sample order
+    if risk is not None:
+        dbg['span_risk'] = risk
+    if pol.observe_by == 'info_gain' or pol.rank_by == 'span_bald':
+        ens = up.query(frames=frames or noise is not None, noise=noise)
+        if ens is not None:
+            dbg.update(weight=ens['weight'], ens_log_evidence=ens['log_evidence'], expected_entropy=ens['expected_entropy'],
+                       span_bald=ens['span_bald'])
+    if pol.observe_by == 'info_gain':
+        ask = np.where(up.query_gain.cpu().numpy() > 0, up.query_point.cpu().numpy(), observe)
+        dbg.update(query_point=up.query_point, query_gain=up.query_gain, post_entropy=up.post_entropy, observe_used=ask)
+        if noise is None and up.agree is not None:               # (neither the noisy posterior nor the ensemble has an agree)
+            dbg['agree'] = up.agree
+    if pol.rank_by == 'span_bald':
+        order = np.argsort(-up.span_bald.cpu().numpy(), kind='stable')      # largest first, ties in sample order; rows at -1 last
+    if pol.acquire_by == 'label_gain':
+        up.label_gain(frames=frames, noise=noise)
+        ask_gain = up.ask_gain.cpu().numpy()
+        ask = np.where(ask_gain > 0, up.ask_point.cpu().numpy(), observe)
+        order = np.argsort(-ask_gain, kind='stable')             # largest gain first, ties in sample order; rows at 0 and -1 last
+        dbg.update(ask_point=up.ask_point, ask_gain=ask_gain, label_value=up.label_value, observe_used=ask)
+    dbg['order'] = order
+    return order, ask, dbg
+
+
+def _round_ask(up, pol, noise, sel, ask, gt_idx, data_old, aps):
+    """append_AP (utils_hual.py:133-139): the annotator answers "is the observed frame inside the ground-truth span?" - up to Q times
+    for a selected sample whose first question has a positive gain (one session launch for all of them), once at the chosen frame for
+    every other; the answers go into data_old and aps, and the updater takes the new lists"""
+    N, Q = len(aps), pol.Q
+    flips = np.zeros(N, dtype=np.uint32)                         # bit k: the sample's k-th answer is wrong
+    if pol.flip is not None:
+        rate, rng = pol.flip
+        for i in sel:                                            # Q draws per selected sample, in selection order, used or not
+            for k in range(Q):
+                if rng.random() < rate:
+                    flips[i] |= np.uint32(1 << k)
+    in_session = np.zeros(0, dtype=np.int64)
+    if Q > 1:                                                    # (sessions need observe_by='info_gain': query() ran and left query_gain)
+        has_gain = up.query_gain.cpu().numpy() > 0
+        in_session = sel[has_gain[sel]]
+    if len(in_session):
+        asked, answers, n_asked = up.session(gt_idx, Q, stop_entropy=pol.stop_entropy, noise=noise, flips=flips, sel=in_session)
+    session, ask, gt, wrong = set(in_session.tolist()), ask.tolist(), gt_idx.tolist(), flips.tolist()      # (plain lists: the loop below is per sample)
+    given, flipped = {}, np.zeros(N, dtype=bool)                 # given: sample -> this round's (frame, is_pos), in the order asked
+    for i in sel.tolist():
+        if i in session:
+            given[i] = [(int(asked[i, k]), bool(answers[i, k])) for k in range(n_asked[i])]
+        else:                                                    # no session: the reference's or the chosen frame, one question
+            given[i] = [(ask[i], (gt[i][0] <= ask[i] <= gt[i][1]) != bool(wrong[i] & 1))]
+        if wrong[i] & ((1 << len(given[i])) - 1):
+            flipped[i] = True
+        for p, is_pos in given[i]:
+            data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
+            aps[i].append((p, is_pos))
+    up.set_active_points(aps)
+    dbg = {}
+    if Q > 1:                                                    # the transcripts: -1 = unused / not read / no session
+        dbg = dict(asked=np.full((N, Q), -1, dtype=np.int64), answers=np.full((N, Q), -1, dtype=np.int64), n_asked=np.zeros(N, dtype=np.int64),
+                   entropy_path=np.full((N, Q + 1), -1.0, dtype=np.float32), stop_reason=np.full(N, -1, dtype=np.int64))
+        for i, qa in given.items():
+            dbg['asked'][i, :len(qa)], dbg['answers'][i, :len(qa)], dbg['n_asked'][i] = [p for p, _ in qa], [a for _, a in qa], len(qa)
+        if len(in_session):
+            dbg['entropy_path'][in_session] = up.entropy_path.cpu().numpy()[in_session]
+            dbg['stop_reason'][in_session] = up.stop_reason.cpu().numpy()[in_session]
+    if pol.flip is not None:
+        dbg['flipped'] = flipped
+    if noise is not None and pol.posterior != 'ensemble':        # (the ensemble's readers tilt the passes themselves, on demand)
+        up.tilt(noise)                                           # (this round's answers included: what the launches below read)
+        dbg['log_evidence'] = up.log_evidence
+    return dbg
+
+
+def _round_soft_labels(up, noise, aps, soft_out):
+    """the whole set's soft labels under the posterior given every answer so far, into the caller's dict"""
+    up.span_marginals(noise=noise)
+    soft_out.update(y1=up.y_start, y2=up.y_end, live=up.marg_status.cpu().numpy() == 1,
+                    answered=np.array([any(0 <= f < int(up.vlen_h[i]) for f, _ in a) for i, a in enumerate(aps)], dtype=bool))
+
+
+def _round_renew(up, pol, noise, sel, old_idx, coff, data_old):
+    """the selected samples' new spans - the reference's renew_label, or the minimum-Bayes-risk label with that renew for the rows
+    that give none - written into data_old as times"""
+    dbg = {}
+    if pol.renew_by == 'posterior':
+        new_idx, label_conf, old_conf = up.mbr_label(sel, old_idx, noise=noise)
+        by_posterior = np.zeros(len(old_idx), dtype=bool)
+        by_posterior[sel] = new_idx[sel, 0] >= 0
+        rest = sel[~by_posterior[sel]]                           # no label: the reference's renew for just those
+        if len(rest):
+            new_idx[rest] = up.renew(rest, old_idx, coff)[rest]
+        dbg.update(label_conf=label_conf, old_conf=old_conf, renewed_by_posterior=by_posterior)
+    else:
+        new_idx = up.renew(sel, old_idx, coff)
+    for i in sel:
+        dur, vl = data_old[i][1], int(up.vlen_h[i])
+        data_old[i][2] = [round(int(t) / (vl - 1) * dur, 2) for t in new_idx[i]]          # index_to_time, update_label.py:50-57
+    dbg['new_idx'] = new_idx
+    return dbg
+
+
+def _round_debug(*parts):
+    """the debug dict of update_labels: the phases' entries, device tensors fetched"""
+    return {k: v.cpu().numpy() if torch.is_tensor(v) else v for part in parts for k, v in part.items()}
 
 
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
@@ -1170,40 +1344,10 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     dict gains 'weight' (float32 [N, K]), 'ens_log_evidence', 'expected_entropy' and 'span_bald' (float32
     [N]) as the query left them: on the answers of the earlier rounds.
     """
-    check_posterior(posterior, bank, mc_samples, rank_by, observe_by, renew_by, acquire_by, soft_out, questions_per_clip, calibrate)
-    Q = check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by)
-    if soft_out is not None and not isinstance(soft_out, dict):
-        raise ValueError('soft_out: None or a dict to receive y1, y2, live and answered')
-    noise = None
-    if answer_noise is not None:
-        try:
-            noise = check_noise(answer_noise)
-        except ValueError:
-            raise ValueError('answer_noise: None or an error probability in (0, 0.5]') from None
-        if observe_by != 'info_gain' and acquire_by != 'label_gain' and renew_by != 'posterior' and soft_out is None:
-            raise ValueError("answer_noise changes the span posterior: switch on one of its readers (observe_by='info_gain', "
-                             "acquire_by='label_gain', renew_by='posterior', soft_out)")
-    temperature = check_calibration(temperature, calibrate, observe_by, acquire_by, renew_by, soft_out)
-    if annotator_flip is not None:
-        ok = isinstance(annotator_flip, (tuple, list)) and len(annotator_flip) == 2 and isinstance(annotator_flip[1], np.random.Generator)
-        try:
-            ok = ok and 0.0 <= float(annotator_flip[0]) <= 1.0
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError('annotator_flip: None or (rate in [0, 1], numpy.random.Generator)')
-    if rank_by not in RANK_BY and not (posterior == 'ensemble' and rank_by in RANK_BY_ENSEMBLE):
-        raise ValueError("rank_by: 'uncert_video' or 'span_risk' ('span_bald' with posterior='ensemble')")
-    if observe_by not in OBSERVE_BY:
-        raise ValueError("observe_by: 'uncert_frame' or 'info_gain'")
-    if renew_by not in RENEW_BY:
-        raise ValueError("renew_by: 'heuristic' or 'posterior'")
-    if acquire_by not in ACQUIRE_BY:
-        raise ValueError("acquire_by: None or 'label_gain'")
-    if acquire_by is not None and (rank_by != RANK_BY[0] or observe_by != OBSERVE_BY[0]):
-        raise ValueError("acquire_by='%s' chooses the samples and the frames itself: leave rank_by and observe_by at their defaults"
-                         % acquire_by)
-    risk = span_risk(last_prop) if rank_by == 'span_risk' else None      # (raises before anything is touched)
+    pol = check_round(posterior=posterior, bank=bank, mc_samples=mc_samples, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by,
+                      acquire_by=acquire_by, soft_out=soft_out, answer_noise=answer_noise, annotator_flip=annotator_flip,
+                      questions_per_clip=questions_per_clip, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate)
+    risk = span_risk(last_prop) if pol.rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
             r.append({'pos_idx': [], 'neg_idx': []})
@@ -1213,120 +1357,18 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     # active points in one list per sample; the reference keeps two lists and only ever asks for min / max / membership
     # of each, so the relative order between the two kinds does not matter
     aps = [[(f, True) for f in r[4]['pos_idx']] + [(f, False) for f in r[4]['neg_idx']] for r in data_old]
-    if bank is not None:
-        up = LabelUpdater.from_bank(bank, [p['v_len'] for p in last_prop], aps, K=mc_samples, stat=mc_stat,
-                                    **(dict(ensemble=True) if posterior == 'ensemble' else {}))
-    else:
-        up = LabelUpdater(last_prop, aps, device=device)
-    up.score(coff[6])
-    fit = None
-    if calibrate == 'evidence':                                  # on the answers of the earlier rounds
-        fit = up.calibrate(at_eps=noise)
-        if fit is not None:
-            temperature, noise = fit['tau'], fit['eps']
-    up.set_temperature(temperature)
-    uv = up.uncert_video.cpu().numpy()
-    observe = up.observe.cpu().numpy()
-    ask = observe
-    if observe_by == 'info_gain' or rank_by == 'span_bald':
-        up.query(frames=return_debug or noise is not None, noise=noise)      # (before set_active_points: on the answers of the earlier rounds)
-    if observe_by == 'info_gain':
-        ask = np.where(up.query_gain.cpu().numpy() > 0, up.query_point.cpu().numpy(), observe)
-    order = np.argsort(uv if risk is None else risk, kind='stable')      # sorted(key=uncert_video), ties in sample order
-    if rank_by == 'span_bald':
-        order = np.argsort(-up.span_bald.cpu().numpy(), kind='stable')      # largest first, ties in sample order; rows at -1 last
-    if acquire_by == 'label_gain':
-        up.label_gain(frames=return_debug, noise=noise)          # (before set_active_points: on the answers of the earlier rounds)
-        ask_gain = up.ask_gain.cpu().numpy()
-        ask = np.where(ask_gain > 0, up.ask_point.cpu().numpy(), observe)
-        order = np.argsort(-ask_gain, kind='stable')             # largest gain first, ties in sample order; rows at 0 and -1 last
+    up, scored = _round_score(pol, last_prop, aps, coff, device, bank, mc_samples, mc_stat)
+    noise, fitted = _round_calibrate(up, pol)
+    order, ask, chosen = _round_choose(up, pol, noise, risk, return_debug)
     sel = order[:math.ceil(N / 2)]
-    vlen = up.vlen_h
-    gt_idx = np.array([[_round_half_even_index(t, data_gt[i][1], int(vlen[i])) for t in data_gt[i][2]] for i in range(N)])
-    old_idx = np.array([[_round_half_even_index(t, data_old[i][1], int(vlen[i])) for t in data_old[i][2]] for i in range(N)])
-    # append_AP (utils_hual.py:133-139): the annotator answers "is the observed frame inside the ground-truth span?"
-    flipped = np.zeros(N, dtype=bool)
-    if Q == 1:
-        for i in sel:
-            p = int(ask[i])
-            is_pos = gt_idx[i, 0] <= p <= gt_idx[i, 1]
-            if annotator_flip is not None and annotator_flip[1].random() < float(annotator_flip[0]):      # the simulated annotator errs
-                is_pos, flipped[i] = not is_pos, True
-            data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
-            aps[i].append((p, bool(is_pos)))
-    else:
-        flips = np.zeros(N, dtype=np.uint32)                     # bit k: the sample's k-th answer is wrong
-        if annotator_flip is not None:
-            for i in sel:                                        # Q draws per selected sample, in selection order, used or not
-                for k in range(Q):
-                    if annotator_flip[1].random() < float(annotator_flip[0]):
-                        flips[i] |= np.uint32(1 << k)
-        has_gain = up.query_gain.cpu().numpy() > 0
-        in_session = np.array([i for i in sel if has_gain[i]], dtype=np.int64)
-        sess = dict(asked=np.full((N, Q), -1, dtype=np.int64), answers=np.full((N, Q), -1, dtype=np.int64), n_asked=np.zeros(N, dtype=np.int64),
-                    entropy_path=np.full((N, Q + 1), -1.0, dtype=np.float32), stop_reason=np.full(N, -1, dtype=np.int64))
-        if len(in_session):
-            asked, answers, n_asked = up.session(gt_idx, Q, stop_entropy=stop_entropy, noise=noise, flips=flips, sel=in_session)
-            sess['asked'][in_session], sess['answers'][in_session] = asked[in_session], answers[in_session]
-            sess['n_asked'][in_session] = n_asked[in_session]
-            sess['entropy_path'][in_session] = up.entropy_path.cpu().numpy()[in_session]
-            sess['stop_reason'][in_session] = up.stop_reason.cpu().numpy()[in_session]
-        for i in sel:
-            if not has_gain[i]:                                  # no positive gain: the reference's frame, one question, as today
-                p = int(ask[i])
-                sess['asked'][i, 0], sess['n_asked'][i] = p, 1
-                sess['answers'][i, 0] = int((gt_idx[i, 0] <= p <= gt_idx[i, 1]) != bool(flips[i] & 1))
-            for k in range(int(sess['n_asked'][i])):
-                p, is_pos = int(sess['asked'][i, k]), bool(sess['answers'][i, k])
-                flipped[i] |= bool((flips[i] >> k) & 1)
-                data_old[i][4]['pos_idx' if is_pos else 'neg_idx'].append(p)
-                aps[i].append((p, is_pos))
-    up.set_active_points(aps)
-    if noise is not None and posterior != 'ensemble':            # (the ensemble's readers tilt the passes themselves, on demand)
-        up.tilt(noise)                                           # (this round's answers included: what the launches below read)
+    idx = dict(gt_idx=np.array([[_round_half_even_index(t, r[1], int(v)) for t in r[2]] for r, v in zip(data_gt, up.vlen_h)]),
+               old_idx=np.array([[_round_half_even_index(t, r[1], int(v)) for t in r[2]] for r, v in zip(data_old, up.vlen_h)]))
+    asked = _round_ask(up, pol, noise, sel, ask, idx['gt_idx'], data_old, aps)
     if soft_out is not None:
-        up.span_marginals(noise=noise)
-        soft_out.update(y1=up.y_start, y2=up.y_end, live=up.marg_status.cpu().numpy() == 1,
-                        answered=np.array([any(0 <= f < int(vlen[i]) for f, _ in aps[i]) for i in range(N)], dtype=bool))
-    if renew_by == 'posterior':
-        new_idx, label_conf, old_conf = up.mbr_label(sel, old_idx, noise=noise)
-        by_posterior = np.zeros(N, dtype=bool)
-        by_posterior[sel] = new_idx[sel, 0] >= 0
-        rest = sel[~by_posterior[sel]]                           # no label: the reference's renew for just those
-        if len(rest):
-            new_idx[rest] = up.renew(rest, old_idx, coff)[rest]
-    else:
-        new_idx = up.renew(sel, old_idx, coff)
-    for i in sel:
-        dur, vl = data_old[i][1], int(vlen[i])
-        data_old[i][2] = [round(int(t) / (vl - 1) * dur, 2) for t in new_idx[i]]          # index_to_time, update_label.py:50-57
+        _round_soft_labels(up, noise, aps, soft_out)
+    renewed = _round_renew(up, pol, noise, sel, idx['old_idx'], coff, data_old)
     if return_debug:
-        dbg = dict(order=order, uncert_video=uv, observe=observe, uncert_frame=up.uncert_frame.cpu().numpy(),
-                   sprob=up.sprob.cpu().numpy(), eprob=up.eprob.cpu().numpy(), new_idx=new_idx, gt_idx=gt_idx,
-                   old_idx=old_idx, updater=up)
-        if risk is not None:
-            dbg['span_risk'] = risk
-        if observe_by == 'info_gain':
-            dbg.update(query_point=up.query_point.cpu().numpy(), query_gain=up.query_gain.cpu().numpy(),
-                       post_entropy=up.post_entropy.cpu().numpy(), observe_used=ask)
-            if noise is None and up.agree is not None:               # (the ensemble has no agree: its ens_log_evidence is below)
-                dbg['agree'] = up.agree.cpu().numpy()
-        if acquire_by == 'label_gain':
-            dbg.update(ask_point=up.ask_point.cpu().numpy(), ask_gain=ask_gain, label_value=up.label_value.cpu().numpy(), observe_used=ask)
-        if renew_by == 'posterior':
-            dbg.update(label_conf=label_conf, old_conf=old_conf, renewed_by_posterior=by_posterior)
-        if noise is not None and posterior != 'ensemble':        # (the ensemble's own is 'ens_log_evidence')
-            dbg['log_evidence'] = up.log_evidence.cpu().numpy()
-        if annotator_flip is not None:
-            dbg['flipped'] = flipped
-        if Q > 1:
-            dbg.update(sess)
-        if calibrate is not None:
-            dbg['calibration'] = fit
-        if posterior == 'ensemble' and (observe_by == 'info_gain' or rank_by == 'span_bald'):
-            dbg.update(weight=up.weight.cpu().numpy(), ens_log_evidence=up.ens_log_evidence.cpu().numpy(),
-                       expected_entropy=up.expected_entropy.cpu().numpy(), span_bald=up.span_bald.cpu().numpy())
-        return data_old, dbg
+        return data_old, _round_debug(scored, fitted, chosen, idx, asked, renewed)
     return data_old
 
 
@@ -1397,21 +1439,19 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         soft = {}
     t0 = time.perf_counter()
     prev = bank if bank is not None and bank.K >= (1 if posterior == 'ensemble' else 2) else None
-    Qn = check_questions(questions_per_clip, stop_entropy, observe_by, acquire_by)      # (on every rank, before rank 0 goes its own way)
-    check_calibration(temperature, calibrate, observe_by, acquire_by, renew_by, soft)
-    check_posterior(posterior, prev if posterior == 'ensemble' else None, None, rank_by, observe_by, renew_by, acquire_by, soft, Qn, calibrate)
+    switches = dict(posterior=posterior, bank=prev, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
+                    soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip, questions_per_clip=questions_per_clip,
+                    stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate)
+    pol = check_round(**switches)                                # (on every rank, before rank 0 goes its own way)
+    want_debug = pol.Q > 1 or calibrate is not None
     new_data = sessions = calibration = None
     if rank == 0:
-        new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, bank=prev,
-                                 mc_stat=mc_stat, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
-                                 soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip,
-                                 questions_per_clip=Qn, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate,
-                                 **(dict(posterior=posterior, rank_by=rank_by) if posterior == 'ensemble' else dict(rank_by=rank_by)),
-                                 return_debug=Qn > 1 or calibrate is not None)
-        if Qn > 1 or calibrate is not None:
+        new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, mc_stat=mc_stat,
+                                 return_debug=want_debug, **switches)
+        if want_debug:
             new_data, dbg = new_data
             calibration = dbg.get('calibration')
-        if Qn > 1:
+        if pol.Q > 1:
             sessions = {k: dbg[k] for k in ('asked', 'answers', 'n_asked', 'entropy_path', 'stop_reason')}
     new_data = hdist.broadcast_object(new_data)
     if soft is not None:

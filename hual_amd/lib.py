@@ -388,24 +388,96 @@ def _span_inputs(who, aset, s0, e0, tlen):
     return N, ld, s0.device
 
 
-def _span_sel(who, sel, dev):
-    """sel: device i32 [nsel] sample ids or None -> nsel, 0 without a list"""
+def _span_index(who, name, x, shape, dev, required=False, text=None):
+    """the gate of every int32 device argument of the span-posterior launches (sel, cand, old_idx, gt, budget, flip): None - unless
+    `required` -, or a contiguous int32 tensor on the logits' device of `shape`, an entry of which is an extent or a range of extents;
+    text: how the message words the shape (default: its numbers)"""
     import torch
-    if sel is None:
-        return 0
-    if sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < 1 or not sel.is_contiguous() or sel.device != dev:
-        raise HualError('%s: sel must be a contiguous, non-empty int32 [nsel] on the logits\' device' % who)
-    return int(sel.numel())
+    if x is None and not required:
+        return
+    ok = x is not None and x.dtype == torch.int32 and x.is_contiguous() and x.device == dev and (
+        tuple(x.shape) == shape or x.dim() == len(shape) and all(d == w or isinstance(w, range) and d in w for d, w in zip(x.shape, shape)))
+    if not ok:
+        raise HualError('%s: %s must be a contiguous int32 %s on the logits\' device' % (who, name, text or list(shape)))
 
 
-def _span_out(who, out, spec, optional, dev):
-    """out: the caller's tuple of tensors to write into, against spec = [(name, shape, dtype)]; only the names in `optional` may be None"""
-    names = ', '.join(name for name, _, _ in spec)
-    if len(out) != len(spec) or any(o is None and name not in optional for o, (name, _, _) in zip(out, spec)):
-        raise HualError('%s: out is (%s)%s' % (who, names, '; only %s may be None' % ' / '.join(optional) if optional else ''))
+def _span_sel(who, sel, N, dev):
+    """sel: device i32 [nsel] sample ids or None -> nsel, N without a list"""
+    _span_index(who, 'sel', sel, (range(1, 2 ** 31),), dev, text='[nsel], nsel >= 1,')
+    return N if sel is None else int(sel.numel())
+
+
+AL_GAIN_MAX_CAND = 256      # candidate frames per sample of hual_al_label_gain
+AL_ENS_MAX_K = 16           # passes per hual_al_ensemble_query / hual_al_ensemble_label launch
+AL_GRID_MAX_TAU = 32        # temperatures per hual_al_evidence_grid launch
+AL_GRID_MAX_EPS = 16        # error rates per launch (csrc/spancalib.h)
+AL_SESSION_MAX_Q = 16           # question slots per sample of hual_al_session
+AL_SESSION_MAX_POINTS = 64      # active points of one sample, the set's and the session's, that hual_al_session holds
+AL_STOP_REASONS = ('budget', 'entropy', 'gain', 'contradictory', 'poisoned', 'overflow')      # HUAL_AL_STOP_*, by value
+
+# The outputs of every span-posterior launch, in the order the C entry point takes them: (name, shape, dtype, fill, optional).
+# shape: extents by name - N, ld, K (passes), Q (question slots), Q1 = Q + 1, AB (grid cells) - or as numbers; fill: what a tensor
+# allocated here holds before the launch writes its part (None: left uninitialised, the launch writes all of it); optional: the caller
+# may leave it out (None) - a switch of the wrapper (frames=, marginals=, old_idx=) does so for tensors allocated here.
+_NAN = float('nan')
+_LABEL_OUT = (('new_idx', ('N', 2), 'int32', -1, False), ('conf', ('N',), 'float32', -1, False), ('old_conf', ('N',), 'float32', -1, True))
+_GAIN_OUT = (('gain', ('N', 'ld'), 'float32', 0, True), ('ask_point', ('N',), 'int32', -1, False), ('ask_gain', ('N',), 'float32', -1, False),
+             ('value', ('N',), 'float32', -1, False))
+_SPAN_OUT = {
+    'al_query': (('incl', ('N', 'ld'), 'float32', 0, True), ('gain', ('N', 'ld'), 'float32', 0, True), ('query_point', ('N',), 'int32', None, False),
+                 ('query_gain', ('N',), 'float32', None, False), ('post_entropy', ('N',), 'float32', None, False),
+                 ('agree', ('N',), 'float32', None, False)),
+    'al_mbr_label': _LABEL_OUT,
+    'al_ensemble_label': _LABEL_OUT,
+    'al_label_gain': _GAIN_OUT,
+    'al_label_gain_noisy': _GAIN_OUT,
+    'al_span_marginals': (('y_start', ('N', 'ld'), 'float32', 0, False), ('y_end', ('N', 'ld'), 'float32', 0, False),
+                          ('status', ('N',), 'int32', 0, False)),
+    'al_noisy_tilt': (('s_t', ('N', 'ld'), 'float32', 0, False), ('e_t', ('N', 'ld'), 'float32', 0, False),
+                      ('log_evidence', ('N',), 'float32', None, False)),
+    'al_ensemble_query': (('weight', ('N', 'K'), 'float32', None, False), ('log_evidence', ('N',), 'float32', None, False),
+                          ('incl', ('N', 'ld'), 'float32', 0, True), ('gain', ('N', 'ld'), 'float32', 0, True),
+                          ('query_point', ('N',), 'int32', None, False), ('query_gain', ('N',), 'float32', None, False),
+                          ('y_start', ('N', 'ld'), 'float32', 0, True), ('y_end', ('N', 'ld'), 'float32', 0, True),
+                          ('post_entropy', ('N',), 'float32', None, False), ('expected_entropy', ('N',), 'float32', None, False),
+                          ('span_bald', ('N',), 'float32', None, False), ('status', ('N',), 'int32', None, False)),
+    'al_evidence_grid': (('table', ('N', 'AB'), 'float64', _NAN, False), ('status', ('N',), 'int32', -1, False),
+                         ('total', ('AB',), 'float64', None, False), ('counts', (4,), 'int32', None, False)),
+    'al_session': (('asked', ('N', 'Q'), 'int32', -1, False), ('answer', ('N', 'Q'), 'int8', -1, False), ('q_asked', ('N', 'Q'), 'float32', -1, False),
+                   ('gain', ('N', 'Q'), 'float32', -1, False), ('entropy', ('N', 'Q1'), 'float32', -1, False), ('n_asked', ('N',), 'int32', -1, False),
+                   ('stop_reason', ('N',), 'int32', -1, False)),
+}
+AL_ENS_QUERY_OUT = tuple(name for name, _, _, _, _ in _SPAN_OUT['al_ensemble_query'])
+
+
+def _span_out(who, out, dev, off=(), tied=None, both=(), **extent):
+    """the output tuple of the launch `who` (its row of _SPAN_OUT) at the extents given by name.  out None: allocated here with the
+    spec's fills, the outputs named in `off` left out.  Else the caller's tuple of tensors to write into, checked: only optional
+    outputs may be None; tied = (output, argument): that output is None exactly when it is named in `off` (when that argument is
+    None); both: two outputs that are given or left out together."""
+    import torch
+    if out is None:
+        return tuple([None if name in off else torch.full([extent.get(d, d) for d in shape], fill, dtype=getattr(torch, dt), device=dev) if fill
+                      else (torch.empty if fill is None else torch.zeros)(*[extent.get(d, d) for d in shape], dtype=getattr(torch, dt), device=dev)
+                      for name, shape, dt, fill, _ in _SPAN_OUT[who]])
+    spec = [(name, tuple(extent.get(d, d) for d in shape), getattr(torch, dt)) for name, shape, dt, _, _ in _SPAN_OUT[who]]
+    names = [name for name, _, _ in spec]
+    optional = [name for name, _, _, _, opt in _SPAN_OUT[who] if opt]
+    given = {name: o is not None for o, name in zip(out, names)}
+    if len(out) != len(spec) or not all(given[name] or name in optional for name in names) or (tied and given[tied[0]] == (tied[0] in off)):
+        rule = '%s is None exactly when %s is' % tied if tied else 'only %s may be None' % ' / '.join(optional) if optional else ''
+        raise HualError('%s: out is (%s)%s' % (who, ', '.join(names), '; ' + rule if rule else ''))
+    if both and given[both[0]] != given[both[1]]:
+        raise HualError('%s: %s and %s are both given or both None' % (who, both[0], both[1]))
     for o, (name, shape, dt) in zip(out, spec):
         if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
             raise HualError('%s: %s must be a contiguous %s %s on the logits\' device' % (who, name, str(dt).replace('torch.', ''), list(shape)))
+    return tuple(out)
+
+
+def _launch(entry, aset, *args):
+    """one C entry point of the family on the hual_al_set `aset`: tensors go as their device pointers, the current stream last"""
+    check(getattr(load(), entry)(ctypes.byref(aset), *[ptr(a) if a is None or hasattr(a, 'data_ptr') else a for a in args], stream_ptr()))
 
 
 def al_query(aset, s0, e0, tlen, frames=True, out=None):
@@ -416,17 +488,19 @@ def al_query(aset, s0, e0, tlen, frames=True, out=None):
     -> (incl, gain, query_point, query_gain, post_entropy, agree): f32 [N, ld] twice (None with frames=False: only the per-sample outputs
     are written), i32 [N], f32 [N] three times.  out: such a tuple of contiguous device tensors to write into instead (incl / gain may be
     None); columns beyond a row's tlen keep what they held (0 in tensors allocated here)."""
-    import torch
     N, ld, dev = _span_inputs('al_query', aset, s0, e0, tlen)
-    if out is None:
-        out = (torch.zeros(N, ld, device=dev) if frames else None, torch.zeros(N, ld, device=dev) if frames else None,
-               torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev))
-    else:
-        f32 = torch.float32
-        _span_out('al_query', out, [('incl', (N, ld), f32), ('gain', (N, ld), f32), ('query_point', (N,), torch.int32),
-                                    ('query_gain', (N,), f32), ('post_entropy', (N,), f32), ('agree', (N,), f32)], ('incl', 'gain'), dev)
-    check(load().hual_al_query(ctypes.byref(aset), ptr(s0), ptr(e0), *[ptr(o) for o in out], stream_ptr()))
-    return tuple(out)
+    out = _span_out('al_query', out, dev, off=() if frames else ('incl', 'gain'), N=N, ld=ld)
+    _launch('hual_al_query', aset, s0, e0, *out)
+    return out
+
+
+def _label(who, entry, head, N, dev, sel, old_idx, out):
+    """al_mbr_label and al_ensemble_label behind their input gates; head: the entry point's arguments before sel"""
+    nsel = _span_sel(who, sel, N, dev)
+    _span_index(who, 'old_idx', old_idx, (N, 2), dev)
+    out = _span_out(who, out, dev, off=('old_conf',) if old_idx is None else (), tied=('old_conf', 'old_idx'), N=N)
+    _launch(entry, *head, sel, nsel, old_idx, *out)
+    return out
 
 
 def al_mbr_label(aset, s0, e0, tlen, sel=None, old_idx=None, out=None):
@@ -438,37 +512,17 @@ def al_mbr_label(aset, s0, e0, tlen, sel=None, old_idx=None, out=None):
     -> (new_idx i32 [N, 2], conf f32 [N], old_conf f32 [N] or None).  out: such a tuple of contiguous device tensors to write into
     instead (old_conf None exactly when old_idx is).  Only the rows of selected samples are written: the others keep what they held
     (-1 in tensors allocated here, the value of a row that gives no label)."""
-    import torch
     N, ld, dev = _span_inputs('al_mbr_label', aset, s0, e0, tlen)
-    nsel = _span_sel('al_mbr_label', sel, dev) or N
-    if old_idx is not None and (old_idx.dtype != torch.int32 or tuple(old_idx.shape) != (N, 2) or not old_idx.is_contiguous()
-                                or old_idx.device != dev):
-        raise HualError('al_mbr_label: old_idx must be contiguous int32 [N, 2] on the logits\' device')
-    if out is None:
-        out = (torch.full((N, 2), -1, dtype=torch.int32, device=dev), torch.full((N,), -1.0, device=dev),
-               torch.full((N,), -1.0, device=dev) if old_idx is not None else None)
-    else:
-        if len(out) != 3 or out[0] is None or out[1] is None or (out[2] is None) != (old_idx is None):
-            raise HualError('al_mbr_label: out is (new_idx, conf, old_conf); old_conf is None exactly when old_idx is')
-        _span_out('al_mbr_label', out, [('new_idx', (N, 2), torch.int32), ('conf', (N,), torch.float32), ('old_conf', (N,), torch.float32)],
-                  ('old_conf',), dev)
-    check(load().hual_al_mbr_label(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, ptr(old_idx), ptr(out[0]), ptr(out[1]),
-                                   ptr(out[2]), stream_ptr()))
-    return tuple(out)
+    return _label('al_mbr_label', 'hual_al_mbr_label', (aset, s0, e0), N, dev, sel, old_idx, out)
 
 
-AL_GAIN_MAX_CAND = 256      # candidate frames per sample of hual_al_label_gain
-
-
-def _span_cand(who, cand, N, dev):
-    """cand: device i32 [N, M] candidate frames or None -> M, 0 without a list"""
-    import torch
-    if cand is None:
-        return 0
-    if (cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != N or not 1 <= cand.shape[1] <= AL_GAIN_MAX_CAND
-            or not cand.is_contiguous() or cand.device != dev):
-        raise HualError('%s: cand must be contiguous int32 [N, M], 1 <= M <= %d, on the logits\' device' % (who, AL_GAIN_MAX_CAND))
-    return int(cand.shape[1])
+def _label_gain(who, entry, head, N, ld, dev, sel, cand, frames, out):
+    """al_label_gain and al_label_gain_noisy behind their input gate; head: the entry point's arguments before sel"""
+    nsel = _span_sel(who, sel, N, dev)
+    _span_index(who, 'cand', cand, (N, range(1, AL_GAIN_MAX_CAND + 1)), dev, text='[N, M], 1 <= M <= %d,' % AL_GAIN_MAX_CAND)
+    out = _span_out(who, out, dev, off=() if frames else ('gain',), N=N, ld=ld)
+    _launch(entry, *head, sel, nsel, cand, 0 if cand is None else int(cand.shape[1]), *out)
+    return out
 
 
 def al_label_gain(aset, s0, e0, tlen, sel=None, cand=None, frames=True, out=None):
@@ -483,19 +537,8 @@ def al_label_gain(aset, s0, e0, tlen, sel=None, cand=None, frames=True, out=None
     contiguous device tensors to write into instead (gain may be None).  Only the rows of selected samples are written, and of gain only
     the columns below a row's tlen: the rest keeps what it held (gain 0, ask_point -1, ask_gain and value -1 in tensors allocated here -
     the values of a row that has no answer to give)."""
-    import torch
     N, ld, dev = _span_inputs('al_label_gain', aset, s0, e0, tlen)
-    nsel = _span_sel('al_label_gain', sel, dev) or N
-    M = _span_cand('al_label_gain', cand, N, dev)
-    if out is None:
-        out = (torch.zeros(N, ld, device=dev) if frames else None, torch.full((N,), -1, dtype=torch.int32, device=dev),
-               torch.full((N,), -1.0, device=dev), torch.full((N,), -1.0, device=dev))
-    else:
-        _span_out('al_label_gain', out, [('gain', (N, ld), torch.float32), ('ask_point', (N,), torch.int32), ('ask_gain', (N,), torch.float32),
-                                         ('value', (N,), torch.float32)], ('gain',), dev)
-    check(load().hual_al_label_gain(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, ptr(cand), M, *[ptr(o) for o in out],
-                                    stream_ptr()))
-    return tuple(out)
+    return _label_gain('al_label_gain', 'hual_al_label_gain', (aset, s0, e0), N, ld, dev, sel, cand, frames, out)
 
 
 def al_span_marginals(aset, s0, e0, tlen, out=None):
@@ -506,15 +549,10 @@ def al_span_marginals(aset, s0, e0, tlen, out=None):
     -> (y_start f32 [N, ld], y_end f32 [N, ld], status i32 [N]): status 1 = a live row, 0 = a poisoned or contradictory one, whose
     columns are 0.  out: such a tuple of contiguous device tensors to write into instead; columns beyond a row's tlen keep what they
     held (0 in tensors allocated here)."""
-    import torch
     N, ld, dev = _span_inputs('al_span_marginals', aset, s0, e0, tlen)
-    if out is None:
-        out = (torch.zeros(N, ld, device=dev), torch.zeros(N, ld, device=dev), torch.zeros(N, dtype=torch.int32, device=dev))
-    else:
-        _span_out('al_span_marginals', out, [('y_start', (N, ld), torch.float32), ('y_end', (N, ld), torch.float32), ('status', (N,), torch.int32)],
-                  (), dev)
-    check(load().hual_al_span_marginals(ctypes.byref(aset), ptr(s0), ptr(e0), *[ptr(o) for o in out], stream_ptr()))
-    return tuple(out)
+    out = _span_out('al_span_marginals', out, dev, N=N, ld=ld)
+    _launch('hual_al_span_marginals', aset, s0, e0, *out)
+    return out
 
 
 def al_noisy_tilt(aset, s0, e0, tlen, eps, out=None):
@@ -526,15 +564,10 @@ def al_noisy_tilt(aset, s0, e0, tlen, eps, out=None):
     -> (s_t f32 [N, ld], e_t f32 [N, ld], log_evidence f32 [N]): the tilted logits and ln P(the answers | the model, eps), NaN on a
     poisoned row (whose columns are raw copies).  out: such a tuple of contiguous device tensors to write into instead; columns beyond
     a row's tlen keep what they held (0 in tensors allocated here)."""
-    import torch
     N, ld, dev = _span_inputs('al_noisy_tilt', aset, s0, e0, tlen)
-    if out is None:
-        out = (torch.zeros(N, ld, device=dev), torch.zeros(N, ld, device=dev), torch.empty(N, device=dev))
-    else:
-        _span_out('al_noisy_tilt', out, [('s_t', (N, ld), torch.float32), ('e_t', (N, ld), torch.float32), ('log_evidence', (N,), torch.float32)],
-                  (), dev)
-    check(load().hual_al_noisy_tilt(ctypes.byref(aset), ptr(s0), ptr(e0), float(eps), *[ptr(o) for o in out], stream_ptr()))
-    return tuple(out)
+    out = _span_out('al_noisy_tilt', out, dev, N=N, ld=ld)
+    _launch('hual_al_noisy_tilt', aset, s0, e0, float(eps), *out)
+    return out
 
 
 def al_label_gain_noisy(aset, s_t, e_t, tlen, eps, sel=None, cand=None, frames=True, out=None):
@@ -544,22 +577,8 @@ def al_label_gain_noisy(aset, s_t, e_t, tlen, eps, sel=None, cand=None, frames=T
     al_noisy_tilt, f32 [N, ld] on the device; of `aset` only N, ld, vlen and tlen are read (the answers are in the rows); tlen, sel,
     cand, frames, out and the returned (gain, ask_point, ask_gain, value) are al_label_gain's; value is al_mbr_label's conf on the same
     rows and a set without answers."""
-    import torch
     N, ld, dev = _span_inputs('al_label_gain_noisy', aset, s_t, e_t, tlen)
-    nsel = _span_sel('al_label_gain_noisy', sel, dev) or N
-    M = _span_cand('al_label_gain_noisy', cand, N, dev)
-    if out is None:
-        out = (torch.zeros(N, ld, device=dev) if frames else None, torch.full((N,), -1, dtype=torch.int32, device=dev),
-               torch.full((N,), -1.0, device=dev), torch.full((N,), -1.0, device=dev))
-    else:
-        _span_out('al_label_gain_noisy', out, [('gain', (N, ld), torch.float32), ('ask_point', (N,), torch.int32),
-                                               ('ask_gain', (N,), torch.float32), ('value', (N,), torch.float32)], ('gain',), dev)
-    check(load().hual_al_label_gain_noisy(ctypes.byref(aset), ptr(s_t), ptr(e_t), float(eps), ptr(sel), nsel, ptr(cand), M,
-                                          *[ptr(o) for o in out], stream_ptr()))
-    return tuple(out)
-
-
-AL_ENS_MAX_K = 16      # passes per hual_al_ensemble_query / hual_al_ensemble_label launch
+    return _label_gain('al_label_gain_noisy', 'hual_al_label_gain_noisy', (aset, s_t, e_t, float(eps)), N, ld, dev, sel, cand, frames, out)
 
 
 def _ens_inputs(who, aset, pass_s, pass_e, tlen, logw):
@@ -579,10 +598,6 @@ def _ens_inputs(who, aset, pass_s, pass_e, tlen, logw):
     return K, N, ld, dev
 
 
-AL_ENS_QUERY_OUT = ('weight', 'log_evidence', 'incl', 'gain', 'query_point', 'query_gain', 'y_start', 'y_end', 'post_entropy',
-                    'expected_entropy', 'span_bald', 'status')
-
-
 def al_ensemble_query(aset, pass_s, pass_e, tlen, logw=None, frames=True, marginals=True, out=None):
     """the span posterior of every sample of the hual_al_set `aset` as the Bayesian model average over K stochastic passes, each
     weighted by its evidence of the answered active points (hual_al_ensemble_query), one launch enqueued on the current stream.
@@ -595,22 +610,11 @@ def al_ensemble_query(aset, pass_s, pass_e, tlen, logw=None, frames=True, margin
     the dropout mask, bits) f32 [N], status i32 [N] (1 = live).  out: such a tuple of contiguous device tensors to write into instead
     (incl / gain may be None, y_start / y_end both or neither); columns beyond a row's tlen keep what they held (0 in tensors allocated
     here)."""
-    import torch
     K, N, ld, dev = _ens_inputs('al_ensemble_query', aset, pass_s, pass_e, tlen, logw)
-    f32, i32 = torch.float32, torch.int32
-    spec = [('weight', (N, K), f32), ('log_evidence', (N,), f32), ('incl', (N, ld), f32), ('gain', (N, ld), f32), ('query_point', (N,), i32),
-            ('query_gain', (N,), f32), ('y_start', (N, ld), f32), ('y_end', (N, ld), f32), ('post_entropy', (N,), f32),
-            ('expected_entropy', (N,), f32), ('span_bald', (N,), f32), ('status', (N,), i32)]
-    if out is None:
-        off = (() if frames else ('incl', 'gain')) + (() if marginals else ('y_start', 'y_end'))
-        out = tuple(None if name in off else (torch.zeros if len(shape) == 2 and name != 'weight' else torch.empty)(shape, dtype=dt, device=dev)
-                    for name, shape, dt in spec)
-    else:
-        _span_out('al_ensemble_query', out, spec, ('incl', 'gain', 'y_start', 'y_end'), dev)
-        if (out[6] is None) != (out[7] is None):
-            raise HualError('al_ensemble_query: y_start and y_end are both given or both None')
-    check(load().hual_al_ensemble_query(ctypes.byref(aset), ptr(pass_s), ptr(pass_e), K, ptr(logw), *[ptr(o) for o in out], stream_ptr()))
-    return tuple(out)
+    off = (() if frames else ('incl', 'gain')) + (() if marginals else ('y_start', 'y_end'))
+    out = _span_out('al_ensemble_query', out, dev, off=off, both=('y_start', 'y_end'), N=N, ld=ld, K=K)
+    _launch('hual_al_ensemble_query', aset, pass_s, pass_e, K, logw, *out)
+    return out
 
 
 def al_ensemble_label(aset, pass_s, pass_e, tlen, logw=None, sel=None, old_idx=None, out=None):
@@ -618,27 +622,8 @@ def al_ensemble_label(aset, pass_s, pass_e, tlen, logw=None, sel=None, old_idx=N
     the consistent set of maximal expected temporal IoU R(a, e) = sum_k w_k R_k(a, e), the passes' values weighted as in
     al_ensemble_query.  pass_s / pass_e, tlen and logw are al_ensemble_query's; sel, old_idx, out and the returned (new_idx i32 [N, 2],
     conf f32 [N], old_conf f32 [N] or None) are al_mbr_label's."""
-    import torch
     K, N, ld, dev = _ens_inputs('al_ensemble_label', aset, pass_s, pass_e, tlen, logw)
-    nsel = _span_sel('al_ensemble_label', sel, dev) or N
-    if old_idx is not None and (old_idx.dtype != torch.int32 or tuple(old_idx.shape) != (N, 2) or not old_idx.is_contiguous()
-                                or old_idx.device != dev):
-        raise HualError('al_ensemble_label: old_idx must be contiguous int32 [N, 2] on the logits\' device')
-    if out is None:
-        out = (torch.full((N, 2), -1, dtype=torch.int32, device=dev), torch.full((N,), -1.0, device=dev),
-               torch.full((N,), -1.0, device=dev) if old_idx is not None else None)
-    else:
-        if len(out) != 3 or out[0] is None or out[1] is None or (out[2] is None) != (old_idx is None):
-            raise HualError('al_ensemble_label: out is (new_idx, conf, old_conf); old_conf is None exactly when old_idx is')
-        _span_out('al_ensemble_label', out, [('new_idx', (N, 2), torch.int32), ('conf', (N,), torch.float32), ('old_conf', (N,), torch.float32)],
-                  ('old_conf',), dev)
-    check(load().hual_al_ensemble_label(ctypes.byref(aset), ptr(pass_s), ptr(pass_e), K, ptr(logw), ptr(sel), nsel, ptr(old_idx),
-                                        ptr(out[0]), ptr(out[1]), ptr(out[2]), stream_ptr()))
-    return tuple(out)
-
-
-AL_GRID_MAX_TAU = 32      # temperatures per hual_al_evidence_grid launch
-AL_GRID_MAX_EPS = 16      # error rates per launch (csrc/spancalib.h)
+    return _label('al_ensemble_label', 'hual_al_ensemble_label', (aset, pass_s, pass_e, K, logw), N, dev, sel, old_idx, out)
 
 
 def al_evidence_grid(aset, s0, e0, tlen, inv_tau, eps, sel=None, out=None):
@@ -653,28 +638,16 @@ def al_evidence_grid(aset, s0, e0, tlen, inv_tau, eps, sel=None, out=None):
     cell of maximal total (-1: no row was summed).  out: such a tuple of contiguous device tensors to write into instead.  Only the rows
     of selected samples are written in table and status: the others keep what they held (NaN and -1 in tensors allocated here)."""
     import numpy as np
-    import torch
     N, ld, dev = _span_inputs('al_evidence_grid', aset, s0, e0, tlen)
-    nsel = _span_sel('al_evidence_grid', sel, dev) or N
+    nsel = _span_sel('al_evidence_grid', sel, N, dev)
     it = np.ascontiguousarray(np.asarray(inv_tau, dtype=np.float32).reshape(-1))
     ep = np.ascontiguousarray(np.asarray(eps, dtype=np.float32).reshape(-1))
     A, B = int(it.size), int(ep.size)
     if not 1 <= A <= AL_GRID_MAX_TAU or not 1 <= B <= AL_GRID_MAX_EPS:
         raise HualError('al_evidence_grid: 1 to %d temperatures and 1 to %d error rates per launch' % (AL_GRID_MAX_TAU, AL_GRID_MAX_EPS))
-    spec = [('table', (N, A * B), torch.float64), ('status', (N,), torch.int32), ('total', (A * B,), torch.float64), ('counts', (4,), torch.int32)]
-    if out is None:
-        out = (torch.full((N, A * B), float('nan'), dtype=torch.float64, device=dev), torch.full((N,), -1, dtype=torch.int32, device=dev),
-               torch.empty(A * B, dtype=torch.float64, device=dev), torch.empty(4, dtype=torch.int32, device=dev))
-    else:
-        _span_out('al_evidence_grid', out, spec, (), dev)
-    check(load().hual_al_evidence_grid(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(sel), nsel, it.ctypes.data_as(ctypes.c_void_p), A,
-                                       ep.ctypes.data_as(ctypes.c_void_p), B, *[ptr(o) for o in out], stream_ptr()))
-    return tuple(out)
-
-
-AL_SESSION_MAX_Q = 16           # question slots per sample of hual_al_session
-AL_SESSION_MAX_POINTS = 64      # active points of one sample, the set's and the session's, that hual_al_session holds
-AL_STOP_REASONS = ('budget', 'entropy', 'gain', 'contradictory', 'poisoned', 'overflow')      # HUAL_AL_STOP_*, by value
+    out = _span_out('al_evidence_grid', out, dev, N=N, AB=A * B)
+    _launch('hual_al_evidence_grid', aset, s0, e0, sel, nsel, it.ctypes.data_as(ctypes.c_void_p), A, ep.ctypes.data_as(ctypes.c_void_p), B, *out)
+    return out
 
 
 def al_session(aset, s0, e0, tlen, gt, qmax, sel=None, budget=None, stop_entropy=-1.0, min_gain=0.0, eps=0.0, flip=None, out=None):
@@ -689,24 +662,14 @@ def al_session(aset, s0, e0, tlen, gt, qmax, sel=None, budget=None, stop_entropy
     stop_reason i32 [N]; AL_STOP_REASONS names its values).  out: such a tuple of contiguous device tensors to write into instead.
     Only the rows of selected samples are written: the others keep what they held (-1 in tensors allocated here, the value of an unused
     slot)."""
-    import torch
     N, ld, dev = _span_inputs('al_session', aset, s0, e0, tlen)
-    nsel = _span_sel('al_session', sel, dev) or N
+    nsel = _span_sel('al_session', sel, N, dev)
     qmax = int(qmax)
     if not 1 <= qmax <= AL_SESSION_MAX_Q:
         raise HualError('al_session: qmax must lie in [1, %d]' % AL_SESSION_MAX_Q)
-    for name, x, shape in (('gt', gt, (N, 2)), ('budget', budget, (N,)), ('flip', flip, (N,))):
-        if x is None and name != 'gt':
-            continue
-        if x is None or x.dtype != torch.int32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
-            raise HualError('al_session: %s must be a contiguous int32 %s on the logits\' device' % (name, list(shape)))
-    i32, f32 = torch.int32, torch.float32
-    spec = [('asked', (N, qmax), i32), ('answer', (N, qmax), torch.int8), ('q_asked', (N, qmax), f32), ('gain', (N, qmax), f32),
-            ('entropy', (N, qmax + 1), f32), ('n_asked', (N,), i32), ('stop_reason', (N,), i32)]
-    if out is None:
-        out = tuple(torch.full(shape, -1, dtype=dt, device=dev) for _, shape, dt in spec)
-    else:
-        _span_out('al_session', out, spec, (), dev)
-    check(load().hual_al_session(ctypes.byref(aset), ptr(s0), ptr(e0), ptr(gt), ptr(sel), nsel, qmax, ptr(budget), float(stop_entropy),
-                                 float(min_gain), float(eps), ptr(flip), *[ptr(o) for o in out], stream_ptr()))
-    return tuple(out)
+    _span_index('al_session', 'gt', gt, (N, 2), dev, required=True)
+    _span_index('al_session', 'budget', budget, (N,), dev)
+    _span_index('al_session', 'flip', flip, (N,), dev)
+    out = _span_out('al_session', out, dev, N=N, Q=qmax, Q1=qmax + 1)
+    _launch('hual_al_session', aset, s0, e0, gt, sel, nsel, qmax, budget, float(stop_entropy), float(min_gain), float(eps), flip, *out)
+    return out

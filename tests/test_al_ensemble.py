@@ -119,12 +119,12 @@ def test_host_side_plumbing():
             al.check_bank_planes(bank, K)
     ok = dict(posterior='ensemble', bank=_Bank(3, 3), mc_samples=None, rank_by='uncert_video', observe_by='info_gain', renew_by='heuristic',
               acquire_by=None, soft_out=None, questions_per_clip=1, calibrate=None)
-    al.check_posterior(**ok)
-    al.check_posterior(**dict(ok, observe_by='uncert_frame', rank_by='span_bald'))
-    al.check_posterior(**dict(ok, posterior='deterministic', bank=None))
+    al.check_round(**ok)
+    al.check_round(**dict(ok, observe_by='uncert_frame', rank_by='span_bald'))
+    al.check_round(**dict(ok, posterior='deterministic', bank=None))
     for bad in (dict(posterior='both'), dict(bank=None), dict(bank=_Bank(3, 0)), dict(acquire_by='label_gain'), dict(questions_per_clip=2),
                 dict(calibrate='evidence'), dict(observe_by='uncert_frame'), dict(mc_samples=4),
                 dict(posterior='deterministic', rank_by='span_bald')):
         with pytest.raises(ValueError):
-            al.check_posterior(**dict(ok, **bad))
+            al.check_round(**dict(ok, **bad))
     assert al.RANK_BY_ENSEMBLE == ('span_bald',) and al.POSTERIOR == ('deterministic', 'ensemble')
