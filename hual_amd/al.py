@@ -66,6 +66,11 @@ first fits a temperature tau and the error rate eps to the answers of the earlie
 ln P(answers | softmax(logits / tau), eps) (LabelUpdater.calibrate: hual_al_evidence_grid on a coarse grid and two zooms), and the
 round's posterior readers use the fitted pair (LabelUpdater.set_temperature; temperature= hands one in).  Off by default: every launch,
 record and result is then what it was.
+
+Question sets (an annotator who is not in the loop - a labelling tool, a crowd batch, one viewing of a clip - takes the frames of a
+clip together): update_labels(questions_at_once=M) asks every selected sample about the M frames of most JOINT information under its
+span posterior, the greedy design of the entropy of their answer vector (LabelUpdater.design, one hual_al_design launch for all of
+them), and answers them on the host.  Off by default: every launch, record and result is then what it was.
 """
 import collections
 import ctypes
@@ -979,6 +984,52 @@ class LabelUpdater:
         self.set_active_points(aps)
         return asked, answers, n_asked
 
+    def design(self, max_points, min_gain=0.0, stop_entropy=None, noise=None, forced=None, sel=None):
+        """the frames to ask TOGETHER about every sample (hual_al_design, one launch): for an annotator who is not in the loop - a
+        labelling tool, a crowd batch, one viewing of the clip - a greedy design of up to max_points (1..16) frames under the span
+        posterior given the set's answered active points.  The answers are a function of the span, so the information a set of frames
+        D carries is the entropy of its answer vector, I(D); step m takes the first frame of maximal I(D + t) - step 0 is query()'s
+        frame and gain - until the best marginal gain is at most min_gain bits (0: only a design that has nothing left to learn stops),
+        the expected entropy left, post_entropy - I(D), is at most stop_entropy bits (None: never), max_points frames are placed, or
+        the row is contradictory or poisoned.  forced: None or int [N, k], k <= max_points - a row's leading entries >= 0 are the first
+        frames of its design, placed without a stop test (-1 ends them; a frame beyond the clip is ignored; a repeated or already
+        answered one stays with 0 bits): how a hand-made grid or a bisection schedule is scored.  sel: None (every sample) or the
+        sample ids (numpy) to run.
+        noise=eps: the posterior under an annotator who errs with probability eps - the same launch on the tilted rows (tilt()) and the
+        set without answers, as query().  design_info is then the information of EXACT answers to the new questions: an upper bound on
+        what noisy answers to them carry.
+        Leaves design_frames (i32 [N, M], in the order chosen), design_info (f32 [N, M]: the information of the first m + 1 frames,
+        bits), design_entropy (f32 [N]: query()'s post_entropy), n_design and design_stop (i32 [N]; lib.AL_STOP_REASONS) as device
+        tensors - rows outside sel and unused slots hold -1.  Installs nothing: no answer exists yet.
+        Returns numpy (frames, n_design)."""
+        self._no_ensemble('design()')
+        M = int(max_points)
+        if not 1 <= M <= lib.AL_DESIGN_MAX_M:
+            raise ValueError('design: max_points must lie in [1, %d]' % lib.AL_DESIGN_MAX_M)
+        if not float(min_gain) >= 0.0:
+            raise ValueError('design: min_gain >= 0')
+        if stop_entropy is not None and not float(stop_entropy) >= 0.0:
+            raise ValueError('design: stop_entropy is None or bits >= 0')
+        rows = np.arange(self.N) if sel is None else np.asarray(sel, dtype=np.int64)
+        if rows.ndim != 1 or rows.size < 1 or rows.min() < 0 or rows.max() >= self.N:
+            raise ValueError('design: sel holds sample ids in [0, N)')
+        forced_h = None
+        if forced is not None:
+            f = np.asarray(forced, dtype=np.int64)
+            if f.ndim != 2 or f.shape[0] != self.N or not 1 <= f.shape[1] <= M:
+                raise ValueError('design: forced must hold N = %d rows of at most max_points frames' % self.N)
+            forced_h = np.full((self.N, M), -1, dtype=np.int32)
+            forced_h[:, :f.shape[1]] = np.clip(f, -1, 2 ** 31 - 1)
+
+        def dev32(x):
+            return torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
+        aset, s, e, _ = self._reads(noise)
+        (self.design_frames, self.design_info, self.design_entropy, self.n_design,
+         self.design_stop) = lib.al_design(aset, s, e, self.tlen_h, M, sel=None if sel is None else dev32(rows.astype(np.int32)),
+                                           forced=None if forced_h is None else dev32(forced_h), min_gain=float(min_gain),
+                                           stop_entropy=-1.0 if stop_entropy is None else float(stop_entropy))
+        return self.design_frames.cpu().numpy(), self.n_design.cpu().numpy()
+
     def label_gain(self, frames=True, cand=None, noise=None):
         """per frame, the tIoU the minimum-Bayes-risk label is expected to gain from the frame's answer under the span posterior given
         the set's answered active points (hual_al_label_gain, one launch over the whole set) on the updater's set and deterministic
@@ -1037,14 +1088,14 @@ CALIBRATE = (None, 'evidence')
 
 # check_round's result: the switches of a round as update_labels works from them - the enumerations as given; Q, the questions per
 # clip, an int; stop_entropy, noise and temperature floats or None; flip None or (rate, Generator); reads_posterior: one of the span
-# posterior's readers is on
+# posterior's readers is on; questions_at_once: M, the frames a selected sample is asked together
 RoundPolicy = collections.namedtuple('RoundPolicy', 'posterior rank_by observe_by renew_by acquire_by Q stop_entropy noise temperature '
-                                                    'calibrate flip reads_posterior')
+                                                    'calibrate flip reads_posterior questions_at_once')
 
 
 def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='uncert_video', observe_by='uncert_frame',
                 renew_by='heuristic', acquire_by=None, soft_out=None, answer_noise=None, annotator_flip=None, questions_per_clip=1,
-                stop_entropy=None, temperature=None, calibrate=None):
+                stop_entropy=None, temperature=None, calibrate=None, questions_at_once=1):
     """every rule between the switches of update_labels / run_round (their docstrings say what each switch does) -> RoundPolicy;
     raises ValueError, and touches nothing"""
     readers = {"observe_by='info_gain'": observe_by == 'info_gain', "acquire_by='label_gain'": acquire_by == 'label_gain',
@@ -1088,6 +1139,18 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
         raise ValueError("questions_per_clip > 1 needs observe_by='info_gain': a session asks by expected information gain")
     if stop_entropy is not None and not (Q > 1 and number(stop_entropy, lambda h: float(h) >= 0.0)):
         raise ValueError('stop_entropy: None, or bits >= 0 with questions_per_clip > 1')
+    # question sets: M frames per clip asked together, designed by information gain under the deterministic posterior
+    if not number(questions_at_once, lambda q: not isinstance(q, bool) and int(q) == q and 1 <= int(q) <= lib.AL_DESIGN_MAX_M):
+        raise ValueError('questions_at_once: an integer in [1, %d]' % lib.AL_DESIGN_MAX_M)
+    M = int(questions_at_once)
+    if M > 1 and posterior != 'deterministic':
+        raise ValueError("questions_at_once > 1 with posterior='ensemble' is not offered: the design has no ensemble form")
+    if M > 1 and acquire_by is not None:
+        raise ValueError("questions_at_once > 1 with acquire_by='label_gain' is not offered: a design asks by information gain")
+    if M > 1 and Q != 1:
+        raise ValueError('questions_at_once > 1 with questions_per_clip > 1 is not offered: a clip is asked adaptively or at once')
+    if M > 1 and observe_by != 'info_gain':
+        raise ValueError("questions_at_once > 1 needs observe_by='info_gain': a design asks by expected information gain")
     if soft_out is not None and not isinstance(soft_out, dict):
         raise ValueError('soft_out: None or a dict to receive y1, y2, live and answered')
     # the noisy annotator, the temperature and their fit change what the posterior's readers see
@@ -1122,7 +1185,7 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
         raise ValueError("acquire_by='%s' chooses the samples and the frames itself: leave rank_by and observe_by at their defaults"
                          % acquire_by)
     return RoundPolicy(posterior, rank_by, observe_by, renew_by, acquire_by, Q, None if stop_entropy is None else float(stop_entropy), noise,
-                       None if temperature is None else float(temperature), calibrate, annotator_flip, any(readers.values()))
+                       None if temperature is None else float(temperature), calibrate, annotator_flip, any(readers.values()), M)
 
 
 def span_risk(last_prop):
@@ -1188,28 +1251,34 @@ def _round_choose(up, pol, noise, risk, frames):
 
 def _round_ask(up, pol, noise, sel, ask, gt_idx, data_old, aps):
     """append_AP (utils_hual.py:133-139): the annotator answers "is the observed frame inside the ground-truth span?" - up to Q times
-    for a selected sample whose first question has a positive gain (one session launch for all of them), once at the chosen frame for
-    every other; the answers go into data_old and aps, and the updater takes the new lists"""
-    N, Q = len(aps), pol.Q
+    for a selected sample whose first question has a positive gain (one session launch for all of them), or about the M frames of
+    its design at once (one design launch for all of them, answered here), once at the chosen frame for every other; the answers go
+    into data_old and aps, and the updater takes the new lists"""
+    N, Q, M = len(aps), pol.Q, pol.questions_at_once
     flips = np.zeros(N, dtype=np.uint32)                         # bit k: the sample's k-th answer is wrong
     if pol.flip is not None:
         rate, rng = pol.flip
-        for i in sel:                                            # Q draws per selected sample, in selection order, used or not
-            for k in range(Q):
+        for i in sel:                                            # Q (M for a design) draws per selected sample, in selection order, used or not
+            for k in range(max(Q, M)):
                 if rng.random() < rate:
                     flips[i] |= np.uint32(1 << k)
-    in_session = np.zeros(0, dtype=np.int64)
-    if Q > 1:                                                    # (sessions need observe_by='info_gain': query() ran and left query_gain)
+    in_session = in_design = np.zeros(0, dtype=np.int64)
+    if Q > 1 or M > 1:                                           # (both need observe_by='info_gain': query() ran and left query_gain)
         has_gain = up.query_gain.cpu().numpy() > 0
-        in_session = sel[has_gain[sel]]
+        in_session, in_design = (sel[has_gain[sel]], in_design) if Q > 1 else (in_session, sel[has_gain[sel]])
     if len(in_session):
         asked, answers, n_asked = up.session(gt_idx, Q, stop_entropy=pol.stop_entropy, noise=noise, flips=flips, sel=in_session)
+    if len(in_design):                                           # one launch for all of them; the annotator answers below, on the host
+        frames, n_design = up.design(M, noise=noise, sel=in_design)
     session, ask, gt, wrong = set(in_session.tolist()), ask.tolist(), gt_idx.tolist(), flips.tolist()      # (plain lists: the loop below is per sample)
+    designed = set(in_design.tolist())
     given, flipped = {}, np.zeros(N, dtype=bool)                 # given: sample -> this round's (frame, is_pos), in the order asked
     for i in sel.tolist():
         if i in session:
             given[i] = [(int(asked[i, k]), bool(answers[i, k])) for k in range(n_asked[i])]
-        else:                                                    # no session: the reference's or the chosen frame, one question
+        elif i in designed:                                      # the design's frames, answered together: draw k decides answer k
+            given[i] = [(int(p), (gt[i][0] <= int(p) <= gt[i][1]) != bool((wrong[i] >> k) & 1)) for k, p in enumerate(frames[i, :n_design[i]])]
+        else:                                                    # neither: the reference's or the chosen frame, one question
             given[i] = [(ask[i], (gt[i][0] <= ask[i] <= gt[i][1]) != bool(wrong[i] & 1))]
         if wrong[i] & ((1 << len(given[i])) - 1):
             flipped[i] = True
@@ -1226,6 +1295,13 @@ def _round_ask(up, pol, noise, sel, ask, gt_idx, data_old, aps):
         if len(in_session):
             dbg['entropy_path'][in_session] = up.entropy_path.cpu().numpy()[in_session]
             dbg['stop_reason'][in_session] = up.stop_reason.cpu().numpy()[in_session]
+    if M > 1:                                                    # the designs as the launch left them: -1 = unused / no design
+        dbg = dict(design=np.full((N, M), -1, dtype=np.int64), design_info=np.full((N, M), -1.0, dtype=np.float32),
+                   n_design=np.zeros(N, dtype=np.int64), design_stop=np.full(N, -1, dtype=np.int64))
+        if len(in_design):
+            dbg['design'][in_design], dbg['n_design'][in_design] = frames[in_design], n_design[in_design]
+            dbg['design_info'][in_design] = up.design_info.cpu().numpy()[in_design]
+            dbg['design_stop'][in_design] = up.design_stop.cpu().numpy()[in_design]
     if pol.flip is not None:
         dbg['flipped'] = flipped
     if noise is not None and pol.posterior != 'ensemble':        # (the ensemble's readers tilt the passes themselves, on demand)
@@ -1270,7 +1346,7 @@ def _round_debug(*parts):
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
                   rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
                   answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None,
-                  posterior='deterministic'):
+                  posterior='deterministic', questions_at_once=1):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -1343,10 +1419,23 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     and are refused.  Under answer_noise the deterministic logits are not tilted and the debug dict has no 'log_evidence'.  The debug
     dict gains 'weight' (float32 [N, K]), 'ens_log_evidence', 'expected_entropy' and 'span_bald' (float32
     [N]) as the query left them: on the answers of the earlier rounds.
+    questions_at_once: 1 (every launch and result as without the argument), or M in 2..16 with observe_by='info_gain',
+    questions_per_clip=1, no acquire_by and the deterministic posterior - the annotator is then not in the loop: every selected sample
+    whose first question has a positive gain (the test sessions use) is asked about up to M frames TOGETHER, the greedy design of
+    most joint information under its span posterior given the answers of the earlier rounds (LabelUpdater.design, one launch for all
+    of them, with the round's answer_noise and temperature; its first frame is the single question's).  The truthful annotator
+    answers the design's frames on the host, as append_AP does; annotator_flip then draws M numbers per selected sample, in selection
+    order, used or not: draw k decides the sample's k-th answer.  pos_idx / neg_idx receive the answers in design order; every other
+    selected sample takes the reference's frame, one question; renew, soft_out and the time conversion read the lists afterwards,
+    unchanged.  The debug dict gains 'design' (int [N, M], -1 = unused), 'design_info' (float32 [N, M]: the information of the first
+    m + 1 frames, bits), 'n_design' and 'design_stop' (int [N], lib.AL_STOP_REASONS; -1: no design), as the launch left them: a
+    sample without a design holds -1 / 0 there.  Under answer_noise the corner of the sessions applies: the kernel stops on the
+    float32 h2(q) > 0, so a sample the float64 test lets in may come back with an empty design and gets no question this round.
     """
     pol = check_round(posterior=posterior, bank=bank, mc_samples=mc_samples, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by,
                       acquire_by=acquire_by, soft_out=soft_out, answer_noise=answer_noise, annotator_flip=annotator_flip,
-                      questions_per_clip=questions_per_clip, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate)
+                      questions_per_clip=questions_per_clip, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate,
+                      questions_at_once=questions_at_once)
     risk = span_risk(last_prop) if pol.rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -1389,7 +1478,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
               observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
               annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None, posterior='deterministic',
-              rank_by='uncert_video'):
+              rank_by='uncert_video', questions_at_once=1):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -1410,6 +1499,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     questions_per_clip / stop_entropy: the questions a selected sample may be asked in the round, as one session on the device, and the
     posterior entropy at which a session stops (update_labels); with more than one, metrics['sessions'] holds the transcripts (asked,
     answers, n_asked, entropy_path, stop_reason).
+    questions_at_once: the frames a selected sample is asked TOGETHER in the round, designed in one launch on the device and answered on
+    the host (update_labels); with more than one, metrics['designs'] holds them (design, design_info, n_design, design_stop).
     temperature / calibrate: the temperature of the round's span posterior, and its fit - with the annotator's error rate - to the
     answers of the earlier rounds by their evidence (update_labels); metrics['calibration'] holds the fit under calibrate.
     posterior / rank_by: 'ensemble' reads the round's span posterior as the model average over the passes `bank` holds from the
@@ -1441,10 +1532,10 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     prev = bank if bank is not None and bank.K >= (1 if posterior == 'ensemble' else 2) else None
     switches = dict(posterior=posterior, bank=prev, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
                     soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip, questions_per_clip=questions_per_clip,
-                    stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate)
+                    stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate, questions_at_once=questions_at_once)
     pol = check_round(**switches)                                # (on every rank, before rank 0 goes its own way)
-    want_debug = pol.Q > 1 or calibrate is not None
-    new_data = sessions = calibration = None
+    want_debug = pol.Q > 1 or pol.questions_at_once > 1 or calibrate is not None
+    new_data = sessions = designs = calibration = None
     if rank == 0:
         new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, mc_stat=mc_stat,
                                  return_debug=want_debug, **switches)
@@ -1453,6 +1544,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
             calibration = dbg.get('calibration')
         if pol.Q > 1:
             sessions = {k: dbg[k] for k in ('asked', 'answers', 'n_asked', 'entropy_path', 'stop_reason')}
+        if pol.questions_at_once > 1:
+            designs = {k: dbg[k] for k in ('design', 'design_info', 'n_design', 'design_stop')}
     new_data = hdist.broadcast_object(new_data)
     if soft is not None:
         weighted = soft['live'] & soft['answered']
@@ -1496,6 +1589,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         m['soft_rows'] = int(weighted.sum())
     if sessions is not None:
         m['sessions'] = sessions
+    if designs is not None:
+        m['designs'] = designs
     if calibrate is not None:
         m['calibration'] = calibration
     if log and rank == 0:

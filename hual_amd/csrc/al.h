@@ -113,6 +113,19 @@ struct AlSessionArgs {
   int32_t *n_asked, *stop_reason;             // [N]
 };
 
+// hual_al_design (spandesign.hip): the frames to ask TOGETHER about every selected sample - a greedy design under the span posterior
+struct AlDesignArgs {
+  AlSpanIn in;
+  const int32_t* sel;                         // [nsel] sample ids (NULL: all)
+  int mmax;                                   // 1..16 frames per sample
+  const int32_t* forced;                      // [N, mmax] the leading entries >= 0: the design's first frames; -1 ends them (NULL: none)
+  float min_gain, stop_entropy;               // bits; stop_entropy < 0: off
+  int32_t* frames;                            // [N, mmax] in the order chosen, unused slots -1
+  float* info;                                // [N, mmax] I(t_1 .. t_{m+1}) in bits, unused slots -1
+  float* post_entropy;                        // [N] hual_al_query's
+  int32_t *n_design, *stop_reason;            // [N]
+};
+
 // the null and N / ld requirements of an AlSpanIn, refused under the entry point's prefix `who`; between the two, in the order the
 // launches have always checked in, the launch's own requirements (`own`: null outputs, nsel, ... - returns 0 or the failure)
 template <class Own>
@@ -130,6 +143,7 @@ int launch_al_label_gain(const AlGainArgs& a, int nsel, hipStream_t s);
 int launch_al_mbr_label(const AlLabelArgs& a, int nsel, hipStream_t s);
 int launch_al_query(const AlQueryArgs& a, hipStream_t s);
 int launch_al_session(const AlSessionArgs& a, int nsel, hipStream_t s);
+int launch_al_design(const AlDesignArgs& a, int nsel, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);
 

@@ -172,6 +172,7 @@ def load():
     lib.hual_al_noisy_tilt.argtypes = [P(hual_al_set), vp, vp, f32, vp, vp, vp, vp]
     lib.hual_al_label_gain_noisy.argtypes = [P(hual_al_set), vp, vp, f32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_al_session.argtypes = [P(hual_al_set), vp, vp, vp, vp, i32, i32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.hual_al_design.argtypes = [P(hual_al_set), vp, vp, vp, i32, i32, vp, f32, f32, vp, vp, vp, vp, vp, vp]
     lib.hual_al_evidence_grid.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_al_ensemble_query.argtypes = [P(hual_al_set), vp, vp, i32, vp] + [vp] * 12 + [vp]
     lib.hual_al_ensemble_label.argtypes = [P(hual_al_set), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -413,10 +414,11 @@ AL_GRID_MAX_TAU = 32        # temperatures per hual_al_evidence_grid launch
 AL_GRID_MAX_EPS = 16        # error rates per launch (csrc/spancalib.h)
 AL_SESSION_MAX_Q = 16           # question slots per sample of hual_al_session
 AL_SESSION_MAX_POINTS = 64      # active points of one sample, the set's and the session's, that hual_al_session holds
+AL_DESIGN_MAX_M = 16            # frames per sample of hual_al_design
 AL_STOP_REASONS = ('budget', 'entropy', 'gain', 'contradictory', 'poisoned', 'overflow')      # HUAL_AL_STOP_*, by value
 
 # The outputs of every span-posterior launch, in the order the C entry point takes them: (name, shape, dtype, fill, optional).
-# shape: extents by name - N, ld, K (passes), Q (question slots), Q1 = Q + 1, AB (grid cells) - or as numbers; fill: what a tensor
+# shape: extents by name - N, ld, K (passes), Q (question slots), Q1 = Q + 1, M (design slots), AB (grid cells) - or as numbers; fill: what a tensor
 # allocated here holds before the launch writes its part (None: left uninitialised, the launch writes all of it); optional: the caller
 # may leave it out (None) - a switch of the wrapper (frames=, marginals=, old_idx=) does so for tensors allocated here.
 _NAN = float('nan')
@@ -446,6 +448,8 @@ _SPAN_OUT = {
     'al_session': (('asked', ('N', 'Q'), 'int32', -1, False), ('answer', ('N', 'Q'), 'int8', -1, False), ('q_asked', ('N', 'Q'), 'float32', -1, False),
                    ('gain', ('N', 'Q'), 'float32', -1, False), ('entropy', ('N', 'Q1'), 'float32', -1, False), ('n_asked', ('N',), 'int32', -1, False),
                    ('stop_reason', ('N',), 'int32', -1, False)),
+    'al_design': (('frames', ('N', 'M'), 'int32', -1, False), ('info', ('N', 'M'), 'float32', -1, False), ('post_entropy', ('N',), 'float32', -1, False),
+                  ('n_design', ('N',), 'int32', -1, False), ('stop_reason', ('N',), 'int32', -1, False)),
 }
 AL_ENS_QUERY_OUT = tuple(name for name, _, _, _, _ in _SPAN_OUT['al_ensemble_query'])
 
@@ -672,4 +676,28 @@ def al_session(aset, s0, e0, tlen, gt, qmax, sel=None, budget=None, stop_entropy
     _span_index('al_session', 'flip', flip, (N,), dev)
     out = _span_out('al_session', out, dev, N=N, Q=qmax, Q1=qmax + 1)
     _launch('hual_al_session', aset, s0, e0, gt, sel, nsel, qmax, budget, float(stop_entropy), float(min_gain), float(eps), flip, *out)
+    return out
+
+
+def al_design(aset, s0, e0, tlen, mmax, sel=None, forced=None, min_gain=0.0, stop_entropy=-1.0, out=None):
+    """the frames to ask TOGETHER about every selected sample of the hual_al_set `aset` (hual_al_design), one launch enqueued on the
+    current stream: a greedy design of up to mmax frames under the span posterior given the answered active points - step m takes the
+    first frame of maximal I(D + t), the entropy of the answer vector of the frames so far and t - for an annotator who answers the
+    frames of a clip at once.  s0 / e0: the deterministic logits f32 [N, ld] on the device; tlen: the set's row lengths on the HOST - a
+    row above AL_QUERY_MAX_T frames is refused here, before the launch, as in al_query; mmax in [1, 16]; sel: device i32 [nsel] sample
+    ids (None: all); forced: device i32 [N, mmax] (None: none) - a row's leading entries >= 0 are the first frames of its design,
+    placed without a stop test (-1 ends them; an entry beyond the clip is ignored); min_gain: bits, >= 0; stop_entropy: bits of
+    expected entropy left at which the design stops, negative = off.
+    -> (frames i32 [N, mmax], info f32 [N, mmax], post_entropy f32 [N], n_design i32 [N], stop_reason i32 [N]; AL_STOP_REASONS names
+    its values): info[n, m] is the information of the first m + 1 frames in bits.  out: such a tuple of contiguous device tensors to
+    write into instead.  Only the rows of selected samples are written: the others keep what they held (-1 in tensors allocated here,
+    the value of an unused slot)."""
+    N, ld, dev = _span_inputs('al_design', aset, s0, e0, tlen)
+    nsel = _span_sel('al_design', sel, N, dev)
+    mmax = int(mmax)
+    if not 1 <= mmax <= AL_DESIGN_MAX_M:
+        raise HualError('al_design: mmax must lie in [1, %d]' % AL_DESIGN_MAX_M)
+    _span_index('al_design', 'forced', forced, (N, mmax), dev)
+    out = _span_out('al_design', out, dev, N=N, M=mmax)
+    _launch('hual_al_design', aset, s0, e0, sel, nsel, mmax, forced, float(min_gain), float(stop_entropy), *out)
     return out

@@ -796,6 +796,46 @@ int hual_al_session(const hual_al_set* set, const float* s0, const float* e0, co
                     int8_t* answer, float* q_asked, float* gain, float* entropy, int32_t* n_asked, int32_t* stop_reason, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Question sets for an annotator who is not in the loop: M frames per clip in one launch (HUAL_ABI_VERSION unchanged: one new symbol,
+ * nothing else moved).  hual_al_session answers each question inside the kernel, so it serves the simulated annotator only; a labelling
+ * tool, a crowd batch or one viewing of a clip takes the frames of a clip TOGETHER.  The answer at frame t is [i <= t <= j], a function
+ * of the span (i, j), so the information a set of frames D = (t_1 .. t_m) carries about the span is the entropy of its answer vector,
+ *   I(D) = -sum over the outcomes o of P(o) log2 P(o),  P(o) = the mass of the spans of A with answer vector o, over Z_A,
+ * with A, Z_A, p_s, p_e of a row exactly hual_al_query's; the expected entropy left after the answers is post_entropy - I(D).  The
+ * positive answers of a span are a contiguous run of the sorted D and every span that holds no frame of D answers alike, so there are at
+ * most m (m + 1) / 2 + 1 outcomes.  hual_al_design builds D greedily: step m takes the first frame t < v of maximal I(D + t).
+ *
+ * Inputs: the set, s0 / e0 f32 [N, ld] and sel / nsel as in hual_al_session (sel NULL: all N samples; rows not listed are left
+ * untouched; an id outside [0, N) writes nothing; a repeated id writes the same values twice); mmax in [1, 16]; forced i32 [N, mmax]
+ * (may be NULL: none): row n's leading entries >= 0 are the first frames of its design, placed in that order without a stop test - how
+ * a hand-made grid or a bisection schedule is scored - and the greedy continues behind them; an entry < 0 ends the prefix; an entry
+ * >= v is ignored, as the family ignores such active points: it takes no slot; a forced frame that repeats, or that the set has already
+ * answered, carries 0 bits and stays in the list.  min_gain in bits, >= 0; stop_entropy in bits (negative: off).
+ *
+ * Per selected sample, with m = the frames placed so far, I = the running float64 information (0 at m = 0):
+ *  1. the row is opened and read by hual_al_query's own code: a poisoned row -> HUAL_AL_STOP_POISONED, a contradictory one ->
+ *     _CONTRADICTORY, nothing placed.  post_entropy f32 [N] is hual_al_query's, bit for bit (-1 on such a row).
+ *  2. m == mmax -> _BUDGET.
+ *  3. every frame's marginal gain g(t) = I(D + t) - I(D).  At m = 0 it is hual_al_query's gain, the float32 h2((float)q(t)), widened; at
+ *     m >= 1 the chain rule, sum over the outcomes o of P(o) h2(q_o(t)) in float64, q_o(t) the inclusion probability of t under the
+ *     posterior restricted to o: t lies inside or outside an outcome (q = 1, 0) or splits its start cell, its end cell or - the
+ *     all-negative outcome - its triangle, each read from float64 sums of p_s / p_e that restart at every negative of the set and at
+ *     every placed frame that carried information (no difference of whole-row prefix sums).  A placed or answered frame has g = 0.
+ *  4. a pending forced frame is placed: I += g(t).  Otherwise, in this order: stop_entropy >= 0 and H_A - I <= stop_entropy (H_A
+ *     post_entropy's float64) -> _ENTROPY; the best g <= min_gain (a gain of 0 always stops) -> _GAIN; else the first frame of
+ *     maximal g is placed.  At m = 0 that frame and gain are hual_al_query's query_point and query_gain.
+ * Outputs, each written for every selected sample: frames i32 [N, mmax] in the order placed; info f32 [N, mmax], info[n][m] = (float) of I
+ * after m + 1 frames, non-decreasing, at most min(m + 1, post_entropy) up to rounding; unused slots hold -1 in both.  n_design i32 [N];
+ * stop_reason i32 [N] (HUAL_AL_STOP_*).  No atomics, a fixed order: two launches give the same bits, and a design fed back as `forced`
+ * returns itself with the same info (the forced frame's gain is read from the row the greedy step maximises).
+ * One workgroup per selected sample; the design and its cell boundaries live in LDS.  Allocates nothing and does not synchronise:
+ * capturable in a hipGraph.  Argument errors (a null pointer other than sel and forced, N < 1, ld outside [2, 1024], nsel < 1 with sel,
+ * mmax outside [1, 16], min_gain < 0 or NaN, a NaN stop_entropy) return HUAL_ERR_INVALID before any HIP call. */
+int hual_al_design(const hual_al_set* set, const float* s0, const float* e0, const int32_t* sel, int nsel, int mmax,
+                   const int32_t* forced, float min_gain, float stop_entropy, int32_t* frames, float* info, float* post_entropy,
+                   int32_t* n_design, int32_t* stop_reason, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Calibrating the span posterior by the evidence of the answers (HUAL_ABI_VERSION unchanged: one new symbol, nothing else moved).  Every
  * launch above takes the softmaxes of s0 / e0 at face value and eps as the caller's number.  With a temperature tau,
  *   L(tau, eps) = sum over the samples n of ln P(the answers of n | softmax(s0[n] / tau), softmax(e0[n] / tau), eps)
