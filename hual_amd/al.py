@@ -518,6 +518,36 @@ def recall_at_k(records, starts, ends, thresholds=(0.3, 0.5, 0.7)):
     return tuple(float(np.mean(best >= t) * 100.0) for t in thresholds)
 
 
+def hit_calibration(prob, hit, bins=10):
+    """reliability of predicted hit probabilities against what happened: prob (floats in [0, 1]; an entry < 0 - no value, as
+    hual_span_hit_prob gives for an invalid slot or a poisoned row - counts out) and hit (truth values of the same shape) ->
+    dict(count int64 [bins], mean_prob, hit_rate float64 [bins] (NaN for an empty bin), ece, brier, n).  The bins are `bins` equal
+    widths on [0, 1]: bin q holds q / bins <= prob < (q + 1) / bins, the last one also prob == 1.  ece is the count-weighted mean over
+    the bins of |hit_rate - mean_prob| (the expected calibration error), brier the mean of (prob - hit)^2; both NaN without entries.
+    Host only, float64."""
+    p = np.asarray(prob, dtype=np.float64).ravel()
+    h = np.asarray(hit).ravel().astype(bool)
+    if p.shape != h.shape:
+        raise ValueError('hit_calibration: prob and hit must have the same number of entries')
+    bins = int(bins)
+    if bins < 1:
+        raise ValueError('hit_calibration: bins >= 1')
+    keep = p >= 0
+    p, h = p[keep], h[keep].astype(np.float64)
+    if p.size and p.max() > 1.0:
+        raise ValueError('hit_calibration: prob must not exceed 1')
+    q = np.minimum((p * bins).astype(np.int64), bins - 1)
+    count = np.bincount(q, minlength=bins).astype(np.int64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean_prob = np.bincount(q, weights=p, minlength=bins) / count
+        hit_rate = np.bincount(q, weights=h, minlength=bins) / count
+    full = count > 0
+    n = int(p.size)
+    ece = float(np.sum(count[full] * np.abs(hit_rate[full] - mean_prob[full])) / n) if n else float('nan')
+    brier = float(np.mean((p - h) ** 2)) if n else float('nan')
+    return dict(count=count, mean_prob=mean_prob, hit_rate=hit_rate, ece=ece, brier=brier, n=n)
+
+
 # ---------------------------------------------------------------- label update -------------------
 def _round_half_even_index(t, duration, vlen):
     """time_to_index_v2 (update_label.py:41-48): python round() of t / duration * (vlen - 1)"""

@@ -156,6 +156,7 @@ def load():
     lib.hual_span_argmax.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
     lib.hual_span_topk.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]
     lib.hual_span_expected_iou.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.hual_span_hit_prob.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.hual_linear_dw.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, u64, vp]
     lib.hual_al_score.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
     lib.hual_al_mc_fold.argtypes = [P(hual_al_bank), vp, vp, vp, vp, i32, i32, i32, vp]
@@ -348,6 +349,91 @@ def span_expected_iou(start_logits, end_logits, video_seq_len, starts, ends, sco
     check(load().hual_span_expected_iou(ptr(s), ptr(e), ptr(vl), B, T, k, ptr(starts), ptr(ends), ptr(score), ptr(out[0]), ptr(out[1]),
                                         1 if reorder else 0, stream_ptr()))
     return out[0], out[1]
+
+
+def hit_thresholds(thresholds):
+    """IoU thresholds as the exact rationals hual_span_hit_prob takes: each a float (through fractions.Fraction(x).limit_denominator(1024);
+    an error when that moves the value by more than 1e-9) or a (num, den) pair -> [(num, den), ...] in lowest terms, 1 <= num <= den <= 1024"""
+    import fractions
+    out = []
+    try:
+        items = list(thresholds)
+    except TypeError:
+        raise HualError('span_hit_prob: thresholds is a sequence of floats or (num, den) pairs')
+    if not 1 <= len(items) <= 4:
+        raise HualError('span_hit_prob: 1 to 4 thresholds, got %d' % len(items))
+    for x in items:
+        if isinstance(x, (tuple, list)):
+            if len(x) != 2 or any(int(y) != y for y in x) or int(x[1]) < 1:
+                raise HualError('span_hit_prob: a threshold pair is (num, den) in integers, got %r' % (x,))
+            f = fractions.Fraction(int(x[0]), int(x[1]))
+        else:
+            f = fractions.Fraction(float(x)).limit_denominator(1024)
+            if abs(float(f) - float(x)) > 1e-9:
+                raise HualError('span_hit_prob: threshold %r is no fraction with a denominator <= 1024 (nearest: %s)' % (x, f))
+        if not (1 <= f.numerator <= f.denominator <= 1024):
+            raise HualError('span_hit_prob: a threshold lies in (0, 1] with a denominator <= 1024, got %r' % (x,))
+        out.append((f.numerator, f.denominator))
+    return out
+
+
+def span_hit_prob(start_logits, end_logits, video_seq_len, thresholds=(0.3, 0.5, 0.7), starts=None, ends=None, score=None, reorder_by=None,
+                  best=False, out=None):
+    """hit probability P(IoU(span, truth) >= m) under the span distribution of start_logits / end_logits f32 [B,T] and video_seq_len [B]
+    for M <= 4 IoU thresholds (hit_thresholds), enqueued on the current stream (hual_span_hit_prob) -> (hit_prob, best):
+    hit_prob float32 [B,k,M] of the proposals starts / ends (int64 [B,k] on the device, k <= 16; -1 = no proposal), or None without
+    proposals; best = (best_start int64 [B,M], best_end int64 [B,M], best_prob float32 [B,M]), each threshold's span of maximal hit
+    probability over the whole triangle, with best=True, else None.  Invalid slots, empty clips and rows with a NaN logit give -1.
+    reorder_by=m sorts every row's slots by column m, best first, stable: starts, ends and score (float32 [B,k] or None) are permuted in
+    place along with all columns of the result.  out: (hit_prob or None, (best_start, best_end, best_prob) or None) contiguous device
+    tensors of those shapes to write into instead."""
+    import torch
+    who = 'span_hit_prob'
+    if start_logits.dtype != torch.float32 or end_logits.dtype != torch.float32:
+        raise HualError(who + ': float32 logits required')
+    if start_logits.dim() != 2 or end_logits.shape != start_logits.shape:
+        raise HualError(who + ': start / end logits must both be [B,T]')
+    thr = hit_thresholds(thresholds)
+    M = len(thr)
+    s, e = start_logits.contiguous(), end_logits.contiguous()
+    B, T = s.shape
+    vl = video_seq_len.to(device=s.device, dtype=torch.int32).contiguous()
+    if vl.numel() != B:
+        raise HualError(who + ': video_seq_len must hold B = %d lengths' % B)
+    if (starts is None) != (ends is None):
+        raise HualError(who + ': starts and ends are given together')
+    k = 0
+    if starts is not None:
+        if starts.dim() != 2 or starts.shape[0] != B:
+            raise HualError(who + ': starts / ends must be [B,k] with B = %d' % B)
+        k = int(starts.shape[1])
+        # (no .contiguous() here: reorder_by writes them in place, and a copy would take the permutation with it)
+        for x, dt, what in ((starts, torch.int64, 'starts'), (ends, torch.int64, 'ends'), (score, torch.float32, 'score')):
+            if x is not None and (x.dtype != dt or tuple(x.shape) != (B, k) or not x.is_contiguous() or x.device != s.device):
+                raise HualError(who + ': %s must be a contiguous [B,k] %s tensor on the logits\' device' % (what, str(dt).replace('torch.', '')))
+    elif score is not None or reorder_by is not None:
+        raise HualError(who + ': score and reorder_by need proposals (starts, ends)')
+    if not k and not best:
+        raise HualError(who + ': nothing to do (no proposals and best=False)')
+    rb = -1 if reorder_by is None else int(reorder_by)
+    if reorder_by is not None and not 0 <= rb < M:
+        raise HualError(who + ': reorder_by is None or a threshold\'s column, 0 <= reorder_by < %d' % M)
+    if out is None:
+        out = (torch.empty(B, k, M, dtype=torch.float32, device=s.device) if k else None,
+               (torch.empty(B, M, dtype=torch.int64, device=s.device), torch.empty(B, M, dtype=torch.int64, device=s.device),
+                torch.empty(B, M, dtype=torch.float32, device=s.device)) if best else None)
+    else:
+        if len(out) != 2 or (out[0] is None) != (k == 0) or (out[1] is None) != (not best) or (best and len(out[1]) != 3):
+            raise HualError(who + ': out is (hit_prob [B,k,M] or None, (best_start, best_end, best_prob) [B,M] or None)')
+        for o, dt, shape in ((out[0], torch.float32, (B, k, M)),) + (tuple(zip(out[1], (torch.int64, torch.int64, torch.float32), ((B, M),) * 3))
+                                                                     if best else ()):
+            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != s.device):
+                raise HualError(who + ': out tensors must be contiguous float32 [B,k,M] and int64, int64, float32 [B,M] on the logits\' device')
+    bst = out[1] if best else (None, None, None)
+    cthr = (ctypes.c_int32 * (2 * M))(*[x for nd in thr for x in nd])
+    check(load().hual_span_hit_prob(ptr(s), ptr(e), ptr(vl), B, T, cthr, M, k, ptr(starts), ptr(ends), ptr(score), ptr(out[0]), rb,
+                                    ptr(bst[0]), ptr(bst[1]), ptr(bst[2]), stream_ptr()))
+    return out[0], (tuple(out[1]) if best else None)
 
 
 def al_score(aset, s0, e0, coff_uncert, out, pair=None, bank=None, info=None, K=2, stat='range', uncert_model=None):

@@ -159,14 +159,18 @@ class Runner:
         return al.iou_metrics(ious)
 
     # ------------------------------------------------------------------ R@k evaluation (top-k proposals after temporal NMS)
-    def evaluate(self, dataset=None, k=5, nms_iou=0.5, max_len=0, return_proposals=False, weights=None, rerank=None):
-        """weights: 'ema' (the default with train.ema_decay) or 'raw'; everything else: _evaluate"""
-        if rerank not in (None, 'expected_iou'):
-            raise ValueError("rerank: None or 'expected_iou'")
-        with self._weights(weights):
-            return self._evaluate(dataset, k, nms_iou, max_len, return_proposals, rerank)
+    BAYES_IOUS = (0.3, 0.5, 0.7)      # the thresholds of the reported R@1 (al.iou_metrics): one Bayes span each
 
-    def _evaluate(self, dataset, k, nms_iou, max_len, return_proposals, rerank=None):
+    def evaluate(self, dataset=None, k=5, nms_iou=0.5, max_len=0, return_proposals=False, weights=None, rerank=None, hit_iou=0.7,
+                 bayes_spans=False):
+        """weights: 'ema' (the default with train.ema_decay) or 'raw'; everything else: _evaluate"""
+        if rerank not in (None, 'expected_iou', 'hit_prob'):
+            raise ValueError("rerank: None, 'expected_iou' or 'hit_prob'")
+        thr = lib.hit_thresholds((hit_iou,)) if rerank == 'hit_prob' else None      # (raises on a threshold the kernel cannot take)
+        with self._weights(weights):
+            return self._evaluate(dataset, k, nms_iou, max_len, return_proposals, rerank, hit_iou, thr, bayes_spans)
+
+    def _evaluate(self, dataset, k, nms_iou, max_len, return_proposals, rerank=None, hit_iou=0.7, hit_thr=None, bayes_spans=False):
         """R1 and R<k> at IoU 0.3 / 0.5 / 0.7 and mIoU (percent) of the k best spans per clip after greedy temporal NMS
         (hual_span_topk).  Batches and ranks as test_epoch; the proposals of all batches collect on the device and come back in one
         transfer.  R1 and mIoU are those of the first proposal, which is the span test_epoch scores.  return_proposals: also a list
@@ -176,7 +180,16 @@ class Runner:
         minimum-Bayes-risk choice among them.  R1 and mIoU are then those of the re-ranked first proposal (R<k> does not depend on the
         order); the result gains 'conf', the mean expected IoU of the first proposal, and 'span_entropy', the mean entropy of the span
         distribution in bits (clips without a value - a poisoned row - count out), and the proposal tuples a fourth element, the
-        expected IoU."""
+        expected IoU.
+        rerank='hit_prob': the same with the proposals' hit probability at IoU >= hit_iou, P(IoU(span, truth) >= hit_iou) under the
+        clip's span distribution (hual_span_hit_prob, one more launch per batch, reordering by that threshold's column) - among the
+        proposals the choice that maximises the chance of an R1@hit_iou hit.  The result gains 'hit_conf', the mean hit probability of
+        the first proposal, and 'ece@<hit_iou>' / 'brier@<hit_iou>', the expected calibration error and the Brier score of that
+        probability against the first proposal's actual hit (al.hit_calibration of it and al.topk_ious >= hit_iou); the proposal
+        tuples gain the hit probability as a fourth element.
+        bayes_spans=True (with any rerank): one more launch per batch finds, for each of IoU 0.3 / 0.5 / 0.7, the span of maximal hit
+        probability over ALL spans of the clip, not only the proposals; the result gains 'R1_bayes@0.3' / '@0.5' / '@0.7', the R@1 of
+        each threshold's own span at that threshold (through al.ious_of_spans), and 'bayes_conf@...', their mean hit probability."""
         ds = dataset or self.test_set
         N, bs, k = len(ds), self.batch_size, int(k)
         mine = [(lo, min(N, lo + bs)) for b, lo in enumerate(range(0, N, bs)) if b % self.world == self.rank]
@@ -188,7 +201,13 @@ class Runner:
         en = buf[8 * n * k:16 * n * k].view(torch.int64).view(n, k)
         sc = buf[16 * n * k:].view(torch.float32).view(n, k)
         # re-ranking: expected IoU [n,k] | span entropy [n] (float32), one more buffer
-        cbuf = torch.empty(n * k + n, dtype=torch.float32, device=dev) if rerank else None
+        cbuf = torch.empty(n * k + n, dtype=torch.float32, device=dev) if rerank == 'expected_iou' else None
+        # hit probability [n,k,1] of the one threshold; the Bayes spans: starts | ends (int64) | probabilities (float32), each [n,3]
+        hbuf = torch.empty(n, k, 1, dtype=torch.float32, device=dev) if rerank == 'hit_prob' else None
+        bbuf = torch.empty(n * 3 * 20, dtype=torch.uint8, device=dev) if bayes_spans else None
+        if bayes_spans:
+            bst, ben = bbuf[:24 * n].view(torch.int64).view(n, 3), bbuf[24 * n:48 * n].view(torch.int64).view(n, 3)
+            bpr = bbuf[48 * n:].view(torch.float32).view(n, 3)
         pos = 0
         for lo, hi in mine:
             sel = np.arange(lo, hi)
@@ -196,18 +215,30 @@ class Runner:
             o = self.model.forward(f['video'], f['video_seq_len'], f['word_ids'], f['char_ids'], drop_rate=0.0)
             lib.span_topk(o['start_logits'], o['end_logits'], f['video_seq_len'], k, max_len=max_len, nms_iou=nms_iou,
                           out=(st[pos:pos + hi - lo], en[pos:pos + hi - lo], sc[pos:pos + hi - lo]))
-            if rerank:
+            if rerank == 'expected_iou':
                 lib.span_expected_iou(o['start_logits'], o['end_logits'], f['video_seq_len'], st[pos:pos + hi - lo], en[pos:pos + hi - lo],
                                       score=sc[pos:pos + hi - lo], reorder=True,
                                       out=(cbuf[:n * k].view(n, k)[pos:pos + hi - lo], cbuf[n * k:][pos:pos + hi - lo]))
+            if rerank == 'hit_prob':
+                lib.span_hit_prob(o['start_logits'], o['end_logits'], f['video_seq_len'], hit_thr, st[pos:pos + hi - lo], en[pos:pos + hi - lo],
+                                  score=sc[pos:pos + hi - lo], reorder_by=0, out=(hbuf[pos:pos + hi - lo], None))
+            if bayes_spans:
+                lib.span_hit_prob(o['start_logits'], o['end_logits'], f['video_seq_len'], self.BAYES_IOUS, best=True,
+                                  out=(None, (bst[pos:pos + hi - lo], ben[pos:pos + hi - lo], bpr[pos:pos + hi - lo])))
             pos += hi - lo
         h = buf.cpu().numpy()
         ids = np.concatenate([np.arange(lo, hi) for lo, hi in mine]) if mine else np.zeros(0, dtype=np.int64)
         part = (ids, h[:8 * n * k].view(np.int64).reshape(n, k), h[8 * n * k:16 * n * k].view(np.int64).reshape(n, k),
                 h[16 * n * k:].view(np.float32).reshape(n, k))
-        if rerank:
+        if rerank == 'expected_iou':
             hc = cbuf.cpu().numpy()
             part += (hc[:n * k].reshape(n, k), hc[n * k:])
+        if rerank == 'hit_prob':
+            part += (hbuf.cpu().numpy().reshape(n, k),)
+        if bayes_spans:
+            hb = bbuf.cpu().numpy()
+            part += (hb[:24 * n].view(np.int64).reshape(n, 3), hb[24 * n:48 * n].view(np.int64).reshape(n, 3),
+                     hb[48 * n:].view(np.float32).reshape(n, 3))
         if self.world > 1:
             parts = hdist.gather_objects(part)
             if self.rank == 0:
@@ -222,12 +253,29 @@ class Runner:
                'mIoU': r1[3]}
         self.log.info('EVAL (k={}, nms_iou={}):\tR1 {:.2f}\t{:.2f}\t{:.2f}\tR{} {:.2f}\t{:.2f}\t{:.2f}\tmIoU {:.2f}'.format(
             k, nms_iou, r1[0], r1[1], r1[2], k, rk[0], rk[1], rk[2], r1[3]))
-        if rerank:
+        if rerank == 'expected_iou':
             EI, ENT = part[4], part[5]
             c0, ent = EI[:, 0][EI[:, 0] >= 0], ENT[ENT >= 0]
             res['conf'] = float(np.mean(c0, dtype=np.float64)) if c0.size else float('nan')
             res['span_entropy'] = float(np.mean(ent, dtype=np.float64)) if ent.size else float('nan')
             self.log.info('EVAL re-ranked by expected IoU:\tconf {:.4f}\tspan entropy {:.3f} bits'.format(res['conf'], res['span_entropy']))
+        if rerank == 'hit_prob':
+            EI = part[4]                                           # (the proposals' fourth element below)
+            h0 = EI[:, 0][EI[:, 0] >= 0]
+            cal = al.hit_calibration(EI[:, 0], ious[:, 0] >= hit_iou)
+            res['hit_conf'] = float(np.mean(h0, dtype=np.float64)) if h0.size else float('nan')
+            res['ece@%g' % hit_iou], res['brier@%g' % hit_iou] = cal['ece'], cal['brier']
+            self.log.info('EVAL re-ranked by hit probability at IoU {:g}:\thit conf {:.4f}\tECE {:.4f}\tBrier {:.4f}'.format(
+                hit_iou, res['hit_conf'], cal['ece'], cal['brier']))
+        if bayes_spans:
+            BS, BE, BP = part[-3:]
+            for c, m in enumerate(self.BAYES_IOUS):
+                hit = al.topk_ious(recs, BS[:, c], BE[:, c])[:, 0] >= m      # (a clip without a span - a poisoned row - is a miss)
+                bp = BP[:, c][BP[:, c] >= 0]
+                res['R1_bayes@%g' % m] = float(np.mean(hit) * 100.0)
+                res['bayes_conf@%g' % m] = float(np.mean(bp, dtype=np.float64)) if bp.size else float('nan')
+            self.log.info('EVAL Bayes spans (maximal hit probability per threshold):\tR1 ' + '\t'.join(
+                '{:.2f}'.format(res['R1_bayes@%g' % m]) for m in self.BAYES_IOUS))
         if not return_proposals:
             return res
         props = [None] * N

@@ -413,6 +413,38 @@ int hual_span_expected_iou(const float* start_logits, const float* end_logits, c
                            int64_t* start_index, int64_t* end_index, float* score, float* expected_iou, float* span_entropy,
                            int reorder, void* stream);
 
+/* hit probability of spans under the clip's own span distribution: the chance that a span counts as a hit at IoU >= m, the confidence in
+ * the metric that selects a checkpoint (R@1 at IoU 0.3 / 0.5 / 0.7), for k proposals per clip and - per threshold - for the span of the
+ * whole triangle that maximises it, the Bayes decision for R@1 at that threshold (ABI 9 unchanged, a new symbol).  v, p_s, p_e as
+ * hual_span_expected_iou (bit for bit those of hual_span_topk); the weights are w(i,j) = (double)p_s[i] * (double)p_e[j] for 0 <= i <= j
+ * < v as hual_al_query takes them, Z their sum.  1 <= T <= 256, 0 <= k <= 16, 1 <= M <= 4.
+ *  - thresholds: HOST int32 [M][2] = (num, den), exact rationals with 1 <= num <= den <= 1024, read before the launch and passed to the
+ *    kernel by value.  A span (i,j) hits the candidate (a,b) iff den * inter >= num * union in integers, inter = max(0, min(b,j) + 1 -
+ *    max(a,i)), union = (b - a + 1) + (j - i + 1) - inter on the half-open frame intervals of hual_span_topk's NMS: no float takes part
+ *    in the hit test.  (al.iou_metrics compares a float32 ratio of float32 times with the threshold; it can differ from this rule only
+ *    where the IoU equals the threshold exactly.)
+ *  - hit_prob [B, k, M] (float; k >= 1): for the candidate (a, b) = (start_index, end_index)[b][slot] the sum of w over the spans that hit
+ *    it, divided by Z, clamped to [0, 1].  Arithmetic: float64 throughout; the sum over the hitting ends of one start is taken as a
+ *    DIFFERENCE of float64 prefix sums of p_e (an absolute error of a few 2^-53, far below the float32 result), the sums over starts and
+ *    Z in a fixed order.  Columns do not increase with the threshold up to that rounding.  A slot is invalid when an index is negative,
+ *    a > b or b >= v: -1.0f in all M columns (not an error).  k == 0 skips the proposals; start_index, end_index, score and hit_prob may
+ *    then be NULL.
+ *  - reorder_by = m in [0, M): the row's slots are sorted by column m of hit_prob descending, stable (equal values and the invalid slots,
+ *    last, keep their incoming order); start_index, end_index, score (when not NULL) and all M columns of hit_prob are permuted alike, in
+ *    place - hual_span_expected_iou's reorder.  reorder_by = -1: start_index / end_index / score are only read.
+ *  - best_start, best_end (int64), best_prob (float), [B, M] each, all three or none: for threshold m the span of the triangle with the
+ *    largest hit mass in the arithmetic above, among equal masses the first in row-major order (smallest a, then smallest b), and its
+ *    hit probability.
+ *  - an empty clip (v < 1), a NaN logit at t < v or a Z that is not a positive finite number (hual_span_expected_iou's rule): every
+ *    hit_prob of the row is -1.0f, best_* are -1, -1, -1.0f and the row is never reordered.  v == 1: every valid candidate and every
+ *    Bayes span is (0, 0) with probability exactly 1.0f.  Logits at t >= v are not read.
+ * Allocates nothing and does not synchronise: capturable in a hipGraph.  Argument errors (a null pointer other than score, the best_*
+ * and - with k == 0 - the proposal arrays; B < 1; T, k, M or a threshold out of range; only some of best_*; reorder_by outside [-1, M) or
+ * set with k == 0; k == 0 without best_*) return HUAL_ERR_INVALID before any HIP call. */
+int hual_span_hit_prob(const float* start_logits, const float* end_logits, const int32_t* video_seq_len, int B, int T,
+                       const int32_t* thresholds, int M, int k, int64_t* start_index, int64_t* end_index, float* score, float* hit_prob,
+                       int reorder_by, int64_t* best_start, int64_t* best_end, float* best_prob, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Device-side batch assembly: TrainLoader.process_batch / TestLoader.process_batch
  * (/root/reference/utils/data_loader.py:30-98,145-164) from a training set that stays resident in HBM.
