@@ -32,19 +32,17 @@ __global__ __launch_bounds__(SPAN_THREADS) void al_evidence_grid_kernel(AlGridAr
   if (n < 0 || n >= a.in.set.N) return;     // (uniform) an id outside the set writes nothing
   const int AB = a.A * a.B;
   double* cells = a.table + (size_t)n * AB;
-  // the row as open_span_row (spanpost.h) opens it, up to the probabilities: those are per temperature
-  const int T = a.in.set.tlen[n];
-  const size_t row = (size_t)n * a.in.set.ld;
-  const bool fits = T >= 1 && T <= 256 && T <= a.in.set.ld;
-  const int v = fits ? span_clip_len(a.in.set.vlen[n], T) : 0;
-  if (v == 0 || span_row_poisoned(a.in.s0, a.in.e0, row, v)) {      // (uniform) x * (1 / tau) is a NaN exactly where x is
+  SpanRow r;
+  open_span_row_header(a.in, n, r);         // (the probabilities are per temperature, below)
+  if (r.status != SPAN_LIVE) {              // (uniform) x * (1 / tau) is a NaN exactly where x is
     for (int c = t; c < AB; c += SPAN_THREADS) cells[c] = NAN;
     if (t == 0) a.status[n] = 0;
     return;
   }
-  const int ap0 = a.in.set.ap_off[n], napn = a.in.set.ap_off[n + 1] - ap0;
-  const int32_t* aidx = a.in.set.ap_idx + ap0;
-  const int8_t* apos = a.in.set.ap_pos + ap0;
+  const int T = r.T, v = r.v, napn = r.napn;
+  const size_t row = r.row;
+  const int32_t* aidx = r.aidx;
+  const int8_t* apos = r.apos;
   int G = 0, npos = 0, nneg = 0;            // (npos / nneg uniform: every thread walks the whole list)
   for (int k = 0; k < napn; ++k) {
     const int f = aidx[k];
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(SPAN_THREADS) void al_evidence_grid_kernel(AlGridAr
       zf += __shfl_xor(zf, off);
     }
     double ev = NAN;                        // hual_al_noisy_tilt's rule: every weight underflowed, or an infinite logit made them NaN
-    if (zf > 0.0 && zf < INFINITY) ev = npos + nneg == 0 ? 0.0 : base + (double)tk * lnr + log(tm) - log(zf);
+    if (span_mass_live(zf)) ev = npos + nneg == 0 ? 0.0 : base + (double)tk * lnr + log(tm) - log(zf);
     if (lane == 0) cells[ia * a.B + w] = ev;
     finite = finite && __builtin_isfinite(ev);
   }

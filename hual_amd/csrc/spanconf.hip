@@ -10,26 +10,11 @@
 // Latency bound: at most 2 KB of logits and 20 * k bytes of candidates in, a few hundred bytes out per clip.
 #include "common.h"
 #include "prof.h"
-#include "spanprob.h"
+#include "spanclip.h"
 
 using namespace hual;
 
 namespace {
-
-constexpr int SC_MAXK = 16;
-
-// first flat index of row i of the triangle i <= j < v (row i holds v - i spans)
-__device__ __forceinline__ int sc_row_off(int i, int v) { return i * v - (i * (i - 1)) / 2; }
-
-// (i, j) of flat index c0 (0 <= c0 < v (v + 1) / 2)
-__device__ __forceinline__ void sc_locate(int c0, int v, int& i, int& j) {
-  int lo = 0, hi = v - 1;      // the largest i with sc_row_off(i) <= c0
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (sc_row_off(mid, v) <= c0) lo = mid; else hi = mid - 1;
-  }
-  i = lo; j = lo + (c0 - sc_row_off(lo, v));
-}
 
 __global__ __launch_bounds__(SPAN_THREADS) void span_expected_iou_kernel(const float* __restrict__ zs_, const float* __restrict__ ze_,
                                                                          const int32_t* __restrict__ vlen_, int T, int k,
@@ -39,32 +24,23 @@ __global__ __launch_bounds__(SPAN_THREADS) void span_expected_iou_kernel(const f
   __shared__ float ps[256], pe[256], ls[256], le[256];
   __shared__ float smf[2 * SPAN_WAVES];
   __shared__ double smd[2 * SPAN_WAVES];
-  __shared__ double red[SPAN_WAVES][SC_MAXK + 2];
-  __shared__ double tot[SC_MAXK + 2];
-  __shared__ long long sa[SC_MAXK], sb[SC_MAXK];      // the incoming slots as given (an invalid one is carried along unchanged)
-  __shared__ float ssc[SC_MAXK], val[SC_MAXK];
-  __shared__ int ca[SC_MAXK], cb[SC_MAXK];            // the slot's span, or ca = -1 for an invalid slot
+  __shared__ double red[SPAN_WAVES][SPAN_MAXK + 2];
+  __shared__ double tot[SPAN_MAXK + 2];
+  __shared__ SpanSlots slots;
+  __shared__ float val[SPAN_MAXK];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int v = span_clip_len(vlen_[b], T);
-  const size_t row = (size_t)b * T, slot = (size_t)b * k + t;
-  if (t < k) {
-    const long long a = start_index[slot], e = end_index[slot];
-    const bool ok = a >= 0 && a <= e && e < v;
-    sa[t] = a; sb[t] = e;
-    ssc[t] = score ? score[slot] : 0.f;
-    ca[t] = ok ? (int)a : -1; cb[t] = ok ? (int)e : -1;
-    val[t] = -1.0f;
-  }
-  const int nanlogit = span_row_poisoned(zs_, ze_, row, v);      // (its barrier also publishes the slots above)
+  if (t < k) val[t] = -1.0f;
+  const SpanClip clip = open_span_clip(zs_, ze_, vlen_, T, ps, pe, smf, smd,
+                                       [&](int v) { load_slots(slots, b, k, v, start_index, end_index, score); });
+  const int v = clip.v, *ca = slots.ca, *cb = slots.cb;
   bool live = false;
-  if (v > 0 && !nanlogit) {
-    span_probabilities(zs_, ze_, row, T, v, ps, pe, smf, smd);
+  if (clip.open) {
     if (t < v) { ls[t] = log2f(ps[t]); le[t] = log2f(pe[t]); }
     __syncthreads();
-    const int n = sc_row_off(v, v);
+    const int n = tri_row_off(v, v);
     const int c0 = t * n / SPAN_THREADS, c1 = (t + 1) * n / SPAN_THREADS;
     int i0 = 0, j0 = 0;
-    if (c0 < c1) sc_locate(c0, v, i0, j0);
+    if (c0 < c1) tri_entry(c0, v, i0, j0);
     // ---- Z and the entropy sum
     double z = 0.0, hs = 0.0;
     {
@@ -105,7 +81,7 @@ __global__ __launch_bounds__(SPAN_THREADS) void span_expected_iou_kernel(const f
     }
     __syncthreads();
     const double Z = tot[k];
-    live = Z > 0.0 && Z < INFINITY;      // (uniform) every weight underflowed, or an Inf logit made them NaN: as a poisoned row
+    live = span_mass_live(Z);      // (uniform)
     if (live) {
       if (t < k && ca[t] >= 0) val[t] = (float)(tot[t] / Z);
       if (t == 0 && span_entropy) {
@@ -118,13 +94,9 @@ __global__ __launch_bounds__(SPAN_THREADS) void span_expected_iou_kernel(const f
   __syncthreads();
   if (t < k) {
     int pos = t;
-    if (reorder && live) {      // stable, descending: the slots that go before this one (invalid slots hold -1, below every value)
-      const float mine = val[t];
-      pos = 0;
-      for (int q = 0; q < k; ++q) pos += (val[q] > mine || (val[q] == mine && q < t)) ? 1 : 0;
-      const size_t o = (size_t)b * k + pos;
-      start_index[o] = sa[t]; end_index[o] = sb[t];      // (every slot was read into LDS before the first barrier)
-      if (score) score[o] = ssc[t];
+    if (reorder && live) {
+      pos = slot_rank(k, t, [&](int q) { return val[q]; });
+      store_slot(slots, t, b, k, pos, start_index, end_index, score);
     }
     expected_iou[(size_t)b * k + pos] = val[t];
   }
@@ -139,7 +111,7 @@ extern "C" int hual_span_expected_iou(const float* start_logits, const float* en
                "hual_span_expected_iou: null pointer");
   HUAL_REQUIRE(B >= 1, "hual_span_expected_iou: B >= 1");
   HUAL_REQUIRE(T >= 1 && T <= 256, "hual_span_expected_iou: 1 <= T <= 256");
-  HUAL_REQUIRE(k >= 1 && k <= SC_MAXK, "hual_span_expected_iou: 1 <= k <= 16");
+  HUAL_REQUIRE(k >= 1 && k <= SPAN_MAXK, "hual_span_expected_iou: 1 <= k <= 16");
   const double bytes = 8.0 * B * T + 8.0 * B + (reorder ? 44.0 : 20.0) * B * k;
   HUAL_LAUNCH(0.0, bytes, span_expected_iou_kernel, dim3(B), dim3(SPAN_THREADS), 0, (hipStream_t)stream, start_logits, end_logits,
               video_seq_len, T, k, start_index, end_index, score, expected_iou, span_entropy, reorder);

@@ -19,29 +19,16 @@
 // the longest clip's lowest threshold on its one CU, bound by the dependent LDS reads.
 #include "common.h"
 #include "prof.h"
-#include "spanprob.h"
+#include "spanclip.h"
 
 using namespace hual;
 
 namespace {
 
-constexpr int SH_MAXK = 16, SH_MAXM = 4, SH_MAXDEN = 1024;
+constexpr int SH_MAXM = 4, SH_MAXDEN = 1024;
 constexpr int SH_NONE = 0x7fffffff;      // key of "no candidate" (mass -1: below every real mass, which is >= 0)
 
 struct ShThresholds { int num[SH_MAXM], den[SH_MAXM]; };      // by value: read on the host before the launch
-
-// first flat index of row r of a triangle whose row r holds v - r entries, 0 <= r < v
-__device__ __forceinline__ int sh_row_off(int r, int v) { return r * v - (r * (r - 1)) / 2; }
-
-// (r, x) of flat index c (0 <= c < v (v + 1) / 2): row r, and r <= x < v counting the row's entries from r
-__device__ __forceinline__ void sh_locate(int c, int v, int& r, int& x) {
-  int lo = 0, hi = v - 1;      // the largest r with sh_row_off(r) <= c
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (sh_row_off(mid, v) <= c) lo = mid; else hi = mid - 1;
-  }
-  r = lo; x = lo + (c - sh_row_off(lo, v));
-}
 
 // The starts and ends that hit the candidate (a, b), 0 <= a <= b < v, at threshold num / den: den * inter >= num * union in integers,
 // inter and union of the half-open frame intervals.  num >= 1 asks inter >= 1, so i <= b and j >= max(a, i), and the union is one
@@ -81,33 +68,27 @@ __global__ __launch_bounds__(SPAN_THREADS) void span_hit_prob_kernel(const float
   __shared__ float smf[2 * SPAN_WAVES];
   __shared__ double smd[2 * SPAN_WAVES];
   __shared__ int ce[SH_MAXM][257], fl[SH_MAXM][257];
-  __shared__ long long sa[SH_MAXK], sb[SH_MAXK];             // the incoming slots as given (an invalid one is carried along unchanged)
-  __shared__ float ssc[SH_MAXK], val[SH_MAXK][SH_MAXM];
-  __shared__ int ca[SH_MAXK], cb[SH_MAXK];                   // the slot's span, or ca = -1 for an invalid slot
+  __shared__ SpanSlots slots;
+  __shared__ float val[SPAN_MAXK][SH_MAXM];
   __shared__ double wbv[SPAN_WAVES];
   __shared__ int wbk[SPAN_WAVES];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int v = span_clip_len(vlen_[b], T);
-  const size_t row = (size_t)b * T, slot = (size_t)b * k + t;
   const bool proposals = k > 0 && blockIdx.y == 0;           // (uniform)
-  if (proposals && t < k) {
-    const long long a = start_index[slot], e = end_index[slot];
-    const bool ok = a >= 0 && a <= e && e < v;
-    sa[t] = a; sb[t] = e;
-    ssc[t] = score ? score[slot] : 0.f;
-    ca[t] = ok ? (int)a : -1; cb[t] = ok ? (int)e : -1;
-    for (int m = 0; m < M; ++m) val[t][m] = -1.0f;
-  }
-  for (int x = t; x < M * 257; x += SPAN_THREADS) {          // the two division tables of every threshold (entry 0 is never read)
-    const int m = x / 257, n = x - m * 257;
-    ce[m][n] = (thr.num[m] * n + thr.den[m] - 1) / thr.den[m];
-    fl[m][n] = min(256, (thr.den[m] * n) / thr.num[m]);
-  }
-  const int nanlogit = span_row_poisoned(zs_, ze_, row, v);      // (its barrier also publishes the slots and the tables above)
+  const SpanClip clip = open_span_clip(zs_, ze_, vlen_, T, ps, pe, smf, smd, [&](int v) {
+    if (proposals) {
+      load_slots(slots, b, k, v, start_index, end_index, score);
+      if (t < k) for (int m = 0; m < M; ++m) val[t][m] = -1.0f;
+    }
+    for (int x = t; x < M * 257; x += SPAN_THREADS) {        // the two division tables of every threshold (entry 0 is never read)
+      const int m = x / 257, n = x - m * 257;
+      ce[m][n] = (thr.num[m] * n + thr.den[m] - 1) / thr.den[m];
+      fl[m][n] = min(256, (thr.den[m] * n) / thr.num[m]);
+    }
+  });
+  const int v = clip.v, *ca = slots.ca, *cb = slots.cb;
   bool live = false;
   double Z = 0.0;
-  if (v > 0 && !nanlogit) {
-    span_probabilities(zs_, ze_, row, T, v, ps, pe, smf, smd);
+  if (clip.open) {
     if (t <= v) {      // the prefix sums, each one serial sum in ascending order (all threads read the same p_e: a broadcast)
       double s = 0.0;
       for (int j = 0; j < t; ++j) s += (double)pe[j];
@@ -116,7 +97,7 @@ __global__ __launch_bounds__(SPAN_THREADS) void span_hit_prob_kernel(const float
     __syncthreads();
     Z = t < v ? (double)ps[t] * (E[v] - E[t]) : 0.0;
     Z = block_reduce<BlockSumD, SPAN_WAVES>(Z, smd);
-    live = Z > 0.0 && Z < INFINITY;      // (uniform) every weight underflowed, or an Inf logit made them NaN: as a poisoned row
+    live = span_mass_live(Z);      // (uniform)
   }
   // ---- the proposals: one wave per (slot, threshold) pair
   if (proposals) {
@@ -132,13 +113,9 @@ __global__ __launch_bounds__(SPAN_THREADS) void span_hit_prob_kernel(const float
     __syncthreads();
     if (t < k) {
       int pos = t;
-      if (reorder_by >= 0 && live) {      // stable, descending: the slots that go before this one (invalid slots hold -1, below every value)
-        const float mine = val[t][reorder_by];
-        pos = 0;
-        for (int q = 0; q < k; ++q) pos += (val[q][reorder_by] > mine || (val[q][reorder_by] == mine && q < t)) ? 1 : 0;
-        const size_t o = (size_t)b * k + pos;
-        start_index[o] = sa[t]; end_index[o] = sb[t];      // (every slot was read into LDS before the first barrier)
-        if (score) score[o] = ssc[t];
+      if (reorder_by >= 0 && live) {
+        pos = slot_rank(k, t, [&](int q) { return val[q][reorder_by]; });
+        store_slot(slots, t, b, k, pos, start_index, end_index, score);
       }
       for (int m = 0; m < M; ++m) hit_prob[((size_t)b * k + pos) * M + m] = val[t][m];
     }
@@ -148,10 +125,10 @@ __global__ __launch_bounds__(SPAN_THREADS) void span_hit_prob_kernel(const float
     const int m = blockIdx.y;
     double bv = -1.0; int bk = SH_NONE;
     if (live) {
-      const int n = sh_row_off(v, v);
+      const int n = tri_row_off(v, v);
       for (int c = t; c < n; c += SPAN_THREADS) {      // by length, then by end: diagonal r holds the v - r spans of r + 1 frames
         int r, e;
-        sh_locate(c, v, r, e);
+        tri_entry(c, v, r, e);
         const int a = e - r, key = (a << 8) | e;
         const double mass = sh_mass(a, e, v, ps, E, ce[m], fl[m], 0, 1);
         if (FirstIndexMax()(mass, key, bv, bk)) { bv = mass; bk = key; }      // (the key a * 256 + b: first in row-major order)
@@ -179,7 +156,7 @@ extern "C" int hual_span_hit_prob(const float* start_logits, const float* end_lo
   HUAL_REQUIRE(start_logits && end_logits && video_seq_len && thresholds, "hual_span_hit_prob: null pointer");
   HUAL_REQUIRE(B >= 1, "hual_span_hit_prob: B >= 1");
   HUAL_REQUIRE(T >= 1 && T <= 256, "hual_span_hit_prob: 1 <= T <= 256");
-  HUAL_REQUIRE(k >= 0 && k <= SH_MAXK, "hual_span_hit_prob: 0 <= k <= 16");
+  HUAL_REQUIRE(k >= 0 && k <= SPAN_MAXK, "hual_span_hit_prob: 0 <= k <= 16");
   HUAL_REQUIRE(M >= 1 && M <= SH_MAXM, "hual_span_hit_prob: 1 <= M <= 4");
   ShThresholds thr = {};
   for (int m = 0; m < M; ++m) {

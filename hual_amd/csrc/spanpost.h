@@ -1,8 +1,9 @@
 // The span posterior of one sample given its answered active points, as every launch of the family opens it (hual_al_query in
 // spanquery.hip, hual_al_mbr_label in spanlabel.hip, hual_al_label_gain in spangain.hip, hual_al_span_marginals in spanmarg.hip,
-// every step of hual_al_session in spansession.hip; the
+// every step of hual_al_session in spansession.hip, hual_al_design in spandesign.hip, every pass of the ensemble launches in
+// spanens.hip, hual_al_noisy_tilt in spannoisy.hip, the header of hual_al_evidence_grid in spancalib.hip; the
 // contract is in include/hual_seqpan.h): which rows are live, what the consistent set A is, and what Z and Z_A are.  One definition, so
-// all launches classify a row alike.
+// all launches classify a row alike (tests/test_gpu_span_rows.py); the per-clip launches of the evaluation have theirs in spanclip.h.
 //
 // The active points: points with a frame index outside [0, v) are ignored, the positives are reduced to their hull, the negatives to the
 // nearest one on either side of it or - without a positive - to the gaps between them.  hual_al_label_gain asks what A would be after one
@@ -109,24 +110,32 @@ struct SpanRow {
 // (uniform) every weight underflowed or an infinite logit made them NaN: poisoned, as hual_span_expected_iou; nothing left in A:
 // contradictory
 __device__ __forceinline__ int posterior_status(double zf, double za) {
-  return !(zf > 0.0 && zf < INFINITY) ? SPAN_POISONED : !(za > 0.0) ? SPAN_CONTRADICTORY : SPAN_LIVE;
+  return !span_mass_live(zf) ? SPAN_POISONED : !(za > 0.0) ? SPAN_CONTRADICTORY : SPAN_LIVE;
 }
 
-// stage 1: sample n's row, LIVE with lds.ps / lds.pe readable, or POISONED - empty, with a NaN logit, or longer than the 256 frames
-// the family handles (the host cannot see tlen without a read-back).  Called by the whole workgroup; its barriers publish what was
-// written before it.
-__device__ __forceinline__ void open_span_row(const hual::AlSpanIn& in, int n, SpanRowLds& lds, SpanRow& r) {
+// the header of stage 1: sample n's row, LIVE with its active-point slice, or POISONED - empty, with a NaN logit, or longer than the
+// 256 frames the family handles (the host cannot see tlen without a read-back).  All a launch needs that takes probabilities of its
+// own (hual_al_evidence_grid: one softmax per temperature).  Called by the whole workgroup; one barrier on a row that is not empty.
+__device__ __forceinline__ void open_span_row_header(const hual::AlSpanIn& in, int n, SpanRow& r) {
   r.T = in.set.tlen[n];
   r.row = (size_t)n * in.set.ld;
   const bool fits = r.T >= 1 && r.T <= 256 && r.T <= in.set.ld;
   r.v = fits ? span_clip_len(in.set.vlen[n], r.T) : 0;
   r.status = (r.v == 0 || span_row_poisoned(in.s0, in.e0, r.row, r.v)) ? SPAN_POISONED : SPAN_LIVE;
   if (r.status == SPAN_LIVE) {
-    span_probabilities(in.s0, in.e0, r.row, r.T, r.v, lds.ps, lds.pe, lds.smf, lds.smd);
     const int ap0 = in.set.ap_off[n];
     r.napn = in.set.ap_off[n + 1] - ap0;
     r.aidx = in.set.ap_idx + ap0;
     r.apos = in.set.ap_pos + ap0;
+  }
+}
+
+// stage 1: the header, and on a LIVE row lds.ps / lds.pe readable and the hull.  Called by the whole workgroup; its barriers publish
+// what was written before it.
+__device__ __forceinline__ void open_span_row(const hual::AlSpanIn& in, int n, SpanRowLds& lds, SpanRow& r) {
+  open_span_row_header(in, n, r);
+  if (r.status == SPAN_LIVE) {
+    span_probabilities(in.s0, in.e0, r.row, r.T, r.v, lds.ps, lds.pe, lds.smf, lds.smd);
     r.hull = ap_hull(r.aidx, r.apos, r.napn, r.v);
   }
 }

@@ -1,4 +1,5 @@
-// The span distribution's probability stage, shared by the per-clip span kernels (topk.hip, spanconf.hip): the masked softmaxes of
+// The span distribution's probability stage, shared by every span kernel outside the forward - the per-clip launches through spanclip.h
+// (topk.hip, spanconf.hip, spanhit.hip), the span-posterior launches through spanpost.h -: the masked softmaxes of
 // the start / end logits exactly as the span stage of heads_kernel computes them (same masking, the same code for the max and the
 // double-sum reductions - block.h -, same rounding), so every kernel that includes this sees the numbers of hual_span_argmax bit for bit.
 #pragma once
@@ -15,6 +16,11 @@ __device__ __forceinline__ int span_row_poisoned(const float* __restrict__ zs_, 
   const int t = threadIdx.x;
   return __syncthreads_or(t < v && (zs_[row + t] != zs_[row + t] || ze_[row + t] != ze_[row + t]));
 }
+
+// (uniform) the live rule of every launch that normalises by the triangle's mass Z: every weight underflowed (Z == 0), or an infinite
+// logit made Z Inf or NaN - as a poisoned row.  Each launch sums its own Z (float32 products in spanconf.hip, float64 ones in
+// spanhit.hip and spanpost.h): they can differ where a float32 product underflows.
+__device__ __forceinline__ bool span_mass_live(double Z) { return Z > 0.0 && Z < INFINITY; }
 
 // ps / pe [256] (LDS) <- softmax of the masked logits of one clip, 1 <= v <= T <= 256, thread t's start / end logit given by start() /
 // end() (called at t < v only): read from memory by span_probabilities below, a register's value scaled by 1 / tau in

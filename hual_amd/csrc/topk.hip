@@ -10,7 +10,7 @@
 // Latency bound: at most 2 KB of logits in and 20 * k bytes out per clip, no matrix work; one barrier per round (ABI 9).
 #include "common.h"
 #include "prof.h"
-#include "spanprob.h"
+#include "spanclip.h"
 
 using namespace hual;
 
@@ -48,12 +48,8 @@ __device__ __forceinline__ void tk_scan(int c0, int c1, int v, int L, const floa
                                         float nms_iou, float& bs, int& bk) {
   bs = -1.f; bk = TK_NONE;
   if (c0 >= c1) return;
-  int lo = 0, hi = v - 1;      // the row holding c0: the largest i with tk_row_off(i) <= c0
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tk_row_off(mid, v, L) <= c0) lo = mid; else hi = mid - 1;
-  }
-  int i = lo, j = lo + (c0 - tk_row_off(lo, v, L));
+  int i = tri_locate(c0, v, [=](int r) { return tk_row_off(r, v, L); });      // the row holding c0
+  int j = i + (c0 - tk_row_off(i, v, L));
   int jend = min(v - 1, i + L - 1);
   float p = ps[i];
   for (int c = c0; c < c1; ++c) {
@@ -77,14 +73,12 @@ __global__ __launch_bounds__(TK_THREADS) void span_topk_kernel(const float* __re
   __shared__ double smd[2 * TK_WAVES];
   __shared__ float wbs[2][TK_WAVES];
   __shared__ int wbk[2][TK_WAVES];
-  __shared__ int sel[16];
+  __shared__ int sel[SPAN_MAXK];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int v = span_clip_len(vlen_[b], T);
-  const size_t row = (size_t)b * T;
+  const SpanClip clip = open_span_clip(zs_, ze_, vlen_, T, ps, pe, smf, smd, [](int) {});
+  const int v = clip.v;
   int nout = 0;
-  const int nanlogit = span_row_poisoned(zs_, ze_, row, v);
-  if (v > 0 && !nanlogit) {
-    span_probabilities(zs_, ze_, row, T, v, ps, pe, smf, smd);      // (spanprob.h: the numbers of hual_span_argmax)
+  if (clip.open) {
     // ---- candidates: this thread's stretch of the row-major triangle
     const int L = max_len > 0 ? min(max_len, v) : v;
     const int n = tk_row_off(v, v, L);
@@ -124,7 +118,7 @@ extern "C" int hual_span_topk(const float* start_logits, const float* end_logits
   HUAL_REQUIRE(start_logits && end_logits && video_seq_len && start_index && end_index && score, "hual_span_topk: null pointer");
   HUAL_REQUIRE(B >= 1, "hual_span_topk: B >= 1");
   HUAL_REQUIRE(T >= 1 && T <= 256, "hual_span_topk: 1 <= T <= 256");
-  HUAL_REQUIRE(k >= 1 && k <= 16, "hual_span_topk: 1 <= k <= 16");
+  HUAL_REQUIRE(k >= 1 && k <= SPAN_MAXK, "hual_span_topk: 1 <= k <= 16");
   HUAL_REQUIRE(nms_iou > 0.f && nms_iou <= 1.f, "hual_span_topk: 0 < nms_iou <= 1");
   HUAL_REQUIRE(max_len >= 0, "hual_span_topk: max_len >= 0 (0: no limit)");
   const double bytes = 8.0 * B * T + 4.0 * B + 20.0 * B * k;

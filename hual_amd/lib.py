@@ -286,20 +286,49 @@ def linear_dw(A, dY, dW, db=None, workgroups=0):
                                 workgroups, ptr(scratch), 1024, stream_ptr()))
 
 
+def _clip_logits(who, start_logits, end_logits):
+    import torch
+    if start_logits.dtype != torch.float32 or end_logits.dtype != torch.float32:
+        raise HualError(who + ': float32 logits required')
+    if start_logits.dim() != 2 or end_logits.shape != start_logits.shape:
+        raise HualError(who + ': start / end logits must both be [B,T]')
+
+
+def _clip_lengths(who, start_logits, end_logits, video_seq_len):
+    import torch
+    s, e = start_logits.contiguous(), end_logits.contiguous()
+    B, T = s.shape
+    vl = video_seq_len.to(device=s.device, dtype=torch.int32).contiguous()
+    if vl.numel() != B:
+        raise HualError(who + ': video_seq_len must hold B = %d lengths' % B)
+    return s, e, vl, B, T
+
+
+def _clip_inputs(who, start_logits, end_logits, video_seq_len):
+    """the gate of every per-clip span launch -> (s, e, vl, B, T), the logits contiguous, the lengths int32 on their device"""
+    _clip_logits(who, start_logits, end_logits)
+    return _clip_lengths(who, start_logits, end_logits, video_seq_len)
+
+
+def _clip_slots(who, starts, ends, score, B, dev):
+    """the gate of the proposal slots starts / ends int64 [B,k] and score float32 [B,k] or None -> k.  No .contiguous() here: a
+    reorder writes them in place, and a copy would take the permutation with it"""
+    import torch
+    if starts.dim() != 2 or starts.shape[0] != B:
+        raise HualError(who + ': starts / ends must be [B,k] with B = %d' % B)
+    k = int(starts.shape[1])
+    for x, dt, what in ((starts, torch.int64, 'starts'), (ends, torch.int64, 'ends'), (score, torch.float32, 'score')):
+        if x is not None and (x.dtype != dt or tuple(x.shape) != (B, k) or not x.is_contiguous() or x.device != dev):
+            raise HualError(who + ': %s must be a contiguous [B,k] %s tensor on the logits\' device' % (what, str(dt).replace('torch.', '')))
+    return k
+
+
 def span_topk(start_logits, end_logits, video_seq_len, k, max_len=0, nms_iou=1.0, out=None):
     """the k best spans of each clip after greedy temporal NMS (hual_span_topk): start_logits / end_logits f32 [B,T] and
     video_seq_len [B] on the device -> (start [B,k] int64, end [B,k] int64, score [B,k] float32), enqueued on the current stream.
     Slots no candidate fills are -1 (score -1.0).  out: three contiguous device tensors of those shapes to write into instead."""
     import torch
-    if start_logits.dtype != torch.float32 or end_logits.dtype != torch.float32:
-        raise HualError('span_topk: float32 logits required')
-    if start_logits.dim() != 2 or end_logits.shape != start_logits.shape:
-        raise HualError('span_topk: start / end logits must both be [B,T]')
-    s, e = start_logits.contiguous(), end_logits.contiguous()
-    B, T = s.shape
-    vl = video_seq_len.to(device=s.device, dtype=torch.int32).contiguous()
-    if vl.numel() != B:
-        raise HualError('span_topk: video_seq_len must hold B = %d lengths' % B)
+    s, e, vl, B, T = _clip_inputs('span_topk', start_logits, end_logits, video_seq_len)
     k = int(k)
     if out is None:
         out = (torch.empty(B, k, dtype=torch.int64, device=s.device), torch.empty(B, k, dtype=torch.int64, device=s.device),
@@ -321,31 +350,17 @@ def span_expected_iou(start_logits, end_logits, video_seq_len, starts, ends, sco
     IoU, best first, stable: starts, ends and score (float32 [B,k] or None) are permuted in place along with the result.
     out: (expected_iou, span_entropy) contiguous device tensors of those shapes to write into instead (span_entropy may be None)."""
     import torch
-    if start_logits.dtype != torch.float32 or end_logits.dtype != torch.float32:
-        raise HualError('span_expected_iou: float32 logits required')
-    if start_logits.dim() != 2 or end_logits.shape != start_logits.shape:
-        raise HualError('span_expected_iou: start / end logits must both be [B,T]')
-    s, e = start_logits.contiguous(), end_logits.contiguous()
-    B, T = s.shape
-    vl = video_seq_len.to(device=s.device, dtype=torch.int32).contiguous()
-    if vl.numel() != B:
-        raise HualError('span_expected_iou: video_seq_len must hold B = %d lengths' % B)
-    if starts.dim() != 2 or starts.shape[0] != B:
-        raise HualError('span_expected_iou: starts / ends must be [B,k] with B = %d' % B)
-    k = int(starts.shape[1])
-    # (no .contiguous() here: reorder writes them in place, and a copy would take the permutation with it)
-    for x, dt, what in ((starts, torch.int64, 'starts'), (ends, torch.int64, 'ends'), (score, torch.float32, 'score')):
-        if x is not None and (x.dtype != dt or tuple(x.shape) != (B, k) or not x.is_contiguous() or x.device != s.device):
-            raise HualError('span_expected_iou: %s must be a contiguous [B,k] %s tensor on the logits\' device'
-                            % (what, str(dt).replace('torch.', '')))
+    who = 'span_expected_iou'
+    s, e, vl, B, T = _clip_inputs(who, start_logits, end_logits, video_seq_len)
+    k = _clip_slots(who, starts, ends, score, B, s.device)
     if out is None:
         out = (torch.empty(B, k, dtype=torch.float32, device=s.device), torch.empty(B, dtype=torch.float32, device=s.device) if entropy else None)
     else:
         if len(out) != 2 or out[0] is None:
-            raise HualError('span_expected_iou: out is (expected_iou [B,k], span_entropy [B] or None)')
+            raise HualError(who + ': out is (expected_iou [B,k], span_entropy [B] or None)')
         for o, shape in zip(out, ((B, k), (B,))):
             if o is not None and (o.dtype != torch.float32 or tuple(o.shape) != shape or not o.is_contiguous() or o.device != s.device):
-                raise HualError('span_expected_iou: out tensors must be contiguous float32 [B,k] and [B] on the logits\' device')
+                raise HualError(who + ': out tensors must be contiguous float32 [B,k] and [B] on the logits\' device')
     check(load().hual_span_expected_iou(ptr(s), ptr(e), ptr(vl), B, T, k, ptr(starts), ptr(ends), ptr(score), ptr(out[0]), ptr(out[1]),
                                         1 if reorder else 0, stream_ptr()))
     return out[0], out[1]
@@ -389,28 +404,15 @@ def span_hit_prob(start_logits, end_logits, video_seq_len, thresholds=(0.3, 0.5,
     tensors of those shapes to write into instead."""
     import torch
     who = 'span_hit_prob'
-    if start_logits.dtype != torch.float32 or end_logits.dtype != torch.float32:
-        raise HualError(who + ': float32 logits required')
-    if start_logits.dim() != 2 or end_logits.shape != start_logits.shape:
-        raise HualError(who + ': start / end logits must both be [B,T]')
+    _clip_logits(who, start_logits, end_logits)      # (_clip_inputs in its two parts: the thresholds' faults are reported between them, as always)
     thr = hit_thresholds(thresholds)
+    s, e, vl, B, T = _clip_lengths(who, start_logits, end_logits, video_seq_len)
     M = len(thr)
-    s, e = start_logits.contiguous(), end_logits.contiguous()
-    B, T = s.shape
-    vl = video_seq_len.to(device=s.device, dtype=torch.int32).contiguous()
-    if vl.numel() != B:
-        raise HualError(who + ': video_seq_len must hold B = %d lengths' % B)
     if (starts is None) != (ends is None):
         raise HualError(who + ': starts and ends are given together')
     k = 0
     if starts is not None:
-        if starts.dim() != 2 or starts.shape[0] != B:
-            raise HualError(who + ': starts / ends must be [B,k] with B = %d' % B)
-        k = int(starts.shape[1])
-        # (no .contiguous() here: reorder_by writes them in place, and a copy would take the permutation with it)
-        for x, dt, what in ((starts, torch.int64, 'starts'), (ends, torch.int64, 'ends'), (score, torch.float32, 'score')):
-            if x is not None and (x.dtype != dt or tuple(x.shape) != (B, k) or not x.is_contiguous() or x.device != s.device):
-                raise HualError(who + ': %s must be a contiguous [B,k] %s tensor on the logits\' device' % (what, str(dt).replace('torch.', '')))
+        k = _clip_slots(who, starts, ends, score, B, s.device)
     elif score is not None or reorder_by is not None:
         raise HualError(who + ': score and reorder_by need proposals (starts, ends)')
     if not k and not best:

@@ -35,6 +35,19 @@ STATE_FORMAT = 1      # Runner.save_state
 from .train import Trainer
 
 
+def _packed(n, groups, dev):
+    """one byte buffer on dev that holds, block after block, an [n, columns] array ([n] with columns None) for each (dtype, columns) of
+    groups - the widest dtype first, so that every block is aligned -> (its typed views, host): host() copies the buffer in ONE
+    transfer and gives the same views of the copy as numpy arrays"""
+    ends = np.cumsum([dt.itemsize * n * (c or 1) for dt, c in groups]).tolist()
+    assert all(a % dt.itemsize == 0 for (dt, _), a in zip(groups, [0] + ends)), 'a block of %s is not aligned: widest dtype first' % (groups,)
+
+    def views(buf):
+        return tuple(buf[a:b].view(dt).view((n, c) if c else (n,)) for (dt, c), a, b in zip(groups, [0] + ends, ends))
+    buf = torch.empty(ends[-1], dtype=torch.uint8, device=dev)
+    return views(buf), lambda: tuple(x.numpy() for x in views(buf.cpu()))
+
+
 class Runner:
     def __init__(self, configs, word_vectors, train_records, test_records, visual_feats, device='cuda:0', seed=12345,
                  ckpt_dir=None, logger=None, feed='device'):
@@ -196,49 +209,38 @@ class Runner:
         n = sum(hi - lo for lo, hi in mine)
         dev = self.model.device
         # one buffer for the three outputs: starts | ends (int64) | scores (float32), each [n,k]
-        buf = torch.empty(n * k * 20, dtype=torch.uint8, device=dev)
-        st = buf[:8 * n * k].view(torch.int64).view(n, k)
-        en = buf[8 * n * k:16 * n * k].view(torch.int64).view(n, k)
-        sc = buf[16 * n * k:].view(torch.float32).view(n, k)
+        (st, en, sc), top_host = _packed(n, ((torch.int64, k), (torch.int64, k), (torch.float32, k)), dev)
         # re-ranking: expected IoU [n,k] | span entropy [n] (float32), one more buffer
-        cbuf = torch.empty(n * k + n, dtype=torch.float32, device=dev) if rerank == 'expected_iou' else None
+        (cei, cent), conf_host = _packed(n, ((torch.float32, k), (torch.float32, None)), dev) if rerank == 'expected_iou' else ((None, None), None)
         # hit probability [n,k,1] of the one threshold; the Bayes spans: starts | ends (int64) | probabilities (float32), each [n,3]
         hbuf = torch.empty(n, k, 1, dtype=torch.float32, device=dev) if rerank == 'hit_prob' else None
-        bbuf = torch.empty(n * 3 * 20, dtype=torch.uint8, device=dev) if bayes_spans else None
-        if bayes_spans:
-            bst, ben = bbuf[:24 * n].view(torch.int64).view(n, 3), bbuf[24 * n:48 * n].view(torch.int64).view(n, 3)
-            bpr = bbuf[48 * n:].view(torch.float32).view(n, 3)
+        (bst, ben, bpr), bayes_host = _packed(n, ((torch.int64, 3), (torch.int64, 3), (torch.float32, 3)), dev) if bayes_spans else ((None,) * 3, None)
         pos = 0
         for lo, hi in mine:
             sel = np.arange(lo, hi)
+            rows = slice(pos, pos + hi - lo)
             f = ds.assemble(sel, labels=False, min_chars=4)
             o = self.model.forward(f['video'], f['video_seq_len'], f['word_ids'], f['char_ids'], drop_rate=0.0)
             lib.span_topk(o['start_logits'], o['end_logits'], f['video_seq_len'], k, max_len=max_len, nms_iou=nms_iou,
-                          out=(st[pos:pos + hi - lo], en[pos:pos + hi - lo], sc[pos:pos + hi - lo]))
+                          out=(st[rows], en[rows], sc[rows]))
             if rerank == 'expected_iou':
-                lib.span_expected_iou(o['start_logits'], o['end_logits'], f['video_seq_len'], st[pos:pos + hi - lo], en[pos:pos + hi - lo],
-                                      score=sc[pos:pos + hi - lo], reorder=True,
-                                      out=(cbuf[:n * k].view(n, k)[pos:pos + hi - lo], cbuf[n * k:][pos:pos + hi - lo]))
+                lib.span_expected_iou(o['start_logits'], o['end_logits'], f['video_seq_len'], st[rows], en[rows], score=sc[rows], reorder=True,
+                                      out=(cei[rows], cent[rows]))
             if rerank == 'hit_prob':
-                lib.span_hit_prob(o['start_logits'], o['end_logits'], f['video_seq_len'], hit_thr, st[pos:pos + hi - lo], en[pos:pos + hi - lo],
-                                  score=sc[pos:pos + hi - lo], reorder_by=0, out=(hbuf[pos:pos + hi - lo], None))
+                lib.span_hit_prob(o['start_logits'], o['end_logits'], f['video_seq_len'], hit_thr, st[rows], en[rows], score=sc[rows],
+                                  reorder_by=0, out=(hbuf[rows], None))
             if bayes_spans:
                 lib.span_hit_prob(o['start_logits'], o['end_logits'], f['video_seq_len'], self.BAYES_IOUS, best=True,
-                                  out=(None, (bst[pos:pos + hi - lo], ben[pos:pos + hi - lo], bpr[pos:pos + hi - lo])))
+                                  out=(None, (bst[rows], ben[rows], bpr[rows])))
             pos += hi - lo
-        h = buf.cpu().numpy()
         ids = np.concatenate([np.arange(lo, hi) for lo, hi in mine]) if mine else np.zeros(0, dtype=np.int64)
-        part = (ids, h[:8 * n * k].view(np.int64).reshape(n, k), h[8 * n * k:16 * n * k].view(np.int64).reshape(n, k),
-                h[16 * n * k:].view(np.float32).reshape(n, k))
+        part = (ids,) + top_host()
         if rerank == 'expected_iou':
-            hc = cbuf.cpu().numpy()
-            part += (hc[:n * k].reshape(n, k), hc[n * k:])
+            part += conf_host()
         if rerank == 'hit_prob':
             part += (hbuf.cpu().numpy().reshape(n, k),)
         if bayes_spans:
-            hb = bbuf.cpu().numpy()
-            part += (hb[:24 * n].view(np.int64).reshape(n, 3), hb[24 * n:48 * n].view(np.int64).reshape(n, 3),
-                     hb[48 * n:].view(np.float32).reshape(n, 3))
+            part += bayes_host()
         if self.world > 1:
             parts = hdist.gather_objects(part)
             if self.rank == 0:

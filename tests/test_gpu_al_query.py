@@ -23,6 +23,7 @@ import torch
 import al_query_ref as Q
 import al_synth
 import span_topk_ref as R
+from span_clip_util import _pads_intact, _sentinel
 
 pytestmark = pytest.mark.gpu
 
@@ -33,17 +34,6 @@ FILL = 777.0
 @pytest.fixture(scope='module')
 def dev():
     return torch.device('cuda:0')
-
-
-def _sentinel(shape, dtype, dev, value, pad=64):
-    """a tensor of `shape` in the middle of a larger allocation filled with `value`: (view, whole buffer, pad)"""
-    n = int(np.prod(shape))
-    whole = torch.full((n + 2 * pad,), value, dtype=dtype, device=dev)
-    return whole[pad:pad + n].view(*shape), whole, pad
-
-
-def _pads_intact(whole, pad, value):
-    return bool((whole[:pad] == value).all()) and bool((whole[-pad:] == value).all())
 
 
 def make_set(dev, vlen, tlen, aps, ld):

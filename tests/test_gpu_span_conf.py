@@ -21,6 +21,7 @@ import torch
 import al_synth
 import span_conf_ref as C
 import span_topk_ref as R
+from span_clip_util import _pads_intact, _sentinel, _task, _videos
 
 pytestmark = pytest.mark.gpu
 
@@ -44,17 +45,6 @@ def inputs(T, seed=SEED):
     vl = torch.randint(1, T + 1, (B,), generator=g, dtype=torch.int32)
     vl[0], vl[1], vl[2] = 1, max(1, T - 1), T
     return s, e, vl
-
-
-def _sentinel(shape, dtype, dev, value, pad=64):
-    """a tensor of `shape` in the middle of a larger allocation filled with `value`: (view, whole buffer, pad)"""
-    n = int(np.prod(shape))
-    whole = torch.full((n + 2 * pad,), value, dtype=dtype, device=dev)
-    return whole[pad:pad + n].view(*shape), whole, pad
-
-
-def _pads_intact(whole, pad, value):
-    return bool((whole[:pad] == value).all()) and bool((whole[-pad:] == value).all())
 
 
 def _run(dev, s, e, vl, st, en, sc=None, reorder=False):
@@ -219,32 +209,6 @@ def test_expected_iou_in_a_captured_graph(dev):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. evaluation
-def _videos(nvid, vdim, seed):
-    g = np.random.default_rng(seed)
-    vis = {}
-    for v in range(nvid):
-        T = int(g.integers(20, 33))
-        f = 0.1 * g.standard_normal((T, vdim)).astype(np.float32)
-        f[:, 0] = np.linspace(-1, 1, T)
-        vis['v%d' % v] = f
-    return vis
-
-
-def _task(n, vis, seed):
-    g = np.random.default_rng(seed)
-    recs = []
-    for i in range(n):
-        vid = 'v%d' % int(g.integers(0, len(vis)))
-        T = vis[vid].shape[0]
-        part = int(g.integers(0, 3))
-        s = part * T // 3 + 1
-        e = min(T - 1, s + T // 3 - 2)
-        words = ['w%d' % (2 + part), 'w%d' % int(g.integers(5, 30)), 'w%d' % int(g.integers(5, 30))]
-        recs.append(dict(vid=vid, duration=float(T), v_len=T, words=words, w_ids=[int(w[1:]) for w in words],
-                         c_ids=[[1 + part, 2, 3, 4]] * 3, s_ind=s, e_ind=e))
-    return recs
-
-
 def test_reranked_evaluation(tmp_path):
     from hual_amd import al, data
     from hual_amd.runner import Runner

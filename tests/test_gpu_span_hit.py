@@ -16,6 +16,7 @@ import torch
 import span_conf_ref as C
 import span_hit_ref as H
 import span_topk_ref as R
+from span_clip_util import _pads_intact, _sentinel, _task, _videos
 
 pytestmark = pytest.mark.gpu
 
@@ -40,17 +41,6 @@ def inputs(T, scale, seed=SEED):
     vl = torch.randint(1, T + 1, (B,), generator=g, dtype=torch.int32)
     vl[0], vl[1], vl[2], vl[3] = T, max(1, T - 1), 1, min(T, 2)
     return s, e, vl
-
-
-def _sentinel(shape, dtype, dev, value, pad=64):
-    """a tensor of `shape` in the middle of a larger allocation filled with `value`: (view, whole buffer, pad)"""
-    n = int(np.prod(shape))
-    whole = torch.full((n + 2 * pad,), value, dtype=dtype, device=dev)
-    return whole[pad:pad + n].view(*shape), whole, pad
-
-
-def _pads_intact(whole, pad, value):
-    return bool((whole[:pad] == value).all()) and bool((whole[-pad:] == value).all())
 
 
 def _run(dev, s, e, vl, thr, st=None, en=None, sc=None, reorder_by=None, best=False):
@@ -367,7 +357,6 @@ def test_second_launch_and_captured_graph(dev):
 
 # ---------------------------------------------------------------------------------------------------------------- 6. evaluation
 def test_hit_prob_evaluation(tmp_path, monkeypatch):
-    from test_gpu_span_conf import _task, _videos
     from hual_amd import al, lib
     from hual_amd.runner import Runner
     vdim, k = 64, 5

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import span_topk_ref as R
+from span_clip_util import _task, _videos
 
 pytestmark = pytest.mark.gpu
 
@@ -153,34 +154,6 @@ def test_topk_in_a_captured_graph(dev):
 
 
 # ------------------------------------------------------------------ whole model: the learnable task of test_gpu_runner.py
-def _videos(nvid, vdim, seed):
-    g = np.random.default_rng(seed)
-    vis = {}
-    for v in range(nvid):
-        T = int(g.integers(20, 33))
-        f = 0.1 * g.standard_normal((T, vdim)).astype(np.float32)
-        f[:, 0] = np.linspace(-1, 1, T)                    # position signal
-        vis['v%d' % v] = f
-    return vis
-
-
-def _task(n, vis, seed):
-    g = np.random.default_rng(seed)
-    nvid = len(vis)
-    dur = {k: float(v.shape[0]) for k, v in vis.items()}
-    recs = []
-    for i in range(n):
-        vid = 'v%d' % int(g.integers(0, nvid))
-        T = vis[vid].shape[0]
-        part = int(g.integers(0, 3))                       # early / middle / late third, named by the first word
-        s = part * T // 3 + 1
-        e = min(T - 1, s + T // 3 - 2)
-        words = ['w%d' % (2 + part), 'w%d' % int(g.integers(5, 30)), 'w%d' % int(g.integers(5, 30))]
-        recs.append(dict(vid=vid, duration=dur[vid], v_len=T, words=words, w_ids=[int(w[1:]) for w in words],
-                         c_ids=[[1 + part, 2, 3, 4]] * 3, s_ind=s, e_ind=e))
-    return recs
-
-
 def test_runner_evaluate_recall_at_k(tmp_path):
     from hual_amd import data
     from hual_amd.runner import Runner
