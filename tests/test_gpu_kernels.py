@@ -64,15 +64,65 @@ def _attn_ref(Q, K, V, qm, km, B, Tq, Tk, drop=None):
     return (pr @ v).transpose(1, 2).reshape(B * Tq, 128)
 
 
-@pytest.mark.parametrize('B,Tq,Tk', [(2, 16, 16), (3, 37, 9), (2, 128, 128), (1, 20, 256), (2, 100, 30), (1, 256, 256), (3, 1, 1)])
+def _attn_fwd_form(Tq, Tk):
+    """csrc/attn.hip launch_attn_fwd with ONE job: NK by the key tiles, eight waves from eight 16-query tiles on"""
+    nkt = (Tk + 15) // 16
+    return 'attn_fwd_kernel<%d, %d>' % (2 if nkt <= 2 else 4 if nkt <= 4 else 8 if nkt <= 8 else 16, 512 if (Tq + 15) // 16 >= 8 else 256)
+
+
+def _attn_bwd_form(Tq, Tk):
+    """csrc/attn.hip launch_attn_bwd with ONE job: never the chain kernel (four jobs); eight waves beyond 128 queries AND keys"""
+    return 'attn_bwd_big_kernel' if Tq > 128 and Tk > 128 else 'attn_bwd_kernel'
+
+
+def _attn_prof(fn):
+    """{symbol: launches} of the attn_ family among the launches fn() makes (hual_prof_begin .. hual_prof_end)"""
+    from hual_amd import lib
+    l = lib.load()
+    lib.check(l.hual_prof_begin())
+    try:
+        fn()
+    finally:
+        n = l.hual_prof_end()
+    got = {}
+    for i in range(n):
+        name, cnt = ctypes.create_string_buffer(256), ctypes.c_int64()
+        lib.check(l.hual_prof_get(i, name, 256, ctypes.byref(cnt), None, None, None))
+        if name.value.decode().startswith('attn_'):
+            got[name.value.decode()] = int(cnt.value)
+    return got
+
+
+# (2, 20, 33), (2, 20, 64): attn_fwd_kernel<4, 256> - fewer than eight query tiles against 33 .. 64 keys, which no dual attention launch
+# reaches (its four jobs have eight tiles from 33 rows on either side on)
+ATTN_FWD_CASES = [(2, 16, 16), (3, 37, 9), (2, 128, 128), (1, 20, 256), (2, 100, 30), (1, 256, 256), (3, 1, 1), (2, 20, 33), (2, 20, 64)]
+ATTN_BWD_CASES = [(2, 16, 16), (3, 37, 9), (2, 128, 128), (1, 20, 256), (2, 128, 20), (1, 256, 20), (2, 200, 32), (2, 100, 100), (1, 256, 256), (3, 1, 1),
+                  (2, 20, 33), (2, 20, 64)]
+
+
+def test_blocks_and_kernels_cover_every_attention_instantiation():
+    """the eight forward instantiations and the three backward kernels of csrc/attn.hip: each is launched - and asserted by symbol - by a
+    case here (one job per launch) or by a case of test_gpu_da_forms.py (the four jobs of a layer)"""
+    import test_gpu_da_forms as da
+    ran = {_attn_fwd_form(Tq, Tk) for _, Tq, Tk in ATTN_FWD_CASES + ATTN_BWD_CASES} | {_attn_bwd_form(Tq, Tk) for _, Tq, Tk in ATTN_BWD_CASES}
+    ran |= {s for s in da.covered_symbols() if s.startswith('attn_')}
+    want = {'attn_fwd_kernel<%d, %d>' % (nk, th) for nk in (2, 4, 8, 16) for th in (256, 512)}
+    assert ran == want | {'attn_bwd_chain_kernel', 'attn_bwd_big_kernel', 'attn_bwd_kernel'}, sorted(ran ^ want)
+    # what only the one-job launches reach
+    assert {'attn_fwd_kernel<%d, 256>' % nk for nk in (4, 8, 16)} <= {_attn_fwd_form(Tq, Tk) for _, Tq, Tk in ATTN_BWD_CASES}
+    assert {_attn_bwd_form(Tq, Tk) for _, Tq, Tk in ATTN_BWD_CASES} == {'attn_bwd_big_kernel', 'attn_bwd_kernel'}
+
+
+@pytest.mark.parametrize('B,Tq,Tk', ATTN_FWD_CASES)
 def test_attention_fwd(dev, B, Tq, Tk):
     """fp16-pair products (three passes, 22-bit operands) + fp32 softmax: at the level of a float32 PyTorch evaluation of the same
     function (3e-7 .. 1.4e-6 measured on these cases against 3e-7 .. 7e-7, scripts/exp/attn_err.py); gate 6e-6 on O(1) outputs (bar: 1e-3)"""
     from hual_amd import lib
     Q, K, V, qm, km = _attn_case(dev, B, Tq, Tk, B * 1000 + Tq + Tk)
     O = torch.empty(B * Tq, 128, device=dev)
-    lib.check(lib.load().hual_attention_fwd(lib.ptr(Q), 128, lib.ptr(K), lib.ptr(V), 128, lib.ptr(O), 128, B, Tq, Tk, lib.ptr(qm),
-                                            lib.ptr(km), lib.stream_ptr()))
+    got = _attn_prof(lambda: lib.check(lib.load().hual_attention_fwd(lib.ptr(Q), 128, lib.ptr(K), lib.ptr(V), 128, lib.ptr(O), 128, B, Tq, Tk,
+                                                                     lib.ptr(qm), lib.ptr(km), lib.stream_ptr())))
+    assert got == {_attn_fwd_form(Tq, Tk): 1}, got
     ref = _attn_ref(Q.double(), K.double(), V.double(), qm.double(), km.double(), B, Tq, Tk)
     assert (O.double() - ref).abs().max().item() < 6e-6
 
@@ -91,7 +141,7 @@ def test_attention_fwd_rejects_more_than_256_queries(dev):
         lib.check(rc)
 
 
-@pytest.mark.parametrize('B,Tq,Tk', [(2, 16, 16), (3, 37, 9), (2, 128, 128), (1, 20, 256), (2, 128, 20), (1, 256, 20), (2, 200, 32), (2, 100, 100), (1, 256, 256), (3, 1, 1)])
+@pytest.mark.parametrize('B,Tq,Tk', ATTN_BWD_CASES)
 @pytest.mark.parametrize('rate', [0.0, 0.2])
 def test_attention_fwd_bwd_with_dropout(dev, B, Tq, Tk, rate):
     """hual_attention_fwd_save + hual_attention_bwd against float64 autograd of the same function with the oracle's dropout
@@ -108,12 +158,16 @@ def test_attention_fwd_bwd_with_dropout(dev, B, Tq, Tk, rate):
     keep = torch.zeros(B * Tq * 8, ldm, dtype=torch.uint8, device=dev)
     stats = torch.zeros(2, B * Tq * 8, device=dev)
     O = torch.empty(B * Tq, 128, device=dev)
-    lib.check(l.hual_attention_fwd_save(lib.ptr(Q), 128, lib.ptr(K), lib.ptr(V), 128, lib.ptr(O), 128, B, Tq, Tk, lib.ptr(qm), lib.ptr(km),
-                                        lib.ptr(stats), lib.ptr(keep), ldm, lib.ptr(rng_state), rate, site, lib.stream_ptr()))
     dQ, dK, dV = torch.full_like(Q, 7.0), torch.full_like(K, 7.0), torch.full_like(V, 7.0)      # written, not accumulated
-    lib.check(l.hual_attention_bwd(lib.ptr(Q), 128, lib.ptr(K), lib.ptr(V), 128, lib.ptr(O), 128, lib.ptr(stats), lib.ptr(keep), ldm,
-                                   lib.ptr(dO), 128, lib.ptr(dQ), 128, lib.ptr(dK), lib.ptr(dV), 128, B, Tq, Tk, lib.ptr(qm), lib.ptr(km),
-                                   lib.ptr(rng_state), rate, site, lib.stream_ptr()))
+
+    def call():
+        lib.check(l.hual_attention_fwd_save(lib.ptr(Q), 128, lib.ptr(K), lib.ptr(V), 128, lib.ptr(O), 128, B, Tq, Tk, lib.ptr(qm), lib.ptr(km),
+                                            lib.ptr(stats), lib.ptr(keep), ldm, lib.ptr(rng_state), rate, site, lib.stream_ptr()))
+        lib.check(l.hual_attention_bwd(lib.ptr(Q), 128, lib.ptr(K), lib.ptr(V), 128, lib.ptr(O), 128, lib.ptr(stats), lib.ptr(keep), ldm,
+                                       lib.ptr(dO), 128, lib.ptr(dQ), 128, lib.ptr(dK), lib.ptr(dV), 128, B, Tq, Tk, lib.ptr(qm), lib.ptr(km),
+                                       lib.ptr(rng_state), rate, site, lib.stream_ptr()))
+    got = _attn_prof(call)
+    assert got == {_attn_fwd_form(Tq, Tk): 1, _attn_bwd_form(Tq, Tk): 1}, got
     Qd, Kd, Vd = (t.double().cpu().requires_grad_(True) for t in (Q, K, V))
     ref = _attn_ref(Qd, Kd, Vd, qm.double().cpu(), km.double().cpu(), B, Tq, Tk, (seed, offset, rate, site) if rate > 0 else None)
     # (6e-6, not 3e-6: an operand element whose residual lies below fp16's normal range - 1.5 % of them - loses it in the matrix pipe:
