@@ -1,5 +1,5 @@
 // One clip of a [B,T] batch as every per-clip span launch opens it (hual_span_topk in topk.hip, hual_span_expected_iou in spanconf.hip,
-// hual_span_hit_prob in spanhit.hip; the contract is in include/hual_seqpan.h): which clips are open, the index of the span triangle,
+// hual_span_hit_prob in spanhit.hip, hual_span_hit_cover in spancover.hip; the contract is in include/hual_seqpan.h): which clips are open, the index of the span triangle,
 // the k <= 16 proposal slots and their stable in-place reorder.  One definition, so all launches classify a clip alike
 // (tests/test_gpu_span_clips.py); the span-posterior launches have theirs in spanpost.h.
 #pragma once

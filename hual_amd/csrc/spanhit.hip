@@ -6,7 +6,7 @@
 // One 1024-thread workgroup per clip, and with the Bayes spans one per (clip, threshold): blockIdx.y = m searches threshold m, and the
 // workgroups with blockIdx.y = 0 also score the proposals.  No workgroup reads what another writes.  The probabilities are those of
 // topk.hip (spanprob.h).  No pair of spans is enumerated: for a candidate (a, b) and a start i of the truth the ends j that hit form one
-// interval [j_lo, j_hi] (the derivation is in front of sh_mass), so a candidate's hit mass is sum_i p_s[i] * (E[j_hi + 1] - E[j_lo]) over
+// interval [j_lo, j_hi] (the derivation is in front of sh_mass, spanmass.h), so a candidate's hit mass is sum_i p_s[i] * (E[j_hi + 1] - E[j_lo]) over
 // the float64 prefix sums E of p_e in LDS - prefix DIFFERENCES, on purpose: their error is a few 2^-53 on values <= 1, far below the
 // float32 result (hual_al_mbr_label avoids them; this kernel need not).  The two integer divisions of the interval ends depend on one
 // length each and come from two tables of 257 entries per threshold, built once per workgroup; the starts i that hit at all are a range
@@ -20,42 +20,11 @@
 #include "common.h"
 #include "prof.h"
 #include "spanclip.h"
+#include "spanmass.h"
 
 using namespace hual;
 
 namespace {
-
-constexpr int SH_MAXM = 4, SH_MAXDEN = 1024;
-constexpr int SH_NONE = 0x7fffffff;      // key of "no candidate" (mass -1: below every real mass, which is >= 0)
-
-struct ShThresholds { int num[SH_MAXM], den[SH_MAXM]; };      // by value: read on the host before the launch
-
-// The starts and ends that hit the candidate (a, b), 0 <= a <= b < v, at threshold num / den: den * inter >= num * union in integers,
-// inter and union of the half-open frame intervals.  num >= 1 asks inter >= 1, so i <= b and j >= max(a, i), and the union is one
-// interval.  With lo = min(a, i), hi = max(a, i):
-//   j <= b: inter = j + 1 - hi, union = b + 1 - lo =: U; a hit iff j >= hi - 1 + ceil(num U / den) =: j_lo   (rising in j)
-//   j >= b: inter = b + 1 - hi =: I, union = j + 1 - lo; a hit iff j <= lo - 1 + floor(den I / num) =: j_hi   (falling in j)
-// The two agree at j = b, so the hits of start i are [j_lo, min(j_hi, v - 1)] when b itself hits (j_lo <= b) and none otherwise.
-//   i <= a: I = n := b + 1 - a is fixed; j_lo <= b iff num (b + 1 - i) <= den n iff i >= b + 1 - fl[n]
-//   i >= a: U = n is fixed;              j_lo <= b iff i <= b + 1 - ce[n]
-// ce[x] = ceil(num x / den), fl[x] = floor(den x / num) (capped at 256: only min(., v - 1) reads it), 1 <= x <= 256; ce[x] <= x <= fl[x].
-
-// this thread's share of the hit mass of (a, b): the starts first, first + step, .. of the hitting range, walked from a outwards
-__device__ __forceinline__ double sh_mass(int a, int b, int v, const float* ps, const double* E, const int* ce, const int* fl, int first,
-                                          int step) {
-  const int n = b + 1 - a, F = fl[n], C = ce[n];
-  const int imin = max(0, b + 1 - F), imax = b + 1 - C;      // imin <= a <= imax <= b
-  double acc = 0.0;
-  for (int i = a - first; i >= imin; i -= step) {            // i <= a: j_lo = a - 1 + ce[b + 1 - i] in [a, b], j_hi = i - 1 + F >= b
-    const int jlo = a - 1 + ce[b + 1 - i], jhi = min(v - 1, i - 1 + F);
-    acc += (double)ps[i] * (E[jhi + 1] - E[jlo]);
-  }
-  for (int i = a + step - first; i <= imax; i += step) {     // i > a: j_lo = i - 1 + C in (a, b], j_hi = a - 1 + fl[b + 1 - i] >= b
-    const int jlo = i - 1 + C, jhi = min(v - 1, a - 1 + fl[b + 1 - i]);
-    acc += (double)ps[i] * (E[jhi + 1] - E[jlo]);
-  }
-  return acc;
-}
 
 __global__ __launch_bounds__(SPAN_THREADS) void span_hit_prob_kernel(const float* __restrict__ zs_, const float* __restrict__ ze_,
                                                                      const int32_t* __restrict__ vlen_, int T, ShThresholds thr, int M, int k,
@@ -79,11 +48,7 @@ __global__ __launch_bounds__(SPAN_THREADS) void span_hit_prob_kernel(const float
       load_slots(slots, b, k, v, start_index, end_index, score);
       if (t < k) for (int m = 0; m < M; ++m) val[t][m] = -1.0f;
     }
-    for (int x = t; x < M * 257; x += SPAN_THREADS) {        // the two division tables of every threshold (entry 0 is never read)
-      const int m = x / 257, n = x - m * 257;
-      ce[m][n] = (thr.num[m] * n + thr.den[m] - 1) / thr.den[m];
-      fl[m][n] = min(256, (thr.den[m] * n) / thr.num[m]);
-    }
+    sh_build_tables(thr.num, thr.den, M, ce, fl);
   });
   const int v = clip.v, *ca = slots.ca, *cb = slots.cb;
   bool live = false;

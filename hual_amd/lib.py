@@ -157,6 +157,7 @@ def load():
     lib.hual_span_topk.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]
     lib.hual_span_expected_iou.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.hual_span_hit_prob.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.hual_span_hit_cover.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, i32, f32, vp, vp, vp, vp]
     lib.hual_linear_dw.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, u64, vp]
     lib.hual_al_score.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
     lib.hual_al_mc_fold.argtypes = [P(hual_al_bank), vp, vp, vp, vp, i32, i32, i32, vp]
@@ -436,6 +437,49 @@ def span_hit_prob(start_logits, end_logits, video_seq_len, thresholds=(0.3, 0.5,
     check(load().hual_span_hit_prob(ptr(s), ptr(e), ptr(vl), B, T, cthr, M, k, ptr(starts), ptr(ends), ptr(score), ptr(out[0]), rb,
                                     ptr(bst[0]), ptr(bst[1]), ptr(bst[2]), stream_ptr()))
     return out[0], (tuple(out[1]) if best else None)
+
+
+def span_hit_cover(start_logits, end_logits, video_seq_len, thresholds=(0.3, 0.5, 0.7), starts=None, ends=None, K=0, min_gain=1e-6, out=None):
+    """coverage P(some span of a set hits the truth at IoU >= m) under the span distribution of start_logits / end_logits f32 [B,T] and
+    video_seq_len [B] for M <= 4 IoU thresholds (hit_thresholds), enqueued on the current stream (hual_span_hit_cover) ->
+    (set_prob, cover): set_prob float32 [B,k,M], column q the coverage of the valid slots among slots 0..q of the proposals starts /
+    ends (int64 [B,k] on the device, k <= 16; -1 = no proposal; only read) - the chance that the clip counts for R@(q+1) - or None
+    without proposals; cover = (cover_start int64 [B,M,K], cover_end int64 [B,M,K], cover_prob float32 [B,M,K]), each threshold's greedy
+    set of K <= 16 spans of the whole triangle, every step the span that adds the most mass not yet covered, with the cumulative
+    coverage after it, or None with K == 0.  The set stops when the best gain is <= min_gain: later slots are -1, -1 and repeat the
+    last coverage.  Empty clips and rows with a NaN logit give -1.  out: (set_prob or None, (cover_start, cover_end, cover_prob) or
+    None) contiguous device tensors of those shapes to write into instead."""
+    import torch
+    who = 'span_hit_cover'
+    _clip_logits(who, start_logits, end_logits)
+    thr = hit_thresholds(thresholds)
+    s, e, vl, B, T = _clip_lengths(who, start_logits, end_logits, video_seq_len)
+    M, K = len(thr), int(K)
+    if (starts is None) != (ends is None):
+        raise HualError(who + ': starts and ends are given together')
+    k = _clip_slots(who, starts, ends, None, B, s.device) if starts is not None else 0
+    if not 0 <= K <= 16:
+        raise HualError(who + ': 0 <= K <= 16, got %d' % K)
+    if not k and not K:
+        raise HualError(who + ': nothing to do (no proposals and K == 0)')
+    if not 0.0 <= float(min_gain) < 1.0:
+        raise HualError(who + ': 0 <= min_gain < 1, got %r' % (min_gain,))
+    if out is None:
+        out = (torch.empty(B, k, M, dtype=torch.float32, device=s.device) if k else None,
+               (torch.empty(B, M, K, dtype=torch.int64, device=s.device), torch.empty(B, M, K, dtype=torch.int64, device=s.device),
+                torch.empty(B, M, K, dtype=torch.float32, device=s.device)) if K else None)
+    else:
+        if len(out) != 2 or (out[0] is None) != (k == 0) or (out[1] is None) != (K == 0) or (K and len(out[1]) != 3):
+            raise HualError(who + ': out is (set_prob [B,k,M] or None, (cover_start, cover_end, cover_prob) [B,M,K] or None)')
+        for o, dt, shape in ((out[0], torch.float32, (B, k, M)),) + (tuple(zip(out[1], (torch.int64, torch.int64, torch.float32), ((B, M, K),) * 3))
+                                                                     if K else ()):
+            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != s.device):
+                raise HualError(who + ': out tensors must be contiguous float32 [B,k,M] and int64, int64, float32 [B,M,K] on the logits\' device')
+    cov = out[1] if K else (None, None, None)
+    cthr = (ctypes.c_int32 * (2 * M))(*[x for nd in thr for x in nd])
+    check(load().hual_span_hit_cover(ptr(s), ptr(e), ptr(vl), B, T, cthr, M, k, ptr(starts), ptr(ends), ptr(out[0]), K, float(min_gain),
+                                     ptr(cov[0]), ptr(cov[1]), ptr(cov[2]), stream_ptr()))
+    return out[0], (tuple(out[1]) if K else None)
 
 
 def al_score(aset, s0, e0, coff_uncert, out, pair=None, bank=None, info=None, K=2, stat='range', uncert_model=None):

@@ -175,15 +175,15 @@ class Runner:
     BAYES_IOUS = (0.3, 0.5, 0.7)      # the thresholds of the reported R@1 (al.iou_metrics): one Bayes span each
 
     def evaluate(self, dataset=None, k=5, nms_iou=0.5, max_len=0, return_proposals=False, weights=None, rerank=None, hit_iou=0.7,
-                 bayes_spans=False):
+                 bayes_spans=False, bayes_sets=False):
         """weights: 'ema' (the default with train.ema_decay) or 'raw'; everything else: _evaluate"""
         if rerank not in (None, 'expected_iou', 'hit_prob'):
             raise ValueError("rerank: None, 'expected_iou' or 'hit_prob'")
         thr = lib.hit_thresholds((hit_iou,)) if rerank == 'hit_prob' else None      # (raises on a threshold the kernel cannot take)
         with self._weights(weights):
-            return self._evaluate(dataset, k, nms_iou, max_len, return_proposals, rerank, hit_iou, thr, bayes_spans)
+            return self._evaluate(dataset, k, nms_iou, max_len, return_proposals, rerank, hit_iou, thr, bayes_spans, bayes_sets)
 
-    def _evaluate(self, dataset, k, nms_iou, max_len, return_proposals, rerank=None, hit_iou=0.7, hit_thr=None, bayes_spans=False):
+    def _evaluate(self, dataset, k, nms_iou, max_len, return_proposals, rerank=None, hit_iou=0.7, hit_thr=None, bayes_spans=False, bayes_sets=False):
         """R1 and R<k> at IoU 0.3 / 0.5 / 0.7 and mIoU (percent) of the k best spans per clip after greedy temporal NMS
         (hual_span_topk).  Batches and ranks as test_epoch; the proposals of all batches collect on the device and come back in one
         transfer.  R1 and mIoU are those of the first proposal, which is the span test_epoch scores.  return_proposals: also a list
@@ -202,7 +202,14 @@ class Runner:
         tuples gain the hit probability as a fourth element.
         bayes_spans=True (with any rerank): one more launch per batch finds, for each of IoU 0.3 / 0.5 / 0.7, the span of maximal hit
         probability over ALL spans of the clip, not only the proposals; the result gains 'R1_bayes@0.3' / '@0.5' / '@0.7', the R@1 of
-        each threshold's own span at that threshold (through al.ious_of_spans), and 'bayes_conf@...', their mean hit probability."""
+        each threshold's own span at that threshold (through al.ious_of_spans), and 'bayes_conf@...', their mean hit probability.
+        bayes_sets=True (with any rerank or bayes_spans): one more launch per batch (hual_span_hit_cover, K = k at IoU 0.3 / 0.5 / 0.7)
+        gives the coverage of the proposals - the chance under the clip's span distribution that at least one of them hits, what R<k>
+        counts - and per threshold the greedy set of k spans over ALL spans of the clip that covers the most.  The result gains
+        'R<k>_bayes@m', the R@k of each threshold's greedy set at that threshold (al.recall_at_k, the rule of 'R<k>@m'),
+        'bayes_set_conf@m', the mean coverage of those sets, 'set_conf@m', the mean coverage of the k proposals scored, and
+        'set_ece@m' / 'set_brier@m', the calibration of that coverage against whether the clip counted for R<k>@m
+        (al.hit_calibration)."""
         ds = dataset or self.test_set
         N, bs, k = len(ds), self.batch_size, int(k)
         mine = [(lo, min(N, lo + bs)) for b, lo in enumerate(range(0, N, bs)) if b % self.world == self.rank]
@@ -215,6 +222,9 @@ class Runner:
         # hit probability [n,k,1] of the one threshold; the Bayes spans: starts | ends (int64) | probabilities (float32), each [n,3]
         hbuf = torch.empty(n, k, 1, dtype=torch.float32, device=dev) if rerank == 'hit_prob' else None
         (bst, ben, bpr), bayes_host = _packed(n, ((torch.int64, 3), (torch.int64, 3), (torch.float32, 3)), dev) if bayes_spans else ((None,) * 3, None)
+        # the sets: greedy starts | ends (int64, [n,3,k]) | their coverage | the proposals' coverage [n,k,3] (float32)
+        (cst, cen, cpr, spr), sets_host = (_packed(n, ((torch.int64, 3 * k), (torch.int64, 3 * k), (torch.float32, 3 * k), (torch.float32, 3 * k)), dev)
+                                           if bayes_sets else ((None,) * 4, None))
         pos = 0
         for lo, hi in mine:
             sel = np.arange(lo, hi)
@@ -232,6 +242,9 @@ class Runner:
             if bayes_spans:
                 lib.span_hit_prob(o['start_logits'], o['end_logits'], f['video_seq_len'], self.BAYES_IOUS, best=True,
                                   out=(None, (bst[rows], ben[rows], bpr[rows])))
+            if bayes_sets:
+                lib.span_hit_cover(o['start_logits'], o['end_logits'], f['video_seq_len'], self.BAYES_IOUS, st[rows], en[rows], K=k,
+                                   out=(spr[rows].view(-1, k, 3), tuple(x[rows].view(-1, 3, k) for x in (cst, cen, cpr))))
             pos += hi - lo
         ids = np.concatenate([np.arange(lo, hi) for lo, hi in mine]) if mine else np.zeros(0, dtype=np.int64)
         part = (ids,) + top_host()
@@ -241,6 +254,8 @@ class Runner:
             part += (hbuf.cpu().numpy().reshape(n, k),)
         if bayes_spans:
             part += bayes_host()
+        if bayes_sets:
+            part += sets_host()
         if self.world > 1:
             parts = hdist.gather_objects(part)
             if self.rank == 0:
@@ -270,7 +285,7 @@ class Runner:
             self.log.info('EVAL re-ranked by hit probability at IoU {:g}:\thit conf {:.4f}\tECE {:.4f}\tBrier {:.4f}'.format(
                 hit_iou, res['hit_conf'], cal['ece'], cal['brier']))
         if bayes_spans:
-            BS, BE, BP = part[-3:]
+            BS, BE, BP = part[-7:-4] if bayes_sets else part[-3:]
             for c, m in enumerate(self.BAYES_IOUS):
                 hit = al.topk_ious(recs, BS[:, c], BE[:, c])[:, 0] >= m      # (a clip without a span - a poisoned row - is a miss)
                 bp = BP[:, c][BP[:, c] >= 0]
@@ -278,6 +293,20 @@ class Runner:
                 res['bayes_conf@%g' % m] = float(np.mean(bp, dtype=np.float64)) if bp.size else float('nan')
             self.log.info('EVAL Bayes spans (maximal hit probability per threshold):\tR1 ' + '\t'.join(
                 '{:.2f}'.format(res['R1_bayes@%g' % m]) for m in self.BAYES_IOUS))
+        if bayes_sets:
+            CS, CE, CP = (x.reshape(len(ids), 3, k) for x in part[-4:-1])
+            SP = part[-1].reshape(len(ids), k, 3)
+            counted = ious.max(axis=1, initial=0.0)                # (the clip counts for R<k>@m iff this is >= m: al.recall_at_k)
+            for c, m in enumerate(self.BAYES_IOUS):
+                cp, sp = CP[:, c, k - 1][CP[:, c, k - 1] >= 0], SP[:, k - 1, c][SP[:, k - 1, c] >= 0]
+                cal = al.hit_calibration(SP[:, k - 1, c], counted >= m)
+                res['R%d_bayes@%g' % (k, m)] = al.recall_at_k(recs, CS[:, c], CE[:, c], thresholds=(m,))[0]
+                res['bayes_set_conf@%g' % m] = float(np.mean(cp, dtype=np.float64)) if cp.size else float('nan')
+                res['set_conf@%g' % m] = float(np.mean(sp, dtype=np.float64)) if sp.size else float('nan')
+                res['set_ece@%g' % m], res['set_brier@%g' % m] = cal['ece'], cal['brier']
+            self.log.info('EVAL Bayes sets (greedy maximal coverage per threshold):\tR{} '.format(k) + '\t'.join(
+                '{:.2f}'.format(res['R%d_bayes@%g' % (k, m)]) for m in self.BAYES_IOUS) + '\tset conf ' + '\t'.join(
+                '{:.4f}'.format(res['set_conf@%g' % m]) for m in self.BAYES_IOUS))
         if not return_proposals:
             return res
         props = [None] * N

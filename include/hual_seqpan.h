@@ -445,6 +445,38 @@ int hual_span_hit_prob(const float* start_logits, const float* end_logits, const
                        const int32_t* thresholds, int M, int k, int64_t* start_index, int64_t* end_index, float* score, float* hit_prob,
                        int reorder_by, int64_t* best_start, int64_t* best_end, float* best_prob, void* stream);
 
+/* coverage of span sets under the clip's own span distribution: the chance that AT LEAST ONE span of a set hits the truth at IoU >= m -
+ * what R@k counts - for the cumulative sets of k proposals, and per threshold the greedy set of K spans of the whole triangle that covers
+ * the most, the sequel of hual_span_hit_prob's Bayes span for R@k (ABI 9 unchanged, a new symbol).  v, p_s, p_e, w(i,j), Z, the
+ * thresholds (HOST (num, den) pairs, by value), the integer hit rule and the float64 arithmetic over prefix differences are exactly
+ * hual_span_hit_prob's.  The coverage of a set S is C(S) = (1/Z) * the sum of w(i,j) over the truths (i,j) that some span of S hits: monotone
+ * and submodular in S, so the greedy set is within 1 - (1 - 1/K)^K of the best set of K spans.
+ * 1 <= T <= 256, 1 <= M <= 4, 0 <= k <= 16, 0 <= K <= 16, k + K >= 1, 0 <= min_gain < 1.
+ *  - set_prob [B, k, M] (float; k >= 1): set_prob[b][q][m] is the coverage at threshold m of the valid slots among slots 0..q of
+ *    (start_index, end_index)[b]; for the proposals of hual_span_topk the chance that the clip counts for R@(q+1).  An invalid slot (an
+ *    index negative, a > b or b >= v) adds nothing; the value is 0.0f while no valid slot has been seen; column 0 of a valid slot is its
+ *    hit_prob (up to the order of one sum).  Each slot adds the mass of the truths it hits that no earlier slot hits, summed over the
+ *    starts in a fixed order; the value is (float)(covered / Z) clamped to [0, 1].  start_index / end_index are only read.  k == 0 skips
+ *    the proposals; start_index, end_index and set_prob may then be NULL.
+ *  - cover_start, cover_end (int64), cover_prob (float), [B, M, K] each, all three (K >= 1) or none (K == 0): per threshold m, with nothing
+ *    covered at the start, step s takes the span of the whole triangle with the largest GAIN - the mass of the truths it hits that no
+ *    earlier pick hits - among equal gains the first in row-major order (smallest a, then smallest b); cover_prob[b][m][s] is the
+ *    cumulative coverage after it, (float)(covered / Z) clamped to [0, 1].  The set stops at the first step whose best gain divided by Z
+ *    is <= min_gain: that and every later slot is -1, -1 with the last cumulative coverage repeated (0.0f if step 0 stopped).  Step 0 is
+ *    hual_span_hit_prob's search itself: with min_gain == 0, cover_*[b][m][0] equal its best_*[b][m] bit for bit.  A launch with a larger
+ *    K extends one with a smaller K: the first columns are equal.  A start's uncovered mass is a difference of prefix differences, clamped
+ *    at >= 0: a span whose truths are all covered has a gain of a few 2^-53 at most, so min_gain == 0 may go on with such spans.
+ *  - an empty clip (v < 1), a NaN logit at t < v or a Z that is not a positive finite number: every set_prob of the row is -1.0f and
+ *    cover_* are -1, -1, -1.0f.  v == 1: the set is (0, 0) with probability exactly 1.0f, then stopped slots.  Logits at t >= v are not
+ *    read.
+ * Float64 throughout, sums in a fixed order, no atomics: a second launch returns equal bits.  Allocates nothing and does not synchronise:
+ * capturable in a hipGraph.  Argument errors (a null pointer among the logits, lengths, thresholds or the arrays of a part that is asked
+ * for; B < 1; T, k, K, M, min_gain or a threshold out of range; k == 0 and K == 0; only some of cover_*) return HUAL_ERR_INVALID before
+ * any HIP call. */
+int hual_span_hit_cover(const float* start_logits, const float* end_logits, const int32_t* video_seq_len, int B, int T,
+                        const int32_t* thresholds, int M, int k, const int64_t* start_index, const int64_t* end_index, float* set_prob,
+                        int K, float min_gain, int64_t* cover_start, int64_t* cover_end, float* cover_prob, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Device-side batch assembly: TrainLoader.process_batch / TestLoader.process_batch
  * (/root/reference/utils/data_loader.py:30-98,145-164) from a training set that stays resident in HBM.
