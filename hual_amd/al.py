@@ -518,6 +518,22 @@ def recall_at_k(records, starts, ends, thresholds=(0.3, 0.5, 0.7)):
     return tuple(float(np.mean(best >= t) * 100.0) for t in thresholds)
 
 
+def frame_hits(idx_a, idx_b, thresholds):
+    """does span a hit span b at IoU >= m? - the integer rule of hual_span_hit_prob and hual_al_hit_label on the host: idx_a / idx_b
+    int [n, 2] frame spans (start, end), thresholds as lib.hit_thresholds takes them -> bool [n, M], den * inter >= num * union on
+    the half-open frame intervals [start, end + 1).  A row with a span that is none (an index < 0 or start > end) is no hit.  What
+    hit_calibration takes beside the launches' probabilities."""
+    a = np.asarray(idx_a, dtype=np.int64).reshape(-1, 2)
+    b = np.asarray(idx_b, dtype=np.int64).reshape(-1, 2)
+    if a.shape != b.shape:
+        raise ValueError('frame_hits: idx_a and idx_b must hold the same number of spans')
+    thr = lib.hit_thresholds(thresholds)
+    ok = (a[:, 0] >= 0) & (a[:, 0] <= a[:, 1]) & (b[:, 0] >= 0) & (b[:, 0] <= b[:, 1])
+    inter = np.maximum(0, np.minimum(a[:, 1], b[:, 1]) + 1 - np.maximum(a[:, 0], b[:, 0]))
+    union = (a[:, 1] - a[:, 0] + 1) + (b[:, 1] - b[:, 0] + 1) - inter
+    return np.stack([ok & (den * inter >= num * union) for num, den in thr], axis=1)
+
+
 def hit_calibration(prob, hit, bins=10):
     """reliability of predicted hit probabilities against what happened: prob (floats in [0, 1]; an entry < 0 - no value, as
     hual_span_hit_prob gives for an invalid slot or a poisoned row - counts out) and hit (truth values of the same shape) ->
@@ -1097,6 +1113,24 @@ class LabelUpdater:
         (new_d, conf, old_conf), _ = self._launch('label', noise, sel=sel_d, old_idx=old_d)
         return new_d.cpu().numpy(), conf.cpu().numpy(), old_conf.cpu().numpy()
 
+    def hit_label(self, sel=None, cand=None, thresholds=(0.3, 0.5, 0.7), best=True, noise=None):
+        """label reliability: P(IoU(span, truth) >= m | the answers) of the spans `cand` (int [N, k, 2], numpy or a device tensor, k <=
+        16; None: none) of the samples `sel` (sample ids, numpy; None: all) under the span posterior given the set's answered active
+        points, at the IoU thresholds `thresholds` (lib.hit_thresholds), and with best=True per threshold the member of the consistent
+        set that maximises it (hual_al_hit_label, one launch) on the updater's set and deterministic logits - of the records or of the
+        bank, as query().  Leaves cand_hit (f32 [N, k, M]; None without cand), hit_best_idx (i32 [N, M, 2]) and hit_best_prob (f32
+        [N, M]; both None with best=False: the launch then does not search) as device tensors; rows outside `sel`, slots that are no
+        span of the clip and rows that give no probability hold -1.
+        noise=eps: the same launch on the rows tilted by eps (tilt()) and the set without answers - every span of the clip is then
+        consistent, and only a poisoned row gives none.  It has no ensemble form."""
+        self._no_ensemble('hit_label()')
+        aset, s, e, _ = self._reads(noise)
+        sel_d = None if sel is None else torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
+        if cand is not None and not torch.is_tensor(cand):
+            cand = torch.from_numpy(np.ascontiguousarray(cand, dtype=np.int32)).to(self.dev)
+        self.cand_hit, found = lib.al_hit_label(aset, s, e, self.tlen_h, thresholds=thresholds, sel=sel_d, cand=cand, best=best)
+        self.hit_best_idx, self.hit_best_prob = found if found is not None else (None, None)
+
     def renew(self, sel, old_idx, coff):
         """sel: sample ids (numpy); old_idx: int [N,2]; returns new_idx int32 [N,2] (valid for the selected rows)"""
         sel_d = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(self.dev)
@@ -1111,25 +1145,31 @@ class LabelUpdater:
 POSTERIOR = ('deterministic', 'ensemble')
 RANK_BY = ('uncert_video', 'span_risk')
 RANK_BY_ENSEMBLE = ('span_bald',)      # with posterior='ensemble' only (check_round)
+RANK_BY_HIT = ('label_miss',)          # label reliability (LabelUpdater.hit_label): the deterministic posterior only
 OBSERVE_BY = ('uncert_frame', 'info_gain')
 RENEW_BY = ('heuristic', 'posterior')
+RENEW_BY_HIT = ('hit_prob',)           # the same
 ACQUIRE_BY = (None, 'label_gain')
 CALIBRATE = (None, 'evidence')
+HIT_IOUS = (0.3, 0.5, 0.7)             # the thresholds of the round's hit_label launches, in column order; hit_iou is one of them
+HIT_MARGIN = 1e-6                      # renew_by='hit_prob' moves a label only for more than this: below it two probabilities are a tie
 
 # check_round's result: the switches of a round as update_labels works from them - the enumerations as given; Q, the questions per
 # clip, an int; stop_entropy, noise and temperature floats or None; flip None or (rate, Generator); reads_posterior: one of the span
-# posterior's readers is on; questions_at_once: M, the frames a selected sample is asked together
+# posterior's readers is on; questions_at_once: M, the frames a selected sample is asked together; hit_iou: the threshold of HIT_IOUS
+# that rank_by='label_miss' and renew_by='hit_prob' decide at
 RoundPolicy = collections.namedtuple('RoundPolicy', 'posterior rank_by observe_by renew_by acquire_by Q stop_entropy noise temperature '
-                                                    'calibrate flip reads_posterior questions_at_once')
+                                                    'calibrate flip reads_posterior questions_at_once hit_iou')
 
 
 def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='uncert_video', observe_by='uncert_frame',
                 renew_by='heuristic', acquire_by=None, soft_out=None, answer_noise=None, annotator_flip=None, questions_per_clip=1,
-                stop_entropy=None, temperature=None, calibrate=None, questions_at_once=1):
+                stop_entropy=None, temperature=None, calibrate=None, questions_at_once=1, hit_iou=0.7):
     """every rule between the switches of update_labels / run_round (their docstrings say what each switch does) -> RoundPolicy;
     raises ValueError, and touches nothing"""
     readers = {"observe_by='info_gain'": observe_by == 'info_gain', "acquire_by='label_gain'": acquire_by == 'label_gain',
-               "renew_by='posterior'": renew_by == 'posterior', 'soft_out': soft_out is not None, "rank_by='span_bald'": rank_by == 'span_bald'}
+               "renew_by='posterior'": renew_by == 'posterior', 'soft_out': soft_out is not None, "rank_by='span_bald'": rank_by == 'span_bald',
+               "rank_by='label_miss'": rank_by == 'label_miss', "renew_by='hit_prob'": renew_by == 'hit_prob'}
 
     def needs_reader(who, but):
         """`who` changes the span posterior, which is idle work unless something reads it: all of `readers` count but the one that
@@ -1158,6 +1198,9 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
             raise ValueError("posterior='ensemble' with questions_per_clip > 1 is not offered: sessions have no ensemble form")
         if calibrate is not None:
             raise ValueError("posterior='ensemble' with calibrate is not offered: the evidence grid has no ensemble form")
+        if rank_by == 'label_miss' or renew_by == 'hit_prob':
+            raise ValueError("posterior='ensemble' with rank_by='label_miss' or renew_by='hit_prob' is not offered: the hit probability "
+                             "of a label has no ensemble form")
         needs_reader("posterior='ensemble'", but="acquire_by='label_gain'")
     # sessions: Q questions per clip, asked by information gain, stopped at stop_entropy bits
     if not number(questions_per_clip, lambda q: not isinstance(q, bool) and int(q) == q and 1 <= int(q) <= lib.AL_SESSION_MAX_Q):
@@ -1203,19 +1246,22 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
             raise ValueError('annotator_flip: None or (rate in [0, 1], numpy.random.Generator)')
         annotator_flip = (float(annotator_flip[0]), annotator_flip[1])
     # ranking and the question: acquire_by decides both
-    if rank_by not in RANK_BY and not (posterior == 'ensemble' and rank_by in RANK_BY_ENSEMBLE):
-        raise ValueError("rank_by: 'uncert_video' or 'span_risk' ('span_bald' with posterior='ensemble')")
+    if rank_by not in RANK_BY + RANK_BY_HIT and not (posterior == 'ensemble' and rank_by in RANK_BY_ENSEMBLE):
+        raise ValueError("rank_by: 'uncert_video', 'span_risk' or 'label_miss' ('span_bald' with posterior='ensemble')")
     if observe_by not in OBSERVE_BY:
         raise ValueError("observe_by: 'uncert_frame' or 'info_gain'")
-    if renew_by not in RENEW_BY:
-        raise ValueError("renew_by: 'heuristic' or 'posterior'")
+    if renew_by not in RENEW_BY + RENEW_BY_HIT:
+        raise ValueError("renew_by: 'heuristic', 'posterior' or 'hit_prob'")
+    if isinstance(hit_iou, bool) or not number(hit_iou, lambda x: float(x) in HIT_IOUS):
+        raise ValueError('hit_iou: one of 0.3, 0.5, 0.7')
     if acquire_by not in ACQUIRE_BY:
         raise ValueError("acquire_by: None or 'label_gain'")
     if acquire_by is not None and (rank_by != RANK_BY[0] or observe_by != OBSERVE_BY[0]):
         raise ValueError("acquire_by='%s' chooses the samples and the frames itself: leave rank_by and observe_by at their defaults"
                          % acquire_by)
     return RoundPolicy(posterior, rank_by, observe_by, renew_by, acquire_by, Q, None if stop_entropy is None else float(stop_entropy), noise,
-                       None if temperature is None else float(temperature), calibrate, annotator_flip, any(readers.values()), M)
+                       None if temperature is None else float(temperature), calibrate, annotator_flip, any(readers.values()), M,
+                       float(hit_iou))
 
 
 def span_risk(last_prop):
@@ -1249,7 +1295,7 @@ def _round_calibrate(up, pol):
     return noise, dbg
 
 
-def _round_choose(up, pol, noise, risk, frames):
+def _round_choose(up, pol, noise, risk, frames, old_idx):
     """whom to ask and where, on the answers of the earlier rounds (before set_active_points) -> (order, the ranking of the samples;
     ask, every sample's frame)"""
     uv, observe = up.uncert_video.cpu().numpy(), up.observe.cpu().numpy()
@@ -1269,6 +1315,13 @@ def _round_choose(up, pol, noise, risk, frames):
             dbg['agree'] = up.agree
     if pol.rank_by == 'span_bald':
         order = np.argsort(-up.span_bald.cpu().numpy(), kind='stable')      # largest first, ties in sample order; rows at -1 last
+    if pol.rank_by == 'label_miss':                              # one candidates-only launch over the whole set: k = 1, no search
+        up.hit_label(cand=np.asarray(old_idx)[:, None, :], thresholds=HIT_IOUS, best=False, noise=noise)
+        old_hit = up.cand_hit.cpu().numpy()[:, 0, :]
+        hit = old_hit[:, HIT_IOUS.index(pol.hit_iou)]
+        miss = np.where(hit < 0, np.float32(-1.0), np.float32(1.0) - hit).astype(np.float32)      # (-1: no span of the clip, or a row without a posterior)
+        order = np.argsort(-miss, kind='stable')                 # the likeliest miss first, ties in sample order; rows at -1 last
+        dbg.update(label_miss=miss, old_hit=old_hit)
     if pol.acquire_by == 'label_gain':
         up.label_gain(frames=frames, noise=noise)
         ask_gain = up.ask_gain.cpu().numpy()
@@ -1348,17 +1401,27 @@ def _round_soft_labels(up, noise, aps, soft_out):
 
 
 def _round_renew(up, pol, noise, sel, old_idx, coff, data_old):
-    """the selected samples' new spans - the reference's renew_label, or the minimum-Bayes-risk label with that renew for the rows
-    that give none - written into data_old as times"""
+    """the selected samples' new spans - the reference's renew_label, or the minimum-Bayes-risk label (under renew_by='hit_prob'
+    replaced by the span of maximal hit probability where that beats it by more than HIT_MARGIN) with that renew for the rows that
+    give none - written into data_old as times"""
     dbg = {}
-    if pol.renew_by == 'posterior':
+    if pol.renew_by in ('posterior', 'hit_prob'):
         new_idx, label_conf, old_conf = up.mbr_label(sel, old_idx, noise=noise)
         by_posterior = np.zeros(len(old_idx), dtype=bool)
         by_posterior[sel] = new_idx[sel, 0] >= 0
+        dbg.update(label_conf=label_conf, old_conf=old_conf, renewed_by_posterior=by_posterior)
+        if pol.renew_by == 'hit_prob':                           # one launch on the selected rows: (old label, MBR label) and the search
+            up.hit_label(sel=sel, cand=np.stack([np.asarray(old_idx), new_idx], axis=1), thresholds=HIT_IOUS, noise=noise)
+            hits, best_idx, best_prob = up.cand_hit.cpu().numpy(), up.hit_best_idx.cpu().numpy(), up.hit_best_prob.cpu().numpy()
+            c = HIT_IOUS.index(pol.hit_iou)
+            # the max-hit span only where it beats the MBR label by more than a tie: once answers shrink the consistent set many
+            # members hit every remaining truth, and the search's pick among them is merely the first in row-major order
+            by_hit = by_posterior & (best_prob[:, c].astype(np.float64) - hits[:, 1, c].astype(np.float64) > HIT_MARGIN)
+            new_idx[by_hit] = best_idx[by_hit, c]
+            dbg.update(old_hit=hits[:, 0], label_hit=hits[:, 1], hit_best_idx=best_idx, hit_best_prob=best_prob, renewed_by_hit=by_hit)
         rest = sel[~by_posterior[sel]]                           # no label: the reference's renew for just those
         if len(rest):
             new_idx[rest] = up.renew(rest, old_idx, coff)[rest]
-        dbg.update(label_conf=label_conf, old_conf=old_conf, renewed_by_posterior=by_posterior)
     else:
         new_idx = up.renew(sel, old_idx, coff)
     for i in sel:
@@ -1376,7 +1439,7 @@ def _round_debug(*parts):
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
                   rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
                   answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None,
-                  posterior='deterministic', questions_at_once=1):
+                  posterior='deterministic', questions_at_once=1, hit_iou=0.7):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -1461,11 +1524,25 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     m + 1 frames, bits), 'n_design' and 'design_stop' (int [N], lib.AL_STOP_REASONS; -1: no design), as the launch left them: a
     sample without a design holds -1 / 0 there.  Under answer_noise the corner of the sessions applies: the kernel stops on the
     float32 h2(q) > 0, so a sample the float64 test lets in may come back with an empty design and gets no question this round.
+    rank_by='label_miss' / renew_by='hit_prob' / hit_iou: label reliability (LabelUpdater.hit_label), both off by default and both
+    readers of the posterior (answer_noise, temperature and calibrate are accepted with them; the ensemble has no form of them).
+    hit_iou is the IoU threshold they decide at, one of 0.3, 0.5, 0.7.  rank_by='label_miss' ranks the samples by the chance that
+    their CURRENT label misses: 1 - P(IoU(old label, truth) >= hit_iou) under the span posterior given the answers of the earlier
+    rounds (one candidates-only launch over the whole set), largest first, the same stable argsort, the same half selected; rows
+    that give no probability (-1) come last; everything else in the round is unchanged.  renew_by='hit_prob' first takes the
+    minimum-Bayes-risk label as renew_by='posterior' does, then one hit_label launch on the selected rows scores the old and that
+    label and searches the consistent set: the new label is the span of maximal hit probability at hit_iou only where its float32
+    probability exceeds the MBR label's by more than 1e-6 (the difference taken in float64) - otherwise the MBR label stays, so the
+    exact ties that are the rule once answers shrink the consistent set move no label; rows without a label take the reference's
+    renew, as under 'posterior'.  It trades expected tIoU for hit probability: a different decision, not a better one.  The debug
+    dict gains 'label_miss' (float32 [N]) and 'old_hit' (float32 [N, 3], columns 0.3 / 0.5 / 0.7) under the ranking, and 'old_hit',
+    'label_hit' (float32 [N, 3]), 'hit_best_idx' (int32 [N, 3, 2]), 'hit_best_prob' (float32 [N, 3]) and 'renewed_by_hit' (bool [N])
+    under the renew, whose 'old_hit' - this round's answers included, rows outside the selection -1 - is the one kept when both are on.
     """
     pol = check_round(posterior=posterior, bank=bank, mc_samples=mc_samples, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by,
                       acquire_by=acquire_by, soft_out=soft_out, answer_noise=answer_noise, annotator_flip=annotator_flip,
                       questions_per_clip=questions_per_clip, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate,
-                      questions_at_once=questions_at_once)
+                      questions_at_once=questions_at_once, hit_iou=hit_iou)
     risk = span_risk(last_prop) if pol.rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -1478,10 +1555,10 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     aps = [[(f, True) for f in r[4]['pos_idx']] + [(f, False) for f in r[4]['neg_idx']] for r in data_old]
     up, scored = _round_score(pol, last_prop, aps, coff, device, bank, mc_samples, mc_stat)
     noise, fitted = _round_calibrate(up, pol)
-    order, ask, chosen = _round_choose(up, pol, noise, risk, return_debug)
-    sel = order[:math.ceil(N / 2)]
     idx = dict(gt_idx=np.array([[_round_half_even_index(t, r[1], int(v)) for t in r[2]] for r, v in zip(data_gt, up.vlen_h)]),
                old_idx=np.array([[_round_half_even_index(t, r[1], int(v)) for t in r[2]] for r, v in zip(data_old, up.vlen_h)]))
+    order, ask, chosen = _round_choose(up, pol, noise, risk, return_debug, idx['old_idx'])
+    sel = order[:math.ceil(N / 2)]
     asked = _round_ask(up, pol, noise, sel, ask, idx['gt_idx'], data_old, aps)
     if soft_out is not None:
         _round_soft_labels(up, noise, aps, soft_out)
@@ -1508,7 +1585,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
               observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
               annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None, posterior='deterministic',
-              rank_by='uncert_video', questions_at_once=1):
+              rank_by='uncert_video', questions_at_once=1, hit_iou=0.7):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -1538,6 +1615,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     McBank.for_dataset(dataset, passes=K) once, hand it with mc_samples=K to a first round under the default posterior (or to
     infer_trainset), which fills it, and to every later round with posterior='ensemble'; without a filled bank that keeps its passes
     the call raises ValueError before anything is touched.
+    rank_by='label_miss' / renew_by='hit_prob' / hit_iou: rank the samples by the chance that their current label misses at IoU
+    hit_iou, and renew by the span of maximal hit probability where it beats the minimum-Bayes-risk label (update_labels).
     soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
     blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
     DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
@@ -1562,7 +1641,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     prev = bank if bank is not None and bank.K >= (1 if posterior == 'ensemble' else 2) else None
     switches = dict(posterior=posterior, bank=prev, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
                     soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip, questions_per_clip=questions_per_clip,
-                    stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate, questions_at_once=questions_at_once)
+                    stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate, questions_at_once=questions_at_once,
+                    hit_iou=hit_iou)
     pol = check_round(**switches)                                # (on every rank, before rank 0 goes its own way)
     want_debug = pol.Q > 1 or pol.questions_at_once > 1 or calibrate is not None
     new_data = sessions = designs = calibration = None

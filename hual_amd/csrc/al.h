@@ -77,6 +77,19 @@ struct AlLabelArgs {
   float *conf, *old_conf;                     // [N]
 };
 
+// hual_al_hit_label (spanhitlabel.hip): the hit probability of given spans under the answered-point posterior, and per IoU threshold
+// the member of the consistent set of maximal hit probability
+struct AlHitArgs {
+  AlSpanIn in;
+  const int32_t* sel;                         // [nsel] sample ids (NULL: all)
+  int num[4], den[4];                         // the thresholds, read on the host before the launch
+  int M, k;                                   // 1..4 thresholds | 0..16 candidate slots per sample
+  const int32_t* cand_idx;                    // [N, k, 2] (NULL with k == 0)
+  float* cand_hit;                            // [N, k, M] (rows of unselected samples are left untouched, as best_idx and best_prob)
+  int32_t* best_idx;                          // [N, M, 2] (NULL with best_prob: no search)
+  float* best_prob;                           // [N, M]
+};
+
 // hual_al_label_gain (spangain.hip): per frame, the tIoU the label of hual_al_mbr_label is expected to gain from the frame's answer
 struct AlGainArgs {
   AlSpanIn in;
@@ -141,6 +154,7 @@ int launch_al_score(const AlScoreArgs& a, AlSource src, hipStream_t s);
 int launch_al_span_marginals(const AlMargArgs& a, hipStream_t s);
 int launch_al_label_gain(const AlGainArgs& a, int nsel, hipStream_t s);
 int launch_al_mbr_label(const AlLabelArgs& a, int nsel, hipStream_t s);
+int launch_al_hit_label(const AlHitArgs& a, int nsel, hipStream_t s);
 int launch_al_query(const AlQueryArgs& a, hipStream_t s);
 int launch_al_session(const AlSessionArgs& a, int nsel, hipStream_t s);
 int launch_al_design(const AlDesignArgs& a, int nsel, hipStream_t s);

@@ -1,5 +1,6 @@
 // The hit mass of a span at an exact rational IoU threshold, as hual_span_hit_prob (spanhit.hip) and hual_span_hit_cover (spancover.hip)
-// take it: the thresholds passed by value, the two division tables, the interval of hitting ends per start and the sum over the starts.
+// take it, and hual_al_hit_label (spanhitlabel.hip) within a consistent set: the thresholds passed by value, the two division tables,
+// the interval of hitting ends per start and the sum over the starts.
 // One definition, so the first step of the cover search is the Bayes search of spanhit.hip instruction for instruction (as spanstep.h
 // is shared by the query and the session kernels).
 #pragma once
@@ -43,6 +44,26 @@ __device__ __forceinline__ double sh_mass(int a, int b, int v, const float* ps, 
   for (int i = a + step - first; i <= imax; i += step) {     // i > a: j_lo = i - 1 + C in (a, b], j_hi = a - 1 + fl[b + 1 - i] >= b
     const int jlo = i - 1 + C, jhi = min(v - 1, a - 1 + fl[b + 1 - i]);
     acc += (double)ps[i] * (E[jhi + 1] - E[jlo]);
+  }
+  return acc;
+}
+
+// sh_mass over the truths of a consistent set A (hual_al_hit_label, spanhitlabel.hip): per start i the ends with (i, j) in A are one
+// interval [elo[i], ehi[i]] (elo > ehi: i starts no member), and the hitting ends of that start are sh_mass's interval clamped to it.
+// The same starts in the same order, from a outwards: with elo[i] = i and ehi[i] = v - 1 - no active point - no clamp binds, no term
+// is skipped and the sum is sh_mass's double.
+__device__ __forceinline__ double sh_mass_within(int a, int b, int v, const float* ps, const double* E, const int* ce, const int* fl,
+                                                 const int* elo, const int* ehi, int first, int step) {
+  const int n = b + 1 - a, F = fl[n], C = ce[n];
+  const int imin = max(0, b + 1 - F), imax = b + 1 - C;
+  double acc = 0.0;
+  for (int i = a - first; i >= imin; i -= step) {
+    const int jlo = max(a - 1 + ce[b + 1 - i], elo[i]), jhi = min(min(v - 1, i - 1 + F), ehi[i]);
+    if (jhi >= jlo) acc += (double)ps[i] * (E[jhi + 1] - E[jlo]);
+  }
+  for (int i = a + step - first; i <= imax; i += step) {
+    const int jlo = max(i - 1 + C, elo[i]), jhi = min(min(v - 1, a - 1 + fl[b + 1 - i]), ehi[i]);
+    if (jhi >= jlo) acc += (double)ps[i] * (E[jhi + 1] - E[jlo]);
   }
   return acc;
 }

@@ -168,6 +168,7 @@ def load():
     lib.hual_al_query.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_al_mbr_label.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_al_label_gain.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    lib.hual_al_hit_label.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp]
     lib.hual_assemble_batch.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_carry.argtypes = [P(hual_dataset), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.hual_al_span_marginals.argtypes = [P(hual_al_set), vp, vp, vp, vp, vp, vp]
@@ -650,6 +651,45 @@ def al_mbr_label(aset, s0, e0, tlen, sel=None, old_idx=None, out=None):
     (-1 in tensors allocated here, the value of a row that gives no label)."""
     N, ld, dev = _span_inputs('al_mbr_label', aset, s0, e0, tlen)
     return _label('al_mbr_label', 'hual_al_mbr_label', (aset, s0, e0), N, dev, sel, old_idx, out)
+
+
+AL_HIT_MAX_CAND = 16        # candidate spans per sample of hual_al_hit_label
+
+
+def al_hit_label(aset, s0, e0, tlen, thresholds=(0.3, 0.5, 0.7), sel=None, cand=None, best=True, out=None):
+    """label reliability: the hit probability P(IoU(span, truth) >= m | the answers) of spans under the span posterior of the selected
+    samples of the hual_al_set `aset` given the answered active points, for M <= 4 IoU thresholds (hit_thresholds), and per threshold
+    the member of the consistent set that maximises it (hual_al_hit_label), one launch enqueued on the current stream.  s0 / e0: the
+    deterministic logits f32 [N, ld] on the device; tlen: the set's row lengths on the HOST - a row above AL_QUERY_MAX_T frames is
+    refused here, before the launch, as in al_mbr_label; sel: device i32 [nsel] sample ids (None: all); cand: device i32 [N, k, 2],
+    1 <= k <= 16, the spans to score - members of the consistent set or not; a slot that is no span of the clip gives -1 (None: none).
+    -> (cand_hit f32 [N, k, M] or None without cand, (best_idx i32 [N, M, 2], best_prob f32 [N, M]) with best=True, else None - the
+    launch then does not search).  out: such a pair of contiguous device tensors to write into instead.  Only the entries of selected
+    samples are written: the others keep what they held (-1 in tensors allocated here, the value of a row that gives no probability)."""
+    import torch
+    who = 'al_hit_label'
+    N, ld, dev = _span_inputs(who, aset, s0, e0, tlen)
+    thr = hit_thresholds(thresholds)
+    M = len(thr)
+    nsel = _span_sel(who, sel, N, dev)
+    _span_index(who, 'cand', cand, (N, range(1, AL_HIT_MAX_CAND + 1), 2), dev, text='[N, k, 2], 1 <= k <= %d,' % AL_HIT_MAX_CAND)
+    k = 0 if cand is None else int(cand.shape[1])
+    if not k and not best:
+        raise HualError(who + ': nothing to do (no candidates and best=False)')
+    if out is None:
+        out = (torch.full((N, k, M), -1.0, dtype=torch.float32, device=dev) if k else None,
+               (torch.full((N, M, 2), -1, dtype=torch.int32, device=dev), torch.full((N, M), -1.0, dtype=torch.float32, device=dev)) if best else None)
+    else:
+        if len(out) != 2 or (out[0] is None) != (k == 0) or (out[1] is None) != (not best) or (best and len(out[1]) != 2):
+            raise HualError(who + ': out is (cand_hit [N,k,M] or None, (best_idx [N,M,2], best_prob [N,M]) or None)')
+        for o, dt, shape in ((out[0], torch.float32, (N, k, M)),) + (tuple(zip(out[1], (torch.int32, torch.float32), ((N, M, 2), (N, M))))
+                                                                     if best else ()):
+            if o is not None and (o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev):
+                raise HualError(who + ': out tensors must be contiguous float32 [N,k,M] and int32 [N,M,2], float32 [N,M] on the logits\' device')
+    bst = out[1] if best else (None, None)
+    cthr = (ctypes.c_int32 * (2 * M))(*[x for nd in thr for x in nd])
+    _launch('hual_al_hit_label', aset, s0, e0, sel, nsel, cthr, M, cand, k, out[0], bst[0], bst[1])
+    return out[0], (tuple(out[1]) if best else None)
 
 
 def _label_gain(who, entry, head, N, ld, dev, sel, cand, frames, out):

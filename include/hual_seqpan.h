@@ -1004,6 +1004,35 @@ int hual_al_ensemble_label(const hual_al_set* set, const float* pass_s, const fl
                            int nsel, const int32_t* old_idx, int32_t* new_idx, float* conf, float* old_conf, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Label reliability: the hit probability of pseudo-labels under the answered-point posterior (HUAL_ABI_VERSION unchanged: one new
+ * symbol, nothing else moved).  hual_al_mbr_label's conf is an expected tIoU - a mean, which no yes/no outcome can check.  This launch
+ * gives P(IoU(span, truth) >= m | the answers), hual_span_hit_prob's quantity with the truth drawn from hual_al_query's posterior: the
+ * one confidence of a label that labelled data can check with a reliability curve (al.hit_calibration).  T, v, p_s, p_e, w(i,j) =
+ * (double)p_s[i] * (double)p_e[j], the ignored active points, the consistent set A, Z_A and the poisoned / contradictory / collapsed
+ * rules are hual_al_query's, word for word; sel / nsel are hual_al_mbr_label's (NULL: all N; an id outside [0, N) writes nothing; only
+ * the entries of selected samples are written); thresholds / M are hual_span_hit_prob's: HOST int32 [M][2] = (num, den), 1 <= num <=
+ * den <= 1024, 1 <= M <= 4, passed by value, the hit test den * inter >= num * union in integers on the half-open frame intervals.
+ *  - cand_idx i32 [N, k, 2], cand_hit f32 [N, k, M], 0 <= k <= 16: for the candidate (a, b), a member of A or not, the sum of w over
+ *    the truths (i, j) IN A that hit it, divided by Z_A, accumulated in float64, clamped to [0, 1].  A slot that is no span of the clip
+ *    (a < 0, a > b or b >= v) holds -1.0f in all M columns.  k == 0: both arrays may be NULL.
+ *  - best_idx i32 [N, M, 2], best_prob f32 [N, M], both or neither: per threshold the member of A with the largest hit mass in the
+ *    kernel's float64 arithmetic, among equal masses the first in row-major order (smallest a, then smallest b), and its probability.
+ *    Once answers shrink A, many members hit every remaining truth and tie exactly: a caller that moves a label to this span should
+ *    ask for a margin over the label it holds (al.update_labels(renew_by='hit_prob') asks for 1e-6).
+ *  - a poisoned or contradictory row: -1.0f in cand_hit and best_prob, (-1, -1) in best_idx.  A collapsed posterior (one span left in
+ *    A) is not an error: the best span is that span, with probability 1.0f.
+ * Arithmetic: as hual_span_hit_prob - per start i of the truth the hitting ends are one interval, clamped here to the interval of
+ * ends A allows that start, and summed as a DIFFERENCE of float64 prefix sums of p_e; the starts are taken in that launch's order, so
+ * on a row without active points the masses are its doubles, and the results differ from its results only by the divisor (Z_A and
+ * its Z are two float64 sums of the same terms in different orders: at most one float32 ulp).  One 1024-thread workgroup per
+ * selected sample, with best_* one per (sample, threshold); a launch without best_* does not search.  No atomics, nothing grid wide:
+ * a second launch returns equal bits.  Allocates nothing and does not synchronise: capturable in a hipGraph.  Argument errors (a null
+ * pointer among set, s0, e0, thresholds or the arrays of a part that is asked for; only one of best_*; k == 0 without best_*; nsel <
+ * 1; N < 1; ld outside [2, 1024]; k, M or a threshold out of range) return HUAL_ERR_INVALID before any HIP call. */
+int hual_al_hit_label(const hual_al_set* set, const float* s0, const float* e0, const int32_t* sel, int nsel, const int32_t* thresholds,
+                      int M, const int32_t* cand_idx, int k, float* cand_hit, int32_t* best_idx, float* best_prob, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
