@@ -17,13 +17,14 @@ DROP, SEED, OFFSET = 0.2, 5, 7
 
 
 class Block:
-    """a model + one batch + everything a block call needs"""
+    """a model + one batch + everything a block call needs.  drop: the dropout rate of the calls and of the oracle's masks;
+    case: a (cfg, p, wv, b, labels) of the caller's own making instead of pu.make_case(**shape)"""
 
-    def __init__(self, **shape):
+    def __init__(self, drop=DROP, case=None, **shape):
         from hual_amd import lib
         self.lib = lib
         self.l = lib.load()
-        self.cfg, self.p, self.wv, self.b, self.labels = pu.make_case(**shape)
+        self.cfg, self.p, self.wv, self.b, self.labels = case if case is not None else pu.make_case(**shape)
         b = self.b
         self.B, self.T = b['video'].shape[:2]
         self.L = b['word_ids'].shape[1]
@@ -34,9 +35,10 @@ class Block:
         self.m.set_rng(SEED, OFFSET)
         self.bt, self.keep, _ = self.m._prep(b['video'].numpy(), b['lens'].numpy(), b['word_ids'].numpy(), b['char_ids'].numpy())
         self.ws = self.m._workspace(self.B, self.T, self.L, self.C)
-        self.opts = self.m._opts(DROP)
+        self.drop = drop
+        self.opts = self.m._opts(drop)
         self.dev = self.m.device
-        self.rng = px.DropoutRNG(SEED, OFFSET, DROP)
+        self.rng = px.DropoutRNG(SEED, OFFSET, drop)
         self.rows_v = np.arange(self.Nv)
         self.rows_q = self.Nv + np.arange(self.Nq)
         self.v_mask = (torch.arange(self.T).unsqueeze(0) < b['lens'].long().unsqueeze(1)).to(torch.int32)
