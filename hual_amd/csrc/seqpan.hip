@@ -1512,6 +1512,13 @@ int hual_video_proj_ln_fwd(const hual_cfg* cfg, const float* params, const float
   return run_block(cfg, params, word_table, batch, opts, nullptr, workspace, ws_bytes, stream, ST_INPUT, 0, false, {},
                    {BlkCopy{"cb.x0", nullptr, x0, 0, R}}, nullptr);
 }
+int hual_input_bwd(const hual_cfg* cfg, const float* params, const float* word_table, const hual_batch* batch,
+                   const hual_run_opts* opts, const float* d_x0, float* grads, void* workspace, uint64_t ws_bytes, void* stream) {
+  HUAL_REQUIRE(cfg && batch && d_x0, "hual_input_bwd: null argument");
+  const size_t R = (size_t)batch->B * (batch->T + batch->L);
+  return run_block(cfg, params, word_table, batch, opts, grads, workspace, ws_bytes, stream, ST_INPUT, 0, true,
+                   {BlkCopy{"d.cb.x0", d_x0, nullptr, 0, R}}, {}, nullptr);
+}
 
 int hual_conv_block_fwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const float* x,
                         float* y, void* workspace, uint64_t ws_bytes, void* stream) {

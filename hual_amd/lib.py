@@ -135,6 +135,7 @@ def load():
     lib.hual_align_loss_rows.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp]
     blk = [P(hual_cfg), vp, P(hual_batch), P(hual_run_opts)]
     lib.hual_video_proj_ln_fwd.argtypes = [P(hual_cfg), vp, vp, P(hual_batch), P(hual_run_opts), vp, vp, u64, vp]
+    lib.hual_input_bwd.argtypes = [P(hual_cfg), vp, vp, P(hual_batch), P(hual_run_opts), vp, vp, vp, u64, vp]
     lib.hual_conv_block_fwd.argtypes = blk + [vp, vp, vp, u64, vp]
     lib.hual_conv_block_bwd.argtypes = blk + [vp, vp, vp, vp, u64, vp]
     lib.hual_dual_attn_fwd.argtypes = blk + [i32, vp, vp, vp, u64, vp]

@@ -286,6 +286,11 @@ int hual_align_loss_rows(const float* that, const float* vhat, int ld, int Bg, i
  * -> x0 [B*(T+L),128] */
 int hual_video_proj_ln_fwd(const hual_cfg* cfg, const float* params, const float* word_table, const hual_batch* batch,
                            const hual_run_opts* opts, float* x0, void* workspace, uint64_t ws_bytes, void* stream);
+/* its backward (HUAL_ABI_VERSION unchanged: a new symbol, nothing else moved): d_x0 [B*(T+L),128] = the gradient wrt x0.  Nothing is
+ * returned but `grads`: the position table, the two input layer norms, video_conv1d / query_conv1d, the char CNN's filters and biases,
+ * the char table, the unk row and - cfg->finetune_word_emb - the word table.  word_table as in the forward call */
+int hual_input_bwd(const hual_cfg* cfg, const float* params, const float* word_table, const hual_batch* batch,
+                   const hual_run_opts* opts, const float* d_x0, float* grads, void* workspace, uint64_t ws_bytes, void* stream);
 /* modules.py:59-70 conv_block (shared weights, video and query rows in one pass): y = conv_block(x) */
 int hual_conv_block_fwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const float* x,
                         float* y, void* workspace, uint64_t ws_bytes, void* stream);
