@@ -136,6 +136,17 @@ int hual_span_argmax(const float* start_logits, const float* end_logits, const f
   return launch_heads(a, B, T, (hipStream_t)stream);
 }
 
+int hual_localizing_loss(const float* start_logits, const float* end_logits, const float* vmask, const float* y1, const float* y2,
+                         float* ds, float* de, float* loc_part, int64_t* start_index, int64_t* end_index, int B, int T, void* stream) {
+  HUAL_REQUIRE(start_logits && end_logits && vmask && y1 && y2 && ds && de && loc_part && start_index && end_index && B > 0 && T > 0,
+               "hual_localizing_loss: null / empty");
+  HeadsArgs a{};
+  a.logit[0] = const_cast<float*>(start_logits); a.logit[1] = const_cast<float*>(end_logits); a.vmask = vmask;
+  a.y1 = y1; a.y2 = y2; a.ds = ds; a.de = de; a.loc_part = loc_part;
+  a.start_index = start_index; a.end_index = end_index; a.inv_batch = 1.0f / (float)B;
+  return launch_heads(a, B, T, (hipStream_t)stream);
+}
+
 int hual_adamw_clip_step_ema(float* params, const float* grads, float* adam_m, float* adam_v, const float* decay,
                              uint64_t n_padded, const float* lr, float clip_norm, float grad_prescale, float* sqnorm,
                              uint32_t* rng_state, int64_t* cursor, const int64_t* spans, int64_t* bank, int span_words, int sel_inc,

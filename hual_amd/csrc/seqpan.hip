@@ -819,12 +819,21 @@ float* fwd_fe(Ctx& c, int ps, float* fin) {
   return b.out;
 }
 
+// ---------------- the loss tail: matching-loss denominator and the four reported terms, from the partial sums of the matching head and the heads
+int close_loss(Ctx& c, const CoreBufs& k, const FuseBufs& fu, const HeadBufs& b, const hual_outputs* out, const hual_run_opts* opt) {
+  LossTailArgs lt{k.loss_acc, fu.match_part, match_fwd_blocks(c.rs.Nv), b.loc_part, c.B, c.cfg->match_lambda, opt->match_denom_override,
+                  opt->match_denom_dev, out->loss_terms, k.ovf, c.novf, opt->align_external ? nullptr : fu.align_rows, c.B};
+  return launch_loss_tail(lt, c.stream);
+}
+
 // ---------------- the two heads on the encoder outputs feo[0] (start) / feo[1] (end) and the loss tail
 void fwd_heads(Ctx& c, const CoreBufs& k, const FuseBufs& fu, float* const feo[2], const hual_labels* lab, const hual_outputs* out,
                const hual_run_opts* opt) {
   const ParamMap& pm = c.pm;
   const int D = HUAL_D, Nv = c.rs.Nv, B = c.B;
   const HeadBufs b = head_bufs(Res{c, true});
+  // a labelled fuse block (hual_fuse_fwd) closes the loss as the whole model does below, on the loc.part its caller supplied
+  if (!c.dry && c.ok() && c.sel_stage == ST_FUSE && lab && !opt->deferred_loss_terms) c.chk(close_loss(c, k, fu, b, out, opt));
   if (!c.live()) return;
   // start / end layer norm + hidden layer ([LN(feats), outputs] . W + b, relu) (modules.py:152-157): one launch
   LnProjArgs lp2[2];
@@ -853,11 +862,7 @@ void fwd_heads(Ctx& c, const CoreBufs& k, const FuseBufs& fu, float* const feo[2
   ha.loc_part = b.loc_part; ha.inv_batch = 1.0f / (float)B;
   if (!lab && c.novf) { ha.ovf = k.ovf; ha.novf = c.novf; }
   c.chk(launch_heads(ha, B, c.T, c.stream));
-  if (lab && c.ok() && !opt->deferred_loss_terms) {      // (deferred: match_bwd_kernel closes the loss, bwd_fuse)
-    LossTailArgs lt{k.loss_acc, fu.match_part, match_fwd_blocks(Nv), b.loc_part, B, c.cfg->match_lambda, opt->match_denom_override,
-                    opt->match_denom_dev, out->loss_terms, k.ovf, c.novf, opt->align_external ? nullptr : fu.align_rows, B};
-    c.chk(launch_loss_tail(lt, c.stream));
-  }
+  if (lab && c.ok() && !opt->deferred_loss_terms) c.chk(close_loss(c, k, fu, b, out, opt));      // (deferred: match_bwd_kernel closes the loss, bwd_fuse)
 }
 
 int forward_graph(Ctx& c, const hual_batch* bt, const hual_labels* lab, const hual_outputs* out, const hual_run_opts* opt) {
@@ -976,6 +981,7 @@ float* bwd_fuse(Ctx& c, const CoreBufs& k, const FuseBufs& f, const HeadBufs& hd
   const ParamMap& pm = c.pm;
   const int D = HUAL_D, Nv = c.rs.Nv, B = c.B;
   c.stage(ST_FUSE);
+  const bool whole = c.sel_stage < 0 || (c.sel_stage == ST_FUSE && lab);      // a labelled fuse block (hual_fuse_bwd) runs what the model runs
   float* d_fuse = c.actv("d.fuse");
   float* match_part_b = c.buf("part." + std::to_string(c.part_seq++), (size_t)match_bwd_blocks(Nv) * 9, D);
   ColsumJob cj{};
@@ -991,7 +997,7 @@ float* bwd_fuse(Ctx& c, const CoreBufs& k, const FuseBufs& f, const HeadBufs& hd
     mb.lambda = c.cfg->match_lambda;
     mb.dE_ortho = k.ortho_dE;
     mb.part = match_part_b;
-    if (opt->deferred_loss_terms && c.sel_stage < 0) {      // the forward left the loss open (hual_run_opts.deferred_loss_terms)
+    if (opt->deferred_loss_terms && whole) {      // the forward left the loss open (hual_run_opts.deferred_loss_terms)
       mb.do_tail = 1;
       mb.tail = LossTailArgs{k.loss_acc, f.match_part, match_fwd_blocks(Nv), hd.loc_part, B, c.cfg->match_lambda,
                              opt->match_denom_override, opt->match_denom_dev, opt->deferred_loss_terms, k.ovf, c.novf,
@@ -1011,7 +1017,7 @@ float* bwd_fuse(Ctx& c, const CoreBufs& k, const FuseBufs& f, const HeadBufs& hd
   float* d_pw = c.buf("d.pool.pw", B, D);
   if (c.live()) {
     AlignPoolBwd ab{f.d_that, f.d_vhat, d_cqf, d_cqf, nullptr, nullptr, 0};     // writes the query rows, accumulates the video rows
-    if (!opt->align_external && c.sel_stage < 0) {      // column part of d vhat: from the similarity scratch of the forward
+    if (!opt->align_external && whole) {      // column part of d vhat: from the similarity scratch of the forward
       ab.col_dq = f.align_scratch; ab.col_da = f.align_scratch + (size_t)B * B; ab.col_Bg = B;
     }
     PoolBwd pb{d_fuse, d_pw, d_cqf, c.g(pm.pool_w)};    // accumulates into the query rows
@@ -1462,7 +1468,8 @@ struct BlkCopy { std::string name; const float* src; float* dst; size_t row0, ro
 
 int run_block(const hual_cfg* cfg, const float* params, const float* word_table, const hual_batch* batch, const hual_run_opts* opts,
               float* grads, void* workspace, uint64_t ws_bytes, void* stream, int stage, int sub, bool backward,
-              const std::vector<BlkCopy>& pre, const std::vector<BlkCopy>& post, const hual_outputs* out, const float** sum2_out = nullptr) {
+              const std::vector<BlkCopy>& pre, const std::vector<BlkCopy>& post, const hual_outputs* out, const float** sum2_out = nullptr,
+              const hual_labels* labels = nullptr) {
   int rc = check_common(cfg, params, batch, opts, workspace);
   if (rc) return rc;
   HUAL_REQUIRE(!backward || (grads != nullptr && ((uintptr_t)grads & 15) == 0), "null/unaligned grads");
@@ -1484,7 +1491,7 @@ int run_block(const hual_cfg* cfg, const float* params, const float* word_table,
     HUAL_CHECK_HIP(hipMemcpyAsync(ptr, k.src, k.rows * cols * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
   }
   hual_outputs dummy{};
-  rc = backward ? backward_graph(c, batch, nullptr, opts) : forward_graph(c, batch, nullptr, out ? out : &dummy, opts);
+  rc = backward ? backward_graph(c, batch, labels, opts) : forward_graph(c, batch, labels, out ? out : &dummy, opts);
   if (rc) return rc;
   for (const BlkCopy& k : post) {
     float* ptr; size_t cols;
@@ -1563,6 +1570,31 @@ int hual_cq_attn_bwd(const hual_cfg* cfg, const float* params, const hual_batch*
   const size_t R = (size_t)batch->B * (batch->T + batch->L);
   return run_block(cfg, params, nullptr, batch, opts, grads, workspace, ws_bytes, stream, ST_CQ, 0, true,
                    {BlkCopy{"d.cq.feats", dfeats, nullptr, 0, R}}, {BlkCopy{"d.cq.x", nullptr, dx, 0, R}}, nullptr);
+}
+
+int hual_fuse_fwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const hual_labels* labels,
+                  const float* feats, const float* loc_part, float* outputs, float* match_scores, float* loss_terms, void* workspace,
+                  uint64_t ws_bytes, void* stream) {
+  HUAL_REQUIRE(cfg && batch && opts && feats && outputs && match_scores, "hual_fuse_fwd: null argument");
+  if (labels) HUAL_REQUIRE(labels->match_labels && labels->inner_labels && loc_part, "hual_fuse_fwd: labels need match_labels, inner_labels and loc_part");
+  const size_t R = (size_t)batch->B * (batch->T + batch->L), Nv = (size_t)batch->B * batch->T;
+  hual_outputs o{};
+  o.match_scores = match_scores; o.loss_terms = labels ? loss_terms : nullptr;
+  std::vector<BlkCopy> pre{BlkCopy{"cq.feats", feats, nullptr, 0, R}};
+  if (labels) pre.push_back(BlkCopy{"loc.part", loc_part, nullptr, 0, (size_t)batch->B});
+  return run_block(cfg, params, nullptr, batch, opts, nullptr, workspace, ws_bytes, stream, ST_FUSE, 0, false, pre,
+                   {BlkCopy{"outputs", nullptr, outputs, 0, Nv}}, &o, nullptr, labels);
+}
+int hual_fuse_bwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const hual_labels* labels,
+                  const float* d_outputs, const float* d_outputs_heads, float* d_feats, float* grads, void* workspace, uint64_t ws_bytes,
+                  void* stream) {
+  HUAL_REQUIRE(cfg && batch && opts && d_outputs && d_outputs_heads && d_feats, "hual_fuse_bwd: null argument");
+  // (without labels the alignment buffers of the forward were never written: their backward would read the workspace's leftovers)
+  HUAL_REQUIRE(labels && labels->match_labels && labels->inner_labels, "hual_fuse_bwd: needs the labels of the forward call");
+  const size_t R = (size_t)batch->B * (batch->T + batch->L), Nv = (size_t)batch->B * batch->T;
+  return run_block(cfg, params, nullptr, batch, opts, grads, workspace, ws_bytes, stream, ST_FUSE, 0, true,
+                   {BlkCopy{"d.fe0.x0", d_outputs, nullptr, 0, Nv}, BlkCopy{"d.outputs.heads", d_outputs_heads, nullptr, 0, Nv}},
+                   {BlkCopy{"d.cq.feats", nullptr, d_feats, 0, R}}, nullptr, nullptr, labels);
 }
 
 int hual_predictor_fwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const float* outputs,

@@ -142,6 +142,9 @@ def load():
     lib.hual_dual_attn_bwd.argtypes = blk + [i32, vp, vp, vp, vp, u64, vp]
     lib.hual_cq_attn_fwd.argtypes = blk + [vp, vp, vp, u64, vp]
     lib.hual_cq_attn_bwd.argtypes = blk + [vp, vp, vp, vp, u64, vp]
+    lib.hual_fuse_fwd.argtypes = blk + [P(hual_labels), vp, vp, vp, vp, vp, vp, u64, vp]
+    lib.hual_fuse_bwd.argtypes = blk + [P(hual_labels), vp, vp, vp, vp, vp, u64, vp]
+    lib.hual_localizing_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     lib.hual_predictor_fwd.argtypes = blk + [vp, vp, vp, vp, vp, vp, u64, vp]
     lib.hual_predictor_bwd.argtypes = blk + [vp, vp, vp, vp, vp, u64, vp]
     lib.hual_prof_get.argtypes = [i32, ctypes.c_char_p, i32, P(ctypes.c_int64), P(ctypes.c_double), P(ctypes.c_double),

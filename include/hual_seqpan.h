@@ -308,6 +308,25 @@ int hual_cq_attn_fwd(const hual_cfg* cfg, const float* params, const hual_batch*
                      float* feats, void* workspace, uint64_t ws_bytes, void* stream);
 int hual_cq_attn_bwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const float* dfeats,
                      float* dx, float* grads, void* workspace, uint64_t ws_bytes, void* stream);
+/* the fuse stage and the close of the loss (HUAL_ABI_VERSION unchanged: new symbols, nothing else moved): layers.py:145-154 cq_concat,
+ * model.py:82-97 matching head + label embeddings, model.py:76 / layers.py:205-248 alignment loss, on feats [B*(T+L),128] = what
+ * hual_cq_attn_fwd returns -> outputs [B*T,128] (masked, the predictor's input) and match_scores [B*T,4].
+ *  - labels NULL: the inference form (no alignment pooling, no loss; loc_part and loss_terms are not read / written).
+ *  - labels given (match_labels and inner_labels are read; y1 / y2 are not): loc_part [B] (device) = the per-clip terms of the localizing
+ *    loss as the heads launch leaves them (hual_localizing_loss); loss_terms float[4] (device) = {total, loc, match, align} as the whole
+ *    model reports them, closed by the same launch - unless opts->deferred_loss_terms is set: then the forward leaves the loss open and
+ *    the backward call's matching-head launch closes it into opts->deferred_loss_terms (pass the same options to both calls).
+ *  - opts->align_external: no similarity rows in the forward; the caller writes the workspace buffers d.align.that / d.align.vhat [B,128]
+ *    (hual_seqpan_ws_table) between the two calls, as an exact data-parallel step does through hual_align_loss_rows.
+ * The backward takes the two parts of d outputs (what the encoders and what the heads' hidden layers send back: summed on the way in)
+ * and returns d_feats [B*(T+L),128] and, in `grads`, the gradients of cq_cat, matching_loss/dense and label_emb (orthogonality term
+ * included).  It must follow hual_fuse_fwd with the same labels on the same workspace; without labels it is refused (HUAL_ERR_INVALID). */
+int hual_fuse_fwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const hual_labels* labels,
+                  const float* feats, const float* loc_part, float* outputs, float* match_scores, float* loss_terms, void* workspace,
+                  uint64_t ws_bytes, void* stream);
+int hual_fuse_bwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const hual_labels* labels,
+                  const float* d_outputs, const float* d_outputs_heads, float* d_feats, float* grads, void* workspace, uint64_t ws_bytes,
+                  void* stream);
 /* modules.py:143-160 conditioned_predictor on `outputs` [B*T,128] -> raw start / end logits [B,T] and the span argmax of
  * layers.py:194-203; the backward takes the gradients of the two logit tensors */
 int hual_predictor_fwd(const hual_cfg* cfg, const float* params, const hual_batch* batch, const hual_run_opts* opts, const float* outputs,
@@ -375,6 +394,11 @@ int hual_attention_bwd(const float* Q, int ldq, const float* K, const float* V, 
  * over rows of the row maxima, end = argmax over columns of the column maxima, first index on ties.  T <= 256. */
 int hual_span_argmax(const float* start_logits, const float* end_logits, const float* vmask, int64_t* start_index,
                      int64_t* end_index, int B, int T, void* stream);
+/* the same launch with labels (HUAL_ABI_VERSION unchanged: a new symbol): localizing_loss (layers.py:177-191) on given logits [B,T] and
+ * soft labels y1 / y2 [B,T] (rows need not sum to 1) -> loc_part [B] = clip b's -(y1 . log_softmax(s) + y2 . log_softmax(e)) / B (their
+ * sum is the loss), ds / de [B,T] = the gradient of that loss wrt the two logit tensors, and the spans of hual_span_argmax.  T <= 256. */
+int hual_localizing_loss(const float* start_logits, const float* end_logits, const float* vmask, const float* y1, const float* y2,
+                         float* ds, float* de, float* loc_part, int64_t* start_index, int64_t* end_index, int B, int T, void* stream);
 
 /* the k best spans of each clip (R@k evaluation, ABI 9): softmax of the masked start / end logits exactly as hual_span_argmax computes
  * it, candidates p_s[i] * p_e[j] (one fp32 product) for 0 <= i <= j < video_seq_len[b] (and j - i < max_len when max_len > 0), greedy
