@@ -1030,6 +1030,61 @@ class LabelUpdater:
         self.set_active_points(aps)
         return asked, answers, n_asked
 
+    def session_label(self, gt_idx, max_questions, thresholds=(0.3, 0.5, 0.7), stop_hit=None, stop_at=0.7, stop_entropy=None, min_gain=0.0,
+                      noise=None, flips=None, budget=None, sel=None):
+        """session() that knows what the annotation is for (hual_al_session_label, one launch): after every pass the session also
+        takes the minimum-Bayes-risk label of the list so far (mbr_label()'s) and that label's hit probability at the IoU thresholds
+        `thresholds` (lib.hit_thresholds, at most 4; hit_label()'s cand_hit of that one span), and with stop_hit=p in (0, 1] it stops
+        as 'reliable' - before the entropy, gain and budget rules - once the stored float32 probability at the threshold stop_at (one
+        of `thresholds`) is at least p.  stop_hit=None: the rule is off and the session is session()'s bit for bit.  Every other
+        argument, the refusals and the returned numpy (asked, answers, n_asked) are session()'s.
+        Leaves session()'s tensors and label_path (i32 [N, Q + 1, 2]), label_conf_path (f32 [N, Q + 1]) and label_hit_path (f32
+        [N, Q + 1, M]) as device tensors: slot k is the pass before question k, slot n_asked the final label - what mbr_label() gives
+        on the installed lists -; unused slots, passes that were not live and rows outside sel hold -1.  Installs the extended lists
+        with set_active_points.  It has no ensemble form."""
+        self._no_ensemble('session_label()')
+        Q = int(max_questions)
+        if not 1 <= Q <= lib.AL_SESSION_MAX_Q:
+            raise ValueError('session_label: max_questions must lie in [1, %d]' % lib.AL_SESSION_MAX_Q)
+        if not float(min_gain) >= 0.0:
+            raise ValueError('session_label: min_gain >= 0')
+        thr = lib.hit_thresholds(thresholds)
+        at = lib.hit_thresholds((stop_at,))[0]
+        if at not in thr:
+            raise ValueError('session_label: stop_at must be one of the thresholds')
+        if stop_hit is not None and not 0.0 < float(stop_hit) <= 1.0:
+            raise ValueError('session_label: stop_hit is None or a probability in (0, 1]')
+        eps = 0.0 if noise is None else check_noise(noise)
+        gt = np.ascontiguousarray(gt_idx, dtype=np.int32)
+        if gt.shape != (self.N, 2):
+            raise ValueError('session_label: gt_idx must hold N = %d spans' % self.N)
+        rows = np.arange(self.N) if sel is None else np.asarray(sel, dtype=np.int64)
+        if rows.ndim != 1 or rows.size < 1 or rows.min() < 0 or rows.max() >= self.N:
+            raise ValueError('session_label: sel holds sample ids in [0, N)')
+        cap = np.full(self.N, Q, dtype=np.int64) if budget is None else np.clip(np.asarray(budget, dtype=np.int64), 0, Q)
+        if cap.shape != (self.N,):
+            raise ValueError('session_label: budget must hold N = %d caps' % self.N)
+        for i in rows:
+            if len(self.aps[i]) + int(cap[i]) > lib.AL_SESSION_MAX_POINTS:
+                raise ValueError('session_label: sample %d holds %d answered points: with a budget of %d that exceeds the %d a session keeps'
+                                 % (i, len(self.aps[i]), int(cap[i]), lib.AL_SESSION_MAX_POINTS))
+
+        def dev32(x):
+            return torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
+        flip_d = None if flips is None else dev32(np.asarray(flips, dtype=np.uint32).view(np.int32))
+        (self.asked, self.answers, self.q_asked, self.session_gain, self.entropy_path, self.n_asked, self.stop_reason, self.label_path,
+         self.label_conf_path, self.label_hit_path) = lib.al_session_label(
+            self.set, *self._logits(), self.tlen_h, dev32(gt), Q, thresholds=thresholds, stop_m=thr.index(at),
+            stop_hit=-1.0 if stop_hit is None else float(stop_hit), sel=None if sel is None else dev32(rows.astype(np.int32)),
+            budget=None if budget is None else dev32(cap.astype(np.int32)),
+            stop_entropy=-1.0 if stop_entropy is None else float(stop_entropy), min_gain=float(min_gain), eps=eps, flip=flip_d)
+        asked, answers, n_asked = self.asked.cpu().numpy(), self.answers.cpu().numpy(), self.n_asked.cpu().numpy()
+        aps = list(self.aps)                                     # (a new outer list and new rows: the caller's lists are not touched)
+        for i in set(int(i) for i in rows):
+            aps[i] = list(aps[i]) + [(int(asked[i, k]), bool(answers[i, k])) for k in range(int(n_asked[i]))]
+        self.set_active_points(aps)
+        return asked, answers, n_asked
+
     def design(self, max_points, min_gain=0.0, stop_entropy=None, noise=None, forced=None, sel=None):
         """the frames to ask TOGETHER about every sample (hual_al_design, one launch): for an annotator who is not in the loop - a
         labelling tool, a crowd batch, one viewing of the clip - a greedy design of up to max_points (1..16) frames under the span
@@ -1157,14 +1212,25 @@ HIT_MARGIN = 1e-6                      # renew_by='hit_prob' moves a label only 
 # check_round's result: the switches of a round as update_labels works from them - the enumerations as given; Q, the questions per
 # clip, an int; stop_entropy, noise and temperature floats or None; flip None or (rate, Generator); reads_posterior: one of the span
 # posterior's readers is on; questions_at_once: M, the frames a selected sample is asked together; hit_iou: the threshold of HIT_IOUS
-# that rank_by='label_miss' and renew_by='hit_prob' decide at
-RoundPolicy = collections.namedtuple('RoundPolicy', 'posterior rank_by observe_by renew_by acquire_by Q stop_entropy noise temperature '
-                                                    'calibrate flip reads_posterior questions_at_once hit_iou')
+# that rank_by='label_miss', renew_by='hit_prob' and stop_hit decide at
+_RoundFields = collections.namedtuple('RoundPolicy', 'posterior rank_by observe_by renew_by acquire_by Q stop_entropy noise temperature '
+                                                     'calibrate flip reads_posterior questions_at_once hit_iou')
+
+
+class RoundPolicy(_RoundFields):
+    """the tuple of a round's switches, and beside it - an attribute, not a field: the tuple of a round without it is the tuple it
+    was - stop_hit: None, or the hit probability of the label at hit_iou at which a session stops"""
+    stop_hit = None
+
+    def __new__(cls, *fields, stop_hit=None):
+        pol = super().__new__(cls, *fields)
+        pol.stop_hit = stop_hit
+        return pol
 
 
 def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='uncert_video', observe_by='uncert_frame',
                 renew_by='heuristic', acquire_by=None, soft_out=None, answer_noise=None, annotator_flip=None, questions_per_clip=1,
-                stop_entropy=None, temperature=None, calibrate=None, questions_at_once=1, hit_iou=0.7):
+                stop_entropy=None, temperature=None, calibrate=None, questions_at_once=1, hit_iou=0.7, stop_hit=None):
     """every rule between the switches of update_labels / run_round (their docstrings say what each switch does) -> RoundPolicy;
     raises ValueError, and touches nothing"""
     readers = {"observe_by='info_gain'": observe_by == 'info_gain', "acquire_by='label_gain'": acquire_by == 'label_gain',
@@ -1212,6 +1278,8 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
         raise ValueError("questions_per_clip > 1 needs observe_by='info_gain': a session asks by expected information gain")
     if stop_entropy is not None and not (Q > 1 and number(stop_entropy, lambda h: float(h) >= 0.0)):
         raise ValueError('stop_entropy: None, or bits >= 0 with questions_per_clip > 1')
+    if stop_hit is not None and not (Q > 1 and not isinstance(stop_hit, bool) and number(stop_hit, lambda p: 0.0 < float(p) <= 1.0)):
+        raise ValueError('stop_hit: None, or a hit probability in (0, 1] with questions_per_clip > 1')
     # question sets: M frames per clip asked together, designed by information gain under the deterministic posterior
     if not number(questions_at_once, lambda q: not isinstance(q, bool) and int(q) == q and 1 <= int(q) <= lib.AL_DESIGN_MAX_M):
         raise ValueError('questions_at_once: an integer in [1, %d]' % lib.AL_DESIGN_MAX_M)
@@ -1261,7 +1329,7 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
                          % acquire_by)
     return RoundPolicy(posterior, rank_by, observe_by, renew_by, acquire_by, Q, None if stop_entropy is None else float(stop_entropy), noise,
                        None if temperature is None else float(temperature), calibrate, annotator_flip, any(readers.values()), M,
-                       float(hit_iou))
+                       float(hit_iou), stop_hit=None if stop_hit is None else float(stop_hit))
 
 
 def span_risk(last_prop):
@@ -1349,7 +1417,10 @@ def _round_ask(up, pol, noise, sel, ask, gt_idx, data_old, aps):
     if Q > 1 or M > 1:                                           # (both need observe_by='info_gain': query() ran and left query_gain)
         has_gain = up.query_gain.cpu().numpy() > 0
         in_session, in_design = (sel[has_gain[sel]], in_design) if Q > 1 else (in_session, sel[has_gain[sel]])
-    if len(in_session):
+    if len(in_session) and pol.stop_hit is not None:             # the same sessions, stopped once the label is reliable at hit_iou
+        asked, answers, n_asked = up.session_label(gt_idx, Q, thresholds=HIT_IOUS, stop_hit=pol.stop_hit, stop_at=pol.hit_iou,
+                                                   stop_entropy=pol.stop_entropy, noise=noise, flips=flips, sel=in_session)
+    elif len(in_session):
         asked, answers, n_asked = up.session(gt_idx, Q, stop_entropy=pol.stop_entropy, noise=noise, flips=flips, sel=in_session)
     if len(in_design):                                           # one launch for all of them; the annotator answers below, on the host
         frames, n_design = up.design(M, noise=noise, sel=in_design)
@@ -1378,6 +1449,12 @@ def _round_ask(up, pol, noise, sel, ask, gt_idx, data_old, aps):
         if len(in_session):
             dbg['entropy_path'][in_session] = up.entropy_path.cpu().numpy()[in_session]
             dbg['stop_reason'][in_session] = up.stop_reason.cpu().numpy()[in_session]
+        if pol.stop_hit is not None:                             # the label trails: -1 = unused / not live / no session
+            dbg.update(label_path=np.full((N, Q + 1, 2), -1, dtype=np.int32), label_conf_path=np.full((N, Q + 1), -1.0, dtype=np.float32),
+                       label_hit_path=np.full((N, Q + 1, len(HIT_IOUS)), -1.0, dtype=np.float32))
+            if len(in_session):
+                for key in ('label_path', 'label_conf_path', 'label_hit_path'):
+                    dbg[key][in_session] = getattr(up, key).cpu().numpy()[in_session]
     if M > 1:                                                    # the designs as the launch left them: -1 = unused / no design
         dbg = dict(design=np.full((N, M), -1, dtype=np.int64), design_info=np.full((N, M), -1.0, dtype=np.float32),
                    n_design=np.zeros(N, dtype=np.int64), design_stop=np.full(N, -1, dtype=np.int64))
@@ -1439,7 +1516,7 @@ def _round_debug(*parts):
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
                   rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
                   answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None,
-                  posterior='deterministic', questions_at_once=1, hit_iou=0.7):
+                  posterior='deterministic', questions_at_once=1, hit_iou=0.7, stop_hit=None):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -1538,11 +1615,19 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     dict gains 'label_miss' (float32 [N]) and 'old_hit' (float32 [N, 3], columns 0.3 / 0.5 / 0.7) under the ranking, and 'old_hit',
     'label_hit' (float32 [N, 3]), 'hit_best_idx' (int32 [N, 3, 2]), 'hit_best_prob' (float32 [N, 3]) and 'renewed_by_hit' (bool [N])
     under the renew, whose 'old_hit' - this round's answers included, rows outside the selection -1 - is the one kept when both are on.
+    stop_hit: None (every launch and result as without the argument), or p in (0, 1] with questions_per_clip > 1 - the sessions then
+    also take, after every pass, the minimum-Bayes-risk label of the answers so far and its hit probability at hit_iou
+    (LabelUpdater.session_label, one launch in place of the session's), and a session stops - stop_reason 'reliable', before the
+    entropy, gain and budget rules - once that probability is at least p: "ask until the label is safe at IoU hit_iou with
+    probability p".  Everything else about the sessions and the round is unchanged; the renew runs as before, so under
+    renew_by='posterior' a session's final label is the label the renew gives.  The debug dict gains 'label_path' (int32 [N, Q + 1,
+    2]), 'label_conf_path' (float32 [N, Q + 1]) and 'label_hit_path' (float32 [N, Q + 1, 3], columns 0.3 / 0.5 / 0.7): slot k is the
+    pass before question k, slot n_asked the final label; -1 = unused, not live or no session.
     """
     pol = check_round(posterior=posterior, bank=bank, mc_samples=mc_samples, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by,
                       acquire_by=acquire_by, soft_out=soft_out, answer_noise=answer_noise, annotator_flip=annotator_flip,
                       questions_per_clip=questions_per_clip, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate,
-                      questions_at_once=questions_at_once, hit_iou=hit_iou)
+                      questions_at_once=questions_at_once, hit_iou=hit_iou, stop_hit=stop_hit)
     risk = span_risk(last_prop) if pol.rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -1585,7 +1670,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
               observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
               annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None, posterior='deterministic',
-              rank_by='uncert_video', questions_at_once=1, hit_iou=0.7):
+              rank_by='uncert_video', questions_at_once=1, hit_iou=0.7, stop_hit=None):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -1617,6 +1702,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     the call raises ValueError before anything is touched.
     rank_by='label_miss' / renew_by='hit_prob' / hit_iou: rank the samples by the chance that their current label misses at IoU
     hit_iou, and renew by the span of maximal hit probability where it beats the minimum-Bayes-risk label (update_labels).
+    stop_hit: the hit probability of the label at hit_iou at which a session stops (update_labels); metrics['sessions'] then also
+    holds label_path, label_conf_path and label_hit_path.
     soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
     blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
     DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
@@ -1642,7 +1729,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     switches = dict(posterior=posterior, bank=prev, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by, acquire_by=acquire_by,
                     soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip, questions_per_clip=questions_per_clip,
                     stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate, questions_at_once=questions_at_once,
-                    hit_iou=hit_iou)
+                    hit_iou=hit_iou, stop_hit=stop_hit)
     pol = check_round(**switches)                                # (on every rank, before rank 0 goes its own way)
     want_debug = pol.Q > 1 or pol.questions_at_once > 1 or calibrate is not None
     new_data = sessions = designs = calibration = None
@@ -1653,7 +1740,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
             new_data, dbg = new_data
             calibration = dbg.get('calibration')
         if pol.Q > 1:
-            sessions = {k: dbg[k] for k in ('asked', 'answers', 'n_asked', 'entropy_path', 'stop_reason')}
+            sessions = {k: dbg[k] for k in ('asked', 'answers', 'n_asked', 'entropy_path', 'stop_reason')
+                        + (('label_path', 'label_conf_path', 'label_hit_path') if pol.stop_hit is not None else ())}
         if pol.questions_at_once > 1:
             designs = {k: dbg[k] for k in ('design', 'design_info', 'n_design', 'design_stop')}
     new_data = hdist.broadcast_object(new_data)

@@ -126,6 +126,18 @@ struct AlSessionArgs {
   int32_t *n_asked, *stop_reason;             // [N]
 };
 
+// hual_al_session_label (spansessionlabel.hip): a session that also keeps, per pass, the MBR label of the list so far and its hit
+// probability, and may stop on the latter
+struct AlSessionLabelArgs {
+  AlSessionArgs s;                            // the session's own arguments and its seven outputs
+  int num[4], den[4];                         // the IoU thresholds, read on the host before the launch
+  int M, stop_m;                              // 1..4 thresholds | the column the stop rule reads
+  float stop_hit;                             // < 0: off; else the session stops once (float)label_hit[stop_m] >= stop_hit
+  int32_t* label;                             // [N, qmax + 1, 2] slot k: the label of the pass before question k; -1: unused / not live
+  float* label_conf;                          // [N, qmax + 1]
+  float* label_hit;                           // [N, qmax + 1, M]
+};
+
 // hual_al_design (spandesign.hip): the frames to ask TOGETHER about every selected sample - a greedy design under the span posterior
 struct AlDesignArgs {
   AlSpanIn in;
@@ -157,6 +169,7 @@ int launch_al_mbr_label(const AlLabelArgs& a, int nsel, hipStream_t s);
 int launch_al_hit_label(const AlHitArgs& a, int nsel, hipStream_t s);
 int launch_al_query(const AlQueryArgs& a, hipStream_t s);
 int launch_al_session(const AlSessionArgs& a, int nsel, hipStream_t s);
+int launch_al_session_label(const AlSessionLabelArgs& a, int nsel, hipStream_t s);
 int launch_al_design(const AlDesignArgs& a, int nsel, hipStream_t s);
 int launch_al_mc_fold(const AlFoldArgs& a, hipStream_t s);
 int launch_al_renew(const AlRenewArgs& a, int nsel, hipStream_t s);

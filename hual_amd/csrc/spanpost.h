@@ -1,6 +1,6 @@
 // The span posterior of one sample given its answered active points, as every launch of the family opens it (hual_al_query in
 // spanquery.hip, hual_al_mbr_label in spanlabel.hip, hual_al_label_gain in spangain.hip, hual_al_span_marginals in spanmarg.hip,
-// every step of hual_al_session in spansession.hip, hual_al_design in spandesign.hip, every pass of the ensemble launches in
+// every step of hual_al_session in spansession.hip and of hual_al_session_label in spansessionlabel.hip, hual_al_design in spandesign.hip, every pass of the ensemble launches in
 // spanens.hip, hual_al_noisy_tilt in spannoisy.hip, hual_al_hit_label in spanhitlabel.hip, the header of hual_al_evidence_grid in spancalib.hip; the
 // contract is in include/hual_seqpan.h): which rows are live, what the consistent set A is, and what Z and Z_A are.  One definition, so
 // all launches classify a row alike (tests/test_gpu_span_rows.py); the per-clip launches of the evaluation have theirs in spanclip.h.

@@ -179,6 +179,8 @@ def load():
     lib.hual_al_noisy_tilt.argtypes = [P(hual_al_set), vp, vp, f32, vp, vp, vp, vp]
     lib.hual_al_label_gain_noisy.argtypes = [P(hual_al_set), vp, vp, f32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_al_session.argtypes = [P(hual_al_set), vp, vp, vp, vp, i32, i32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.hual_al_session_label.argtypes = ([P(hual_al_set), vp, vp, vp, vp, i32, i32, vp, f32, f32, f32, vp, vp, i32, i32, f32] + [vp] * 10
+                                          + [vp])
     lib.hual_al_design.argtypes = [P(hual_al_set), vp, vp, vp, i32, i32, vp, f32, f32, vp, vp, vp, vp, vp, vp]
     lib.hual_al_evidence_grid.argtypes = [P(hual_al_set), vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_al_ensemble_query.argtypes = [P(hual_al_set), vp, vp, i32, vp] + [vp] * 12 + [vp]
@@ -552,7 +554,7 @@ AL_GRID_MAX_EPS = 16        # error rates per launch (csrc/spancalib.h)
 AL_SESSION_MAX_Q = 16           # question slots per sample of hual_al_session
 AL_SESSION_MAX_POINTS = 64      # active points of one sample, the set's and the session's, that hual_al_session holds
 AL_DESIGN_MAX_M = 16            # frames per sample of hual_al_design
-AL_STOP_REASONS = ('budget', 'entropy', 'gain', 'contradictory', 'poisoned', 'overflow')      # HUAL_AL_STOP_*, by value
+AL_STOP_REASONS = ('budget', 'entropy', 'gain', 'contradictory', 'poisoned', 'overflow', 'reliable')      # HUAL_AL_STOP_*, by value
 
 # The outputs of every span-posterior launch, in the order the C entry point takes them: (name, shape, dtype, fill, optional).
 # shape: extents by name - N, ld, K (passes), Q (question slots), Q1 = Q + 1, M (design slots), AB (grid cells) - or as numbers; fill: what a tensor
@@ -562,6 +564,9 @@ _NAN = float('nan')
 _LABEL_OUT = (('new_idx', ('N', 2), 'int32', -1, False), ('conf', ('N',), 'float32', -1, False), ('old_conf', ('N',), 'float32', -1, True))
 _GAIN_OUT = (('gain', ('N', 'ld'), 'float32', 0, True), ('ask_point', ('N',), 'int32', -1, False), ('ask_gain', ('N',), 'float32', -1, False),
              ('value', ('N',), 'float32', -1, False))
+_SESSION_OUT = (('asked', ('N', 'Q'), 'int32', -1, False), ('answer', ('N', 'Q'), 'int8', -1, False), ('q_asked', ('N', 'Q'), 'float32', -1, False),
+                ('gain', ('N', 'Q'), 'float32', -1, False), ('entropy', ('N', 'Q1'), 'float32', -1, False), ('n_asked', ('N',), 'int32', -1, False),
+                ('stop_reason', ('N',), 'int32', -1, False))
 _SPAN_OUT = {
     'al_query': (('incl', ('N', 'ld'), 'float32', 0, True), ('gain', ('N', 'ld'), 'float32', 0, True), ('query_point', ('N',), 'int32', None, False),
                  ('query_gain', ('N',), 'float32', None, False), ('post_entropy', ('N',), 'float32', None, False),
@@ -582,9 +587,9 @@ _SPAN_OUT = {
                           ('span_bald', ('N',), 'float32', None, False), ('status', ('N',), 'int32', None, False)),
     'al_evidence_grid': (('table', ('N', 'AB'), 'float64', _NAN, False), ('status', ('N',), 'int32', -1, False),
                          ('total', ('AB',), 'float64', None, False), ('counts', (4,), 'int32', None, False)),
-    'al_session': (('asked', ('N', 'Q'), 'int32', -1, False), ('answer', ('N', 'Q'), 'int8', -1, False), ('q_asked', ('N', 'Q'), 'float32', -1, False),
-                   ('gain', ('N', 'Q'), 'float32', -1, False), ('entropy', ('N', 'Q1'), 'float32', -1, False), ('n_asked', ('N',), 'int32', -1, False),
-                   ('stop_reason', ('N',), 'int32', -1, False)),
+    'al_session': _SESSION_OUT,
+    'al_session_label': _SESSION_OUT + (('label', ('N', 'Q1', 2), 'int32', -1, False), ('label_conf', ('N', 'Q1'), 'float32', -1, False),
+                                        ('label_hit', ('N', 'Q1', 'M'), 'float32', -1, False)),
     'al_design': (('frames', ('N', 'M'), 'int32', -1, False), ('info', ('N', 'M'), 'float32', -1, False), ('post_entropy', ('N',), 'float32', -1, False),
                   ('n_design', ('N',), 'int32', -1, False), ('stop_reason', ('N',), 'int32', -1, False)),
 }
@@ -852,6 +857,41 @@ def al_session(aset, s0, e0, tlen, gt, qmax, sel=None, budget=None, stop_entropy
     _span_index('al_session', 'flip', flip, (N,), dev)
     out = _span_out('al_session', out, dev, N=N, Q=qmax, Q1=qmax + 1)
     _launch('hual_al_session', aset, s0, e0, gt, sel, nsel, qmax, budget, float(stop_entropy), float(min_gain), float(eps), flip, *out)
+    return out
+
+
+def al_session_label(aset, s0, e0, tlen, gt, qmax, thresholds=(0.3, 0.5, 0.7), stop_m=0, stop_hit=-1.0, sel=None, budget=None,
+                     stop_entropy=-1.0, min_gain=0.0, eps=0.0, flip=None, out=None):
+    """al_session with a label trail and a stop rule on the label's reliability (hual_al_session_label), one launch enqueued on the
+    current stream: after every pass of the session the minimum-Bayes-risk label of the list so far (al_mbr_label's) and its hit
+    probability at the M <= 4 IoU thresholds `thresholds` (hit_thresholds; al_hit_label's cand_hit of that one span), and the session
+    stops as 'reliable' once the stored float32 hit probability at thresholds[stop_m] reaches stop_hit - a probability in (0, 1];
+    negative: the rule is off and the session is al_session's bit for bit.  aset, s0 / e0, tlen, gt, qmax, sel, budget, stop_entropy,
+    min_gain, eps and flip are al_session's.
+    -> al_session's seven tensors, then label i32 [N, qmax + 1, 2], label_conf f32 [N, qmax + 1], label_hit f32 [N, qmax + 1, M]: slot k
+    is the pass before question k, slot n_asked the final label.  out: such a tuple of ten contiguous device tensors to write into
+    instead.  Only the rows of selected samples are written: the others keep what they held (-1 in tensors allocated here, the value
+    of an unused slot and of a pass that was not live)."""
+    who = 'al_session_label'
+    N, ld, dev = _span_inputs(who, aset, s0, e0, tlen)
+    thr = hit_thresholds(thresholds)
+    M = len(thr)
+    nsel = _span_sel(who, sel, N, dev)
+    qmax = int(qmax)
+    if not 1 <= qmax <= AL_SESSION_MAX_Q:
+        raise HualError(who + ': qmax must lie in [1, %d]' % AL_SESSION_MAX_Q)
+    if isinstance(stop_m, bool) or int(stop_m) != stop_m or not 0 <= int(stop_m) < M:
+        raise HualError(who + ': stop_m is the index of one of the %d thresholds' % M)
+    stop_hit = float(stop_hit)
+    if not (stop_hit < 0.0 or 0.0 < stop_hit <= 1.0):
+        raise HualError(who + ': stop_hit is negative (off) or a probability in (0, 1]')
+    _span_index(who, 'gt', gt, (N, 2), dev, required=True)
+    _span_index(who, 'budget', budget, (N,), dev)
+    _span_index(who, 'flip', flip, (N,), dev)
+    out = _span_out(who, out, dev, N=N, Q=qmax, Q1=qmax + 1, M=M)
+    cthr = (ctypes.c_int32 * (2 * M))(*[x for nd in thr for x in nd])
+    _launch('hual_al_session_label', aset, s0, e0, gt, sel, nsel, qmax, budget, float(stop_entropy), float(min_gain), float(eps), flip,
+            cthr, M, int(stop_m), stop_hit, *out)
     return out
 
 

@@ -888,6 +888,43 @@ int hual_al_session(const hual_al_set* set, const float* s0, const float* e0, co
                     const int32_t* budget, float stop_entropy, float min_gain, float eps, const uint32_t* flip, int32_t* asked,
                     int8_t* answer, float* q_asked, float* gain, float* entropy, int32_t* n_asked, int32_t* stop_reason, void* stream);
 
+/* Sessions that stop once the pseudo-label is reliable (HUAL_ABI_VERSION unchanged: one new symbol, nothing else moved).  The stop
+ * rules above are in bits, but the annotation is for a label: hual_al_session_label is hual_al_session with, per pass, the label the
+ * list so far gives and the chance that this label counts as a hit, and one more stop rule on that chance - "ask until the label is
+ * safe at IoU 0.7 with probability 0.9".
+ *
+ * Inputs: those of hual_al_session, word for word, plus thresholds / M as in hual_al_hit_label (HOST int32 [M][2] = (num, den), 1 <=
+ * num <= den <= 1024, 1 <= M <= 4, passed by value), stop_m in [0, M), the threshold the rule reads, and stop_hit: negative = the rule
+ * is off, else a probability in (0, 1].
+ *
+ * Per selected sample, with k = the questions asked so far:
+ *  1. the posterior on the list and the frame: steps 1 and 2 of hual_al_session.
+ *  2. on a live pass, the label: hual_al_mbr_label's new_idx and conf on a set that holds the list (eps == 0), or on the tilted rows
+ *     and a set without answers (eps > 0: any span of the clip).
+ *  3. its reliability: hual_al_hit_label's cand_hit of that one span at the M thresholds, on the same set and rows.
+ *  4. the stop conditions, in this order: poisoned; contradictory; stop_hit >= 0 and the STORED float32 label_hit[k][stop_m] >=
+ *     stop_hit -> HUAL_AL_STOP_RELIABLE; then stop_entropy, min_gain and the budget exactly as in hual_al_session.
+ *  5. otherwise the question is asked, answered and appended as in hual_al_session.
+ * The 64-point list and HUAL_AL_STOP_OVERFLOW are hual_al_session's.
+ *
+ * Outputs, each written for every selected sample: the seven outputs of hual_al_session with the same meaning, and label i32
+ * [N, qmax + 1, 2], label_conf f32 [N, qmax + 1], label_hit f32 [N, qmax + 1, M]: slot k holds the pass before question k, slot
+ * n_asked the pass that stopped the session - the final label, what hual_al_mbr_label gives on the list the session leaves.  Unused
+ * slots, and passes that found the row poisoned or contradictory, hold -1 in all three.  With stop_hit off the seven session outputs
+ * are hual_al_session's bit for bit.  Every stored value is bit for bit what hual_al_noisy_tilt (eps > 0), hual_al_query,
+ * hual_al_mbr_label and hual_al_hit_label store on the same list (shared bodies: csrc/spansession.h, spanstep.h, spanmbr.h,
+ * spanmass.h; the divisor Z_A is that of the two label launches), and every decision follows from the stored float32 values.
+ * One 1024-thread workgroup per selected sample; each pass costs one label search, about v^3 / 2 float64 additions on a row without
+ * answers.  No atomics, nothing grid wide: a second launch returns equal bits.  Allocates nothing and does not synchronise:
+ * capturable in a hipGraph.  Argument errors (those of hual_al_session; a null thresholds, label, label_conf or label_hit; M, a
+ * threshold or stop_m out of range; stop_hit 0, above 1 or NaN) return HUAL_ERR_INVALID before any HIP call. */
+#define HUAL_AL_STOP_RELIABLE 6
+int hual_al_session_label(const hual_al_set* set, const float* s0, const float* e0, const int32_t* gt, const int32_t* sel, int nsel,
+                          int qmax, const int32_t* budget, float stop_entropy, float min_gain, float eps, const uint32_t* flip,
+                          const int32_t* thresholds, int M, int stop_m, float stop_hit, int32_t* asked, int8_t* answer, float* q_asked,
+                          float* gain, float* entropy, int32_t* n_asked, int32_t* stop_reason, int32_t* label, float* label_conf,
+                          float* label_hit, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Question sets for an annotator who is not in the loop: M frames per clip in one launch (HUAL_ABI_VERSION unchanged: one new symbol,
  * nothing else moved).  hual_al_session answers each question inside the kernel, so it serves the simulated annotator only; a labelling
