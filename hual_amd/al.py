@@ -1218,21 +1218,95 @@ _RoundFields = collections.namedtuple('RoundPolicy', 'posterior rank_by observe_
 
 
 class RoundPolicy(_RoundFields):
-    """the tuple of a round's switches, and beside it - an attribute, not a field: the tuple of a round without it is the tuple it
-    was - stop_hit: None, or the hit probability of the label at hit_iou at which a session stops"""
+    """the tuple of a round's switches, and beside it - attributes, not fields: the tuple of a round without them is the tuple it
+    was - stop_hit: None, or the hit probability of the label at hit_iou at which a session stops; select_by / descriptors /
+    diversity_init: how the asked half is chosen from the ranking (None: its top half; 'kcenter': diverse_select on the descriptors,
+    with diversity_init='answered' around the clips that already hold an active point)"""
     stop_hit = None
+    select_by = None
+    descriptors = None
+    diversity_init = None
 
-    def __new__(cls, *fields, stop_hit=None):
+    def __new__(cls, *fields, stop_hit=None, select_by=None, descriptors=None, diversity_init=None):
         pol = super().__new__(cls, *fields)
         pol.stop_hit = stop_hit
+        pol.select_by, pol.descriptors, pol.diversity_init = select_by, descriptors, diversity_init
         return pol
+
+
+SELECT_BY = (None, 'kcenter')
+DIVERSITY_INIT = (None, 'answered')
+
+
+def rank_weights(order):
+    """the selection weights of a ranking: w[i] = float32((N - rank_i) / N), computed in float64, rank_i the position of i in
+    `order` - 1 for the first-ranked clip, 1 / N for the last.  Ranks, not scores: scale-free, and valid for every rank_by whichever
+    way its scalar points."""
+    order = np.asarray(order)
+    N = len(order)
+    if sorted(order.tolist()) != list(range(N)):
+        raise ValueError('order must be a permutation of range(N)')
+    rank = np.empty(N, dtype=np.int64)
+    rank[order] = np.arange(N)
+    return ((N - rank).astype(np.float64) / N).astype(np.float32)
+
+
+def _diverse(desc, order, n_select, weighted=True, init=None):
+    """diverse_select's launch -> (picks without the -1 of an exhausted selection, picked, pick_dist, mind: the launch's tensors)"""
+    if not (torch.is_tensor(desc) and desc.dim() == 2 and desc.dtype == torch.float32):
+        raise ValueError('descriptors: a float32 [N, D] device tensor')
+    order = np.asarray(order)
+    N = int(desc.shape[0])
+    if len(order) != N:
+        raise ValueError('descriptors: %d rows for %d ranked samples' % (N, len(order)))
+    init = None if init is None or len(init) == 0 else np.asarray(init, dtype=np.int64)
+    if weighted:
+        w = rank_weights(order)
+    elif init is None:                                           # plain k-center started at order[0]: the one larger weight wins step 0
+        rank_weights(order)                                      # (the permutation check)
+        w = np.full(N, 0.5, dtype=np.float32)                    # (equal weights: every later step is plain k-center - 0.5 x is exact)
+        w[order[0]] = 1.0
+    else:                                                        # plain k-center around the given centers: no weights at all
+        rank_weights(order)
+        w = None
+    w_d = None if w is None else torch.from_numpy(w).to(desc.device)
+    picked, dist, mind, _ = lib.kcenter_select(desc, n_select, weight=w_d, init=init)
+    picks = picked.cpu().numpy().astype(np.int64)
+    return picks[picks >= 0], picked, dist, mind
+
+
+def diverse_select(desc, order, n_select, weighted=True, init=None):
+    """core-set selection of the clips to ask: n_select greedy k-center picks in the descriptor space (lib.kcenter_select, one call),
+    weighted by the ranking.  desc: device f32 [N, D] (DeviceDataset.clip_descriptors()); order: the ranking of the N samples, best
+    first (update_labels' order, whatever rank_by made it).  weighted: the weights are rank_weights(order), so step s asks the clip
+    of maximal weight x squared distance to the clips asked so far, and among exact ties - duplicate descriptors - the better-ranked
+    one; the first pick is order[0].  weighted=False: plain k-center started at order[0] - weight 1 for order[0] and 0.5 for every
+    other row, which decides step 0 and scales every later score by the same exact factor; with init centers there is no start to
+    choose and no weight is passed.  init: rows (host ints, in [0, N), no repeats: ValueError) that count as asked already - centers
+    before the first pick, never picked.
+    -> the picks as a numpy int array in pick order; shorter than n_select when the eligible rows run out."""
+    return _diverse(desc, order, n_select, weighted=weighted, init=init)[0]
 
 
 def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='uncert_video', observe_by='uncert_frame',
                 renew_by='heuristic', acquire_by=None, soft_out=None, answer_noise=None, annotator_flip=None, questions_per_clip=1,
-                stop_entropy=None, temperature=None, calibrate=None, questions_at_once=1, hit_iou=0.7, stop_hit=None):
+                stop_entropy=None, temperature=None, calibrate=None, questions_at_once=1, hit_iou=0.7, stop_hit=None, select_by=None,
+                descriptors=None, diversity_init=None):
     """every rule between the switches of update_labels / run_round (their docstrings say what each switch does) -> RoundPolicy;
     raises ValueError, and touches nothing"""
+    # the selection: the ranking's top half, or a diverse half of it
+    if select_by not in SELECT_BY:
+        raise ValueError("select_by: None or 'kcenter'")
+    if select_by is None and descriptors is not None:
+        raise ValueError("descriptors without select_by='kcenter': nothing reads them")
+    if select_by is None and diversity_init is not None:
+        raise ValueError("diversity_init without select_by='kcenter': nothing reads it")
+    if diversity_init not in DIVERSITY_INIT:
+        raise ValueError("diversity_init: None or 'answered'")
+    if select_by == 'kcenter' and not (torch.is_tensor(descriptors) and descriptors.dim() == 2 and descriptors.dtype == torch.float32
+                                       and 1 <= descriptors.shape[1] <= lib.KCENTER_MAX_D and descriptors.shape[0] >= 1):
+        raise ValueError("select_by='kcenter' needs descriptors: a float32 [N, D] device tensor, 1 <= D <= %d "
+                         "(DeviceDataset.clip_descriptors())" % lib.KCENTER_MAX_D)
     readers = {"observe_by='info_gain'": observe_by == 'info_gain', "acquire_by='label_gain'": acquire_by == 'label_gain',
                "renew_by='posterior'": renew_by == 'posterior', 'soft_out': soft_out is not None, "rank_by='span_bald'": rank_by == 'span_bald',
                "rank_by='label_miss'": rank_by == 'label_miss', "renew_by='hit_prob'": renew_by == 'hit_prob'}
@@ -1329,7 +1403,8 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
                          % acquire_by)
     return RoundPolicy(posterior, rank_by, observe_by, renew_by, acquire_by, Q, None if stop_entropy is None else float(stop_entropy), noise,
                        None if temperature is None else float(temperature), calibrate, annotator_flip, any(readers.values()), M,
-                       float(hit_iou), stop_hit=None if stop_hit is None else float(stop_hit))
+                       float(hit_iou), stop_hit=None if stop_hit is None else float(stop_hit), select_by=select_by, descriptors=descriptors,
+                       diversity_init=diversity_init)
 
 
 def span_risk(last_prop):
@@ -1398,6 +1473,22 @@ def _round_choose(up, pol, noise, risk, frames, old_idx):
         dbg.update(ask_point=up.ask_point, ask_gain=ask_gain, label_value=up.label_value, observe_used=ask)
     dbg['order'] = order
     return order, ask, dbg
+
+
+def _round_select(pol, order, aps):
+    """the samples to ask, on the answers of the earlier rounds: the top half of the ranking, or under select_by='kcenter' a diverse
+    half of it (diverse_select; with diversity_init='answered' around the samples that hold an active point, and filled from the
+    ranking, best first, where the others run out)"""
+    N = len(order)
+    n_select = math.ceil(N / 2)
+    if pol.select_by is None:
+        return order[:n_select], {}
+    init = [i for i, a in enumerate(aps) if len(a)] if pol.diversity_init == 'answered' else None
+    sel, picked, dist, mind = _diverse(pol.descriptors, order, n_select, weighted=True, init=init)
+    if len(sel) < n_select:
+        asked = set(sel.tolist())
+        sel = np.concatenate([sel, np.array([i for i in order.tolist() if i not in asked][:n_select - len(sel)], dtype=np.int64)])
+    return sel, dict(kcenter_picked=picked.cpu().numpy().astype(np.int64), kcenter_dist=dist, cover_radius=float(mind.max()))
 
 
 def _round_ask(up, pol, noise, sel, ask, gt_idx, data_old, aps):
@@ -1516,7 +1607,8 @@ def _round_debug(*parts):
 def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_debug=False, bank=None, mc_samples=None, mc_stat='range',
                   rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
                   answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None,
-                  posterior='deterministic', questions_at_once=1, hit_iou=0.7, stop_hit=None):
+                  posterior='deterministic', questions_at_once=1, hit_iou=0.7, stop_hit=None, select_by=None, descriptors=None,
+                  diversity_init=None):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -1623,11 +1715,24 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     renew_by='posterior' a session's final label is the label the renew gives.  The debug dict gains 'label_path' (int32 [N, Q + 1,
     2]), 'label_conf_path' (float32 [N, Q + 1]) and 'label_hit_path' (float32 [N, Q + 1, 3], columns 0.3 / 0.5 / 0.7): slot k is the
     pass before question k, slot n_asked the final label; -1 = unused, not live or no session.
+    select_by: None (the top half of the ranking is asked: every launch, record and result as without the argument), or 'kcenter' -
+    the asked half is then chosen as a SET: diverse_select(descriptors, order, ceil(N / 2)), greedy k-center in the descriptor space
+    weighted by the ranking (lib.kcenter_select, one call), so the round's clicks are not spent on near-duplicate clips of a few
+    hard videos; `order` is whatever rank_by / acquire_by made it, and everything after the selection is unchanged.  descriptors:
+    device f32 [N, D], one row per sample in the order of data_old (DeviceDataset.clip_descriptors()).  diversity_init: None, or
+    'answered' - the samples that already hold an active point are centers before the first pick: they count as asked, none of them
+    is asked while others remain, and the picks spread around them; when fewer than ceil(N / 2) others exist the half is filled from
+    the ranking, best first.  The debug dict gains 'kcenter_picked' (int [ceil(N / 2)], -1 past the end of the eligible rows),
+    'kcenter_dist' (float32, the pick's squared distance to the nearest earlier center) and 'cover_radius' (float: the largest
+    squared distance of any sample to its nearest asked clip).  Deterministic, so every rank of a process group gets equal picks.
     """
     pol = check_round(posterior=posterior, bank=bank, mc_samples=mc_samples, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by,
                       acquire_by=acquire_by, soft_out=soft_out, answer_noise=answer_noise, annotator_flip=annotator_flip,
                       questions_per_clip=questions_per_clip, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate,
-                      questions_at_once=questions_at_once, hit_iou=hit_iou, stop_hit=stop_hit)
+                      questions_at_once=questions_at_once, hit_iou=hit_iou, stop_hit=stop_hit, select_by=select_by, descriptors=descriptors,
+                      diversity_init=diversity_init)
+    if pol.select_by is not None and int(pol.descriptors.shape[0]) != len(data_old):      # (raises before anything is touched)
+        raise ValueError('descriptors: %d rows for %d samples' % (int(pol.descriptors.shape[0]), len(data_old)))
     risk = span_risk(last_prop) if pol.rank_by == 'span_risk' else None      # (raises before anything is touched)
     if len(data_old[0]) == 4:
         for r in data_old:
@@ -1643,13 +1748,13 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     idx = dict(gt_idx=np.array([[_round_half_even_index(t, r[1], int(v)) for t in r[2]] for r, v in zip(data_gt, up.vlen_h)]),
                old_idx=np.array([[_round_half_even_index(t, r[1], int(v)) for t in r[2]] for r, v in zip(data_old, up.vlen_h)]))
     order, ask, chosen = _round_choose(up, pol, noise, risk, return_debug, idx['old_idx'])
-    sel = order[:math.ceil(N / 2)]
+    sel, diverse = _round_select(pol, order, aps)
     asked = _round_ask(up, pol, noise, sel, ask, idx['gt_idx'], data_old, aps)
     if soft_out is not None:
         _round_soft_labels(up, noise, aps, soft_out)
     renewed = _round_renew(up, pol, noise, sel, idx['old_idx'], coff, data_old)
     if return_debug:
-        return data_old, _round_debug(scored, fitted, chosen, idx, asked, renewed)
+        return data_old, _round_debug(scored, fitted, chosen, idx, diverse, asked, renewed)
     return data_old
 
 
@@ -1670,7 +1775,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
               shuffle_seed=0, log=None, trainer=None, mc_samples=None, mc_stat='range', bank=None, span_conf=False,
               observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
               annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None, posterior='deterministic',
-              rank_by='uncert_video', questions_at_once=1, hit_iou=0.7, stop_hit=None):
+              rank_by='uncert_video', questions_at_once=1, hit_iou=0.7, stop_hit=None, select_by=None, descriptors=None,
+              diversity_init=None):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -1704,6 +1810,9 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     hit_iou, and renew by the span of maximal hit probability where it beats the minimum-Bayes-risk label (update_labels).
     stop_hit: the hit probability of the label at hit_iou at which a session stops (update_labels); metrics['sessions'] then also
     holds label_path, label_conf_path and label_hit_path.
+    select_by / descriptors / diversity_init: 'kcenter' asks a diverse half of the ranking instead of its top half (update_labels);
+    the descriptors default to dataset.clip_descriptors(), computed once per call; metrics['diversity'] then holds kcenter_picked,
+    kcenter_dist and cover_radius.
     soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
     blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
     DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
@@ -1730,9 +1839,13 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
                     soft_out=soft, answer_noise=answer_noise, annotator_flip=annotator_flip, questions_per_clip=questions_per_clip,
                     stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate, questions_at_once=questions_at_once,
                     hit_iou=hit_iou, stop_hit=stop_hit)
+    if select_by is not None or descriptors is not None or diversity_init is not None:      # (a round without them: the call it was)
+        if select_by == 'kcenter' and descriptors is None:
+            descriptors = dataset.clip_descriptors()
+        switches.update(select_by=select_by, descriptors=descriptors, diversity_init=diversity_init)
     pol = check_round(**switches)                                # (on every rank, before rank 0 goes its own way)
-    want_debug = pol.Q > 1 or pol.questions_at_once > 1 or calibrate is not None
-    new_data = sessions = designs = calibration = None
+    want_debug = pol.Q > 1 or pol.questions_at_once > 1 or calibrate is not None or pol.select_by is not None
+    new_data = sessions = designs = calibration = diversity = None
     if rank == 0:
         new_data = update_labels(data_old, data_gt, last_prop, get_coff(task, I), device=model.device, mc_stat=mc_stat,
                                  return_debug=want_debug, **switches)
@@ -1744,6 +1857,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
                         + (('label_path', 'label_conf_path', 'label_hit_path') if pol.stop_hit is not None else ())}
         if pol.questions_at_once > 1:
             designs = {k: dbg[k] for k in ('design', 'design_info', 'n_design', 'design_stop')}
+        if pol.select_by is not None:
+            diversity = {k: dbg[k] for k in ('kcenter_picked', 'kcenter_dist', 'cover_radius')}
     new_data = hdist.broadcast_object(new_data)
     if soft is not None:
         weighted = soft['live'] & soft['answered']
@@ -1791,6 +1906,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         m['designs'] = designs
     if calibrate is not None:
         m['calibration'] = calibration
+    if diversity is not None:
+        m['diversity'] = diversity
     if log and rank == 0:
         log('round %d: update_label %.3f s | train %d steps %.3f s (%.0f clips/s) | infer_trainset %.3f s | pseudo-label '
             'R1@0.5 %.2f mIoU %.2f' % (I, m['update_s'], steps, m['train_s'], m['clips_per_s'], m['infer_s'], r5, mi))

@@ -125,6 +125,14 @@ class DeviceDataset:
         self.ds = lib.hual_dataset(p(self.feat_bank), p(self.feat_off), self.vdim, p(self.sample_vid), p(self.word_off),
                                    p(self.word_bank), p(self.char_off), p(self.char_bank), p(self.s_ind), p(self.e_ind))
 
+    def clip_descriptors(self, normalize=True):
+        """one descriptor per SAMPLE for the core-set selection (al.diverse_select): float32 [N, vdim] on the device, the mean over
+        the frames of the sample's video of the raw features in the bank (lib.clip_mean_features, one launch over the videos), with
+        normalize scaled to unit L2 norm, gathered by sample_vid.  Samples of one video hold bit-equal rows - intended: their
+        distances are exact zeros, and the selection's second key then decides among them."""
+        per_video = lib.clip_mean_features(self.feat_bank, self.feat_off, normalize=normalize)
+        return per_video.index_select(0, self.sample_vid.long())
+
     def batch_shape(self, sel):
         """(T, L, C) of the batch: maxima of its lengths, as the reference's padding produces them"""
         sel = np.asarray(sel)

@@ -187,6 +187,10 @@ def load():
     lib.hual_al_ensemble_label.argtypes = [P(hual_al_set), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.hual_assemble_batch_soft.argtypes = lib.hual_assemble_batch_carry.argtypes[:-1] + [P(hual_soft_labels), vp]
     lib.hual_assemble_batch_cursor_soft.argtypes = lib.hual_assemble_batch_cursor.argtypes[:-1] + [P(hual_soft_labels), vp]
+    lib.hual_clip_mean_features.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
+    lib.hual_kcenter_workspace_bytes.restype = ctypes.c_uint64
+    lib.hual_kcenter_workspace_bytes.argtypes = [i32]
+    lib.hual_kcenter_greedy.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp]
     _lib = lib
     return lib
 
@@ -917,3 +921,105 @@ def al_design(aset, s0, e0, tlen, mmax, sel=None, forced=None, min_gain=0.0, sto
     out = _span_out('al_design', out, dev, N=N, M=mmax)
     _launch('hual_al_design', aset, s0, e0, sel, nsel, mmax, forced, float(min_gain), float(stop_entropy), *out)
     return out
+
+
+# ---------------------------------------------------------------- core-set clip selection
+KCENTER_MAX_D = 4096        # columns of hual_kcenter_greedy's x and of hual_clip_mean_features' bank
+
+
+def clip_mean_features(feat_bank, feat_off, normalize=True, out=None):
+    """one descriptor per video of a resident feature bank (hual_clip_mean_features), one launch enqueued on the current stream.
+    feat_bank: device f32 [frames, vdim], contiguous; feat_off: device i64 [V + 1], the frames of video v are the rows
+    feat_off[v] .. feat_off[v + 1] (DeviceDataset.feat_bank / feat_off).  -> f32 [V, vdim]: the mean over the video's frames, with
+    normalize divided by its L2 norm (a zero row stays zero).  out: a contiguous device f32 [V, vdim] to write into instead."""
+    import torch
+    who = 'clip_mean_features'
+    if not (torch.is_tensor(feat_bank) and feat_bank.dtype == torch.float32 and feat_bank.dim() == 2 and feat_bank.is_contiguous()):
+        raise HualError(who + ': feat_bank must be a contiguous float32 [frames, vdim] tensor')
+    dev, vdim = feat_bank.device, int(feat_bank.shape[1])
+    if not (torch.is_tensor(feat_off) and feat_off.dtype == torch.int64 and feat_off.dim() == 1 and feat_off.numel() >= 2
+            and feat_off.is_contiguous() and feat_off.device == dev):
+        raise HualError(who + ': feat_off must be a contiguous int64 [V + 1] tensor on the bank\'s device, V >= 1')
+    if not 1 <= vdim <= KCENTER_MAX_D:
+        raise HualError(who + ': vdim must lie in [1, %d]' % KCENTER_MAX_D)
+    V = int(feat_off.numel()) - 1
+    if out is None:
+        out = torch.empty(V, vdim, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (V, vdim) and out.is_contiguous() and out.device == dev):
+        raise HualError(who + ': out must be a contiguous float32 [%d, %d] tensor on the bank\'s device' % (V, vdim))
+    check(load().hual_clip_mean_features(ptr(feat_bank), ptr(feat_off), V, vdim, int(bool(normalize)), ptr(out), vdim, stream_ptr()))
+    return out
+
+
+def kcenter_workspace_bytes(N):
+    return int(load().hual_kcenter_workspace_bytes(int(N)))
+
+
+def kcenter_select(x, n_select, weight=None, init=None, out=None, workspace=None, validate=True):
+    """core-set selection: n_select greedy k-center picks among the rows of x, weighted by `weight` (hual_kcenter_greedy: 2 + n_init +
+    n_select launches enqueued on the current stream by one call, nothing synchronised).  x: device f32 [N, D], 1 <= D <= 4096, its
+    rows contiguous (a row stride above D is taken as it is); weight: device f32 [N] (None: every weight 1; a negative or NaN weight:
+    never picked); init: the rows that are centers before the first pick - a HOST sequence or array of ints, checked here (in [0, N),
+    no repeats: ValueError) and uploaded, or a device int32 tensor, read back for the same check; n_select in [0, N].
+    -> (picked i32 [n_select], pick_dist f32 [n_select], mind f32 [N], assign i32 [N]): step s picks the eligible row of maximal
+    (weight * mind, weight, -index), mind the squared distance to the nearest center so far; picked = -1 and pick_dist = -1 once no
+    eligible row is left; mind / assign account for every center on return (assign: the row index of the nearest center).  out: such
+    a tuple of contiguous device tensors to write into instead.  n_select = 0 launches and writes nothing (tensors allocated here then
+    hold +inf in mind and -1 in assign).  workspace: a device uint8 tensor of at least kcenter_workspace_bytes(N) bytes to reuse.
+    validate=False: a device int32 init is taken as it is, without the read-back - for a graph capture, where nothing can be read back
+    (the kernel range-checks every index itself: a row outside [0, N) is skipped there)."""
+    import numpy as np
+    import torch
+    who = 'kcenter_select'
+    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and x.stride(1) == 1
+            and x.stride(0) >= x.shape[1]):
+        raise HualError(who + ': x must be a float32 [N, D] tensor with contiguous rows, N >= 1')
+    N, D, dev = int(x.shape[0]), int(x.shape[1]), x.device
+    if D > KCENTER_MAX_D:
+        raise HualError(who + ': D must lie in [1, %d]' % KCENTER_MAX_D)
+    if isinstance(n_select, bool) or int(n_select) != n_select or not 0 <= int(n_select) <= N:
+        raise ValueError(who + ': n_select must be an integer in [0, N] = [0, %d]' % N)
+    n_select = int(n_select)
+    if weight is not None and not (torch.is_tensor(weight) and weight.dtype == torch.float32 and tuple(weight.shape) == (N,)
+                                   and weight.is_contiguous() and weight.device == dev):
+        raise HualError(who + ': weight must be a contiguous float32 [N] tensor on x\'s device')
+    init_d, n_init = None, 0
+    if not validate:                                             # (inside a graph capture nothing can be read back or uploaded)
+        if init is not None and not (torch.is_tensor(init) and init.dtype == torch.int32 and init.dim() == 1 and init.is_contiguous()
+                                     and init.device == dev and init.numel() <= N):
+            raise HualError(who + ': validate=False takes init as a contiguous device int32 [n_init <= N] tensor')
+        init_d, n_init = (init, int(init.numel())) if init is not None and init.numel() else (None, 0)
+    elif init is not None:
+        init_h = init.cpu().numpy() if torch.is_tensor(init) else np.asarray(init)
+        if init_h.ndim != 1 or (init_h.size and init_h.dtype.kind not in 'iu'):
+            raise ValueError(who + ': init must be a one-dimensional sequence of row indices')
+        init_h = init_h.astype(np.int64)
+        if init_h.size and (init_h.min() < 0 or init_h.max() >= N):
+            raise ValueError(who + ': init holds a row outside [0, N) = [0, %d)' % N)
+        if len(np.unique(init_h)) != init_h.size:
+            raise ValueError(who + ': init holds a row twice')
+        n_init = int(init_h.size)
+        if n_init:
+            init_d = (init if torch.is_tensor(init) and init.dtype == torch.int32 and init.is_contiguous() and init.device == dev
+                      else torch.from_numpy(init_h.astype(np.int32)).to(dev))
+    if out is None:
+        out = (torch.full((n_select,), -1, dtype=torch.int32, device=dev), torch.full((n_select,), -1.0, dtype=torch.float32, device=dev),
+               torch.full((N,), float('inf'), dtype=torch.float32, device=dev), torch.full((N,), -1, dtype=torch.int32, device=dev))
+    else:
+        spec = (('picked', torch.int32, (n_select,)), ('pick_dist', torch.float32, (n_select,)), ('mind', torch.float32, (N,)),
+                ('assign', torch.int32, (N,)))
+        if len(out) != 4:
+            raise HualError(who + ': out is (picked, pick_dist, mind, assign)')
+        for o, (name, dt, shape) in zip(out, spec):
+            if not (torch.is_tensor(o) and o.dtype == dt and tuple(o.shape) == shape and o.is_contiguous() and o.device == dev):
+                raise HualError('%s: %s must be a contiguous %s %s on x\'s device' % (who, name, str(dt).replace('torch.', ''), list(shape)))
+        out = tuple(out)
+    need = kcenter_workspace_bytes(N)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (torch.is_tensor(workspace) and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= need
+              and workspace.device == dev and workspace.data_ptr() % 16 == 0):
+        raise HualError(who + ': workspace must be a contiguous 16-byte aligned uint8 tensor of at least %d bytes on x\'s device' % need)
+    check(load().hual_kcenter_greedy(ptr(x), N, D, int(x.stride(0)), ptr(weight), ptr(init_d), n_init, n_select, ptr(out[0]), ptr(out[1]),
+                                     ptr(out[2]), ptr(out[3]), ptr(workspace), int(workspace.numel()), stream_ptr()))
+    return out      # (a workspace allocated here goes back to the caching allocator in stream order: behind the launches)

@@ -1099,6 +1099,60 @@ int hual_al_hit_label(const hual_al_set* set, const float* s0, const float* e0, 
                       int M, const int32_t* cand_idx, int k, float* cand_hit, int32_t* best_idx, float* best_prob, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Core-set clip selection: greedy k-center in a feature space, weighted by a score (HUAL_ABI_VERSION unchanged: three new symbols,
+ * nothing else moved).  Every launch above sharpens WHAT a clip is asked; this family decides WHICH clips are asked, as a set: a
+ * top half by score may spend a round on near-duplicate clips of a few hard videos, greedy k-center spreads it over the feature
+ * space.
+ *
+ * hual_clip_mean_features: one descriptor per video of a resident feature bank (hual_dataset's feat_bank f32 [frames, vdim] and
+ * feat_off i64 [V + 1]: the frames of video v are the rows feat_off[v] .. feat_off[v + 1]).  out f32 [V, vdim] with row stride ld_out
+ * >= vdim: the mean over the video's frames, a column's frames added in float32 in ascending frame order and divided by the count
+ * (a video without frames: a zero row); with normalize != 0 every row is then divided by its L2 norm (summed in float64), a zero row
+ * stays zero.  One workgroup per video, the bank read exactly once with loads coalesced along vdim; a fixed order, no atomics: a
+ * second launch returns equal bits.  Argument errors (a null pointer, V < 1, vdim outside [1, 4096], ld_out < vdim) return
+ * HUAL_ERR_INVALID before any HIP call. */
+int hual_clip_mean_features(const float* feat_bank, const int64_t* feat_off, int V, int vdim, int normalize, float* out, int ld_out,
+                            void* stream);
+
+/* hual_kcenter_greedy: n_select picks among the N rows of x, all enqueued on `stream` by this one call, no host synchronisation
+ * between the steps.
+ * Inputs: x f32 [N, D] with row stride ld >= D, 1 <= D <= 4096; weight f32 [N] or NULL (every weight 1); init i32 [n_init] ON THE
+ * DEVICE, rows that are centers before the first pick (n_init == 0: may be NULL); 0 <= n_select <= N; workspace: caller-owned,
+ * 16-byte aligned, at least hual_kcenter_workspace_bytes(N) bytes, contents irrelevant on entry.
+ * Outputs: picked i32 [n_select], pick_dist f32 [n_select], mind f32 [N], assign i32 [N].
+ *  - Distance: d(i, c) = sum_k (x[i,k] - x[c,k])^2 in float32.  The columns are dealt to the 64 lanes of one wave in chunks of four
+ *    (chunk k / 4 to lane (k / 4) % 64, ascending) and the lanes' sums are folded by one butterfly: the order depends on D alone, not
+ *    on where row i sits in the grid, so two bit-equal rows get bit-equal distances to every center.
+ *  - State: mind[i] is the minimum of d(i, c) over the centers so far - the init rows in their order, then the picks -, +inf while
+ *    there is none; assign[i] is the ROW INDEX of the first center in that order that attains it (a strictly smaller distance
+ *    replaces), -1 while there is none.  A NaN distance makes mind[i] NaN and leaves assign[i].
+ *  - Eligibility: a row is eligible when it is not in init, has not been picked, its weight is >= 0 (a negative or NaN weight means
+ *    "never ask"), its score is not NaN, and all its features are finite (d(i, i) == 0: a row that holds a NaN or an infinity is
+ *    never picked, also while there is no center, and changes no other row's state).
+ *  - Step s: score[i] = w[i] * mind[i]; while there is no center, score[i] = w[i].  The pick is the eligible row of maximal (score,
+ *    w, -i) in lexicographic order: the largest score, then the larger weight, then the lower index.  Duplicate descriptors give
+ *    exact zeros and exact ties, and the second key then sends the ask to the row the ranking prefers.
+ *  - picked[s] is that row, pick_dist[s] its mind before the pick (+inf for a first pick without centers).  When no eligible row is
+ *    left, picked[s] = -1 and pick_dist[s] = -1.0f for this and every later step.
+ *  - On return mind and assign account for every center, the last pick included.
+ * n_select == 0 returns at once: nothing is launched and nothing is written.
+ * Launches: an opening launch (the state, and the finite test of every row), one update-only launch per init row, one launch per
+ * step and one closing update - 2 + n_init + n_select in all, each over ceil(N / 16) workgroups.  A step stages the newest center's
+ * row in LDS, updates the rows it owns (one wave per row), reduces their keys to one partial per workgroup, publishes it with an
+ * agent-scope release and draws a ticket from a device-scope counter; the workgroup that draws the last ticket reduces the partials
+ * behind an agent-scope acquire, writes picked[s] / pick_dist[s], marks the row taken and returns the counter to zero.  No workgroup
+ * ever waits for another one: nothing polls, no grid barrier, no cooperative launch.  The keys are a total order, so the pick does
+ * not depend on arrival order: a second call returns equal bits.  Every index read from device memory (picked[s - 1], init[j]) is
+ * range-checked in the kernel before it becomes a row number: outside [0, N) - the -1 of an exhausted selection - the update is a
+ * no-op.  Allocates nothing and does not synchronise: capturable in a hipGraph.  Argument errors (a null pointer other than weight,
+ * and init with n_init == 0; N < 1; D outside [1, 4096]; ld < D; n_select outside [0, N]; n_init outside [0, N]; a workspace that is
+ * too small or misaligned) return HUAL_ERR_INVALID before any HIP call. */
+uint64_t hual_kcenter_workspace_bytes(int N);
+int hual_kcenter_greedy(const float* x, int N, int D, int ld, const float* weight, const int32_t* init, int n_init, int n_select,
+                        int32_t* picked, float* pick_dist, float* mind, int32_t* assign, void* workspace, uint64_t workspace_bytes,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
  * kernel launch carries its own start / stop events (hipExtLaunchKernelGGL: the begin / end timestamps of that
  * kernel's dispatch, the quantity rocprofv3 --kernel-trace reports).  hual_prof_end() synchronises those events (the
