@@ -290,8 +290,71 @@ def attach_uncert(records, rows, bank, K, stat):
 
 
 # ---------------------------------------------------------------- infer_trainset ----------------
+GRAD_HYP = ('prediction', 'pseudo')
+
+
+class GradBank:
+    """the gradient embeddings of a whole training set on the device (hual_al_grad_embed): desc f32 [N, 256] - the gradient of the
+    localizing loss with respect to the start_dense / end_dense kernels under a hypothesised span, columns 0..127 g_s and 128..255
+    g_e -, gnorm2 f32 [N] its squared length and egl f32 [N] the expected squared gradient length under y ~ p.  infer_trainset(grad_bank=)
+    writes the rows of the samples it sees, one launch per batch; a row nobody wrote holds zeros.  desc is the descriptor space of
+    badge_select / update_labels(select_by='badge'), egl the scalar of rank_by='egl'."""
+
+    def __init__(self, N, device='cuda:0'):
+        N = int(N)
+        if N < 1:
+            raise ValueError('GradBank: N >= 1')
+        self.N, self.device = N, torch.device(device)
+        self.desc = torch.zeros(N, lib.GRAD_EMBED_DIM, dtype=torch.float32, device=self.device)
+        self.gnorm2 = torch.zeros(N, dtype=torch.float32, device=self.device)
+        self.egl = torch.zeros(N, dtype=torch.float32, device=self.device)
+
+    @classmethod
+    def for_dataset(cls, dataset, device=None):
+        return cls(len(dataset), device=dataset.dev if device is None else device)
+
+    def rows(self, ids):
+        """the bank rows of the samples `ids` as the launch reads them: device int32, range-checked here"""
+        ids = np.asarray(ids, dtype=np.int64)
+        if ids.ndim != 1 or (ids.size and (ids.min() < 0 or ids.max() >= self.N)):
+            raise ValueError('GradBank: sample ids outside [0, %d)' % self.N)
+        return torch.from_numpy(ids.astype(np.int32)).to(self.device)
+
+    def embed(self, model, out, lens, rows, hyp):
+        """one hual_al_grad_embed launch on the label-free forward `model` has just run (`out`: its fetches): reads model.tap('head.hs')
+        / ('head.he') in place where the workspace table shows that nothing else lives in their bytes, else copies of them made in the
+        forward's stream.  hyp: device int32 [B, 2]."""
+        taps, private = _head_taps(model)
+        if not private:
+            taps = tuple(t.clone() for t in taps)
+        return lib.al_grad_embed(taps[0], taps[1], out['start_logits'], out['end_logits'], lens, hyp, self.desc, self.gnorm2, self.egl,
+                                 rows=rows)
+
+
+def _head_taps(model):
+    """-> ((head.hs, head.he) views of the workspace, private): private is False when another entry of hual_seqpan_ws_table overlaps
+    the bytes of either - a later launch of the same forward could then have overwritten them, and a reader must copy them out in the
+    forward's stream.  The table gives every named buffer its own range today, so the views are read in place."""
+    table = model._ws_table
+    private = True
+    for name in ('head.hs', 'head.he'):
+        off, rows, cols = table[name]
+        end = off + rows * cols * 4
+        for other, (o2, r2, c2) in table.items():
+            if other != name and o2 < end and off < o2 + r2 * c2 * 4:
+                private = False
+    return (model.tap('head.hs'), model.tap('head.he')), private
+
+
+def attach_grad(records, rows, grad_bank):
+    """records[j]['prop_egl'] / ['prop_gnorm2'] = the floats of bank row rows[j], read from the bank once"""
+    egl, gn = grad_bank.egl.cpu().numpy(), grad_bank.gnorm2.cpu().numpy()
+    for r, n in zip(records, rows):
+        r['prop_egl'], r['prop_gnorm2'] = float(egl[n]), float(gn[n])
+
+
 def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc_samples=None, bank=None, sample_ids=None,
-                   mc_stat='range', _attach=True, span_conf=False):
+                   mc_stat='range', _attach=True, span_conf=False, grad_bank=None, grad_hyp='prediction'):
     """eval_test_save (runner_utils.py:69-110) without the file write: returns (records, ious).
 
     batches: iterable of (raw_records, video, video_seq_len, word_ids, char_ids) as TestLoader.test_iter yields them
@@ -309,9 +372,22 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
     span_conf=True: every record gains 'prop_conf' (float: the expected temporal IoU of its own prop_idx under the span distribution of
     the deterministic pass, -1.0 where the forward gave no span) and 'prop_span_entropy' (float, bits): one hual_span_expected_iou
     launch per batch with k = 1 on the forward's start_index / end_index, fetched with the five deterministic fetches.
+    grad_bank: None (every launch and record as without the argument), or a GradBank over the whole set - after the deterministic
+    forward of a batch one hual_al_grad_embed launch writes the bank rows sample_ids[i] (default: arrival order) from the forward's
+    head.hs / head.he, its logits and the hypothesis grad_hyp: 'prediction' (the forward's own start_index / end_index - BADGE's
+    hypothesised label) or 'pseudo' (the records' s_ind / e_ind).  The records gain 'prop_egl' and 'prop_gnorm2' (floats, -1.0 for a
+    sample whose logits are not finite), read from the bank once at the end.  Single process only.
     """
     from . import data
     records, ious = [], []
+    if grad_hyp not in GRAD_HYP:
+        raise ValueError("grad_hyp: 'prediction' or 'pseudo'")
+    if grad_bank is not None:
+        from . import dist as hdist
+        if not isinstance(grad_bank, GradBank):
+            raise ValueError('grad_bank: a GradBank over the whole training set')
+        if hdist.world_size() > 1:
+            raise ValueError('grad_bank is single-process only: the rows of other ranks are not gathered')
     K = None
     if mc_samples is not None:
         K = int(mc_samples)
@@ -340,10 +416,18 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
         if span_conf:
             nb = o['start_index'].numel()
             conf = lib.span_expected_iou(o['start_logits'], o['end_logits'], lens, o['start_index'].view(nb, 1), o['end_index'].view(nb, 1))
-        if K is not None:
+        if K is not None or grad_bank is not None:
             n0 = sum(len(x) for x in rows_seen)
             ids = np.asarray(next(sample_ids)) if sample_ids is not None else np.arange(n0, n0 + len(raw))
             rows_seen.append(ids)
+        if grad_bank is not None:                                # (before the stochastic forwards overwrite the workspace, in stream order)
+            if grad_hyp == 'prediction':
+                hyp = torch.stack([o['start_index'], o['end_index']], dim=1).to(torch.int32)
+            else:
+                hyp = torch.tensor([[int(r['s_ind']), int(r['e_ind'])] for r in raw], dtype=torch.int32).to(model.device)
+            lens_d = lens if torch.is_tensor(lens) and lens.is_cuda and lens.dtype == torch.int32 else model._to_dev(lens, torch.int32)
+            grad_bank.embed(model, o, lens_d, grad_bank.rows(ids), hyp)
+        if K is not None:
             rows = bank.rows(ids)
             bank.fold(rows, lens, o['start_logits'], o['end_logits'], 0, _checked=True)
         if P and rng_base is not None:
@@ -399,11 +483,13 @@ def infer_trainset(model, batches, mc_dropout=None, batch_ids=None, rng=None, mc
         emit(pending)
     if K is not None and _attach and records:
         attach_uncert(records, np.concatenate(rows_seen), bank, K, mc_stat)
+    if grad_bank is not None and records:
+        attach_grad(records, np.concatenate(rows_seen), grad_bank)
     return records, ious
 
 
 def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_chars=4, mc_samples=None, bank=None, mc_stat='range',
-                           span_conf=False):
+                           span_conf=False, grad_bank=None, grad_hyp='prediction'):
     """infer_trainset over a DeviceDataset in the reference's order (TrainNoSuffleLoader.test_iter, data_loader.py:167-206), the
     batches dealt round-robin to the ranks of the process group (batch i -> rank i % world; every rank holds the whole set):
     rank 0 returns (records, ious) of the WHOLE set in sample order, the other ranks (None, None).  One rank: the plain pass.
@@ -413,9 +499,13 @@ def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_char
     info=True when mc_stat is 'bald', 'entropy' or 'expected_entropy'); the
     rows of the other ranks reach rank 0's bank with the records (disjoint rows: copied, never reduced), and rank 0 reads
     'prop_uncert' from the gathered bank.  Every rank's own stream advances by K * n_batches.
-    span_conf: as infer_trainset (the two floats travel with the records)."""
+    span_conf: as infer_trainset (the two floats travel with the records).
+    grad_bank / grad_hyp: as infer_trainset, the rows being the samples' positions in the set; one process only (ValueError under a
+    process group of more, like soft labels)."""
     from . import dist as hdist
     world, rank = hdist.world_size(), hdist.rank()
+    if grad_bank is not None and world > 1:
+        raise ValueError('grad_bank is single-process only: the rows of other ranks are not gathered')
     N = len(dataset)
     los = list(range(0, N, batch_size))
     own = [i for i in range(len(los)) if i % world == rank]
@@ -432,7 +522,8 @@ def infer_trainset_sharded(model, dataset, batch_size, mc_dropout=None, min_char
     if K is not None and bank is None:
         bank = McBank.for_dataset(dataset, device=model.device, info=mc_stat in lib.AL_STAT_INFO)
     records, ious = infer_trainset(model, batches(), mc_dropout=mc_dropout, batch_ids=own, rng=rng, mc_samples=mc_samples, bank=bank,
-                                   sample_ids=own_rows if K is not None else None, mc_stat=mc_stat, _attach=False, span_conf=span_conf)
+                                   sample_ids=own_rows if K is not None or grad_bank is not None else None, mc_stat=mc_stat, _attach=False,
+                                   span_conf=span_conf, grad_bank=grad_bank, grad_hyp=grad_hyp)
     # every rank returns to its OWN dropout stream, behind the whole pass
     model.set_rng(own_rng[0], own_rng[1] + ((2 if K is None else K) * len(los) if mc_dropout is not None else 0))
     part = None
@@ -1201,6 +1292,7 @@ POSTERIOR = ('deterministic', 'ensemble')
 RANK_BY = ('uncert_video', 'span_risk')
 RANK_BY_ENSEMBLE = ('span_bald',)      # with posterior='ensemble' only (check_round)
 RANK_BY_HIT = ('label_miss',)          # label reliability (LabelUpdater.hit_label): the deterministic posterior only
+RANK_BY_GRAD = ('egl',)                # the expected gradient length of the records (infer_trainset(grad_bank=)), largest first
 OBSERVE_BY = ('uncert_frame', 'info_gain')
 RENEW_BY = ('heuristic', 'posterior')
 RENEW_BY_HIT = ('hit_prob',)           # the same
@@ -1220,21 +1312,24 @@ _RoundFields = collections.namedtuple('RoundPolicy', 'posterior rank_by observe_
 class RoundPolicy(_RoundFields):
     """the tuple of a round's switches, and beside it - attributes, not fields: the tuple of a round without them is the tuple it
     was - stop_hit: None, or the hit probability of the label at hit_iou at which a session stops; select_by / descriptors /
-    diversity_init: how the asked half is chosen from the ranking (None: its top half; 'kcenter': diverse_select on the descriptors,
-    with diversity_init='answered' around the clips that already hold an active point)"""
+    diversity_init: how the asked half is chosen from the ranking (None: its top half; 'kcenter': diverse_select on the descriptors;
+    'badge': badge_select on them - D^2 sampling from the origin under selection_seed; with diversity_init='answered' around the
+    clips that already hold an active point)"""
     stop_hit = None
     select_by = None
     descriptors = None
     diversity_init = None
+    selection_seed = None
 
-    def __new__(cls, *fields, stop_hit=None, select_by=None, descriptors=None, diversity_init=None):
+    def __new__(cls, *fields, stop_hit=None, select_by=None, descriptors=None, diversity_init=None, selection_seed=None):
         pol = super().__new__(cls, *fields)
         pol.stop_hit = stop_hit
         pol.select_by, pol.descriptors, pol.diversity_init = select_by, descriptors, diversity_init
+        pol.selection_seed = selection_seed
         return pol
 
 
-SELECT_BY = (None, 'kcenter')
+SELECT_BY = (None, 'kcenter', 'badge')
 DIVERSITY_INIT = (None, 'answered')
 
 
@@ -1288,25 +1383,61 @@ def diverse_select(desc, order, n_select, weighted=True, init=None):
     return _diverse(desc, order, n_select, weighted=weighted, init=init)[0]
 
 
+def _badge(desc, n_select, weight=None, init=None, seed=0, sample=True, origin=True):
+    """badge_select's launch -> (picks without the -1 of an exhausted selection, picked, pick_dist, mind: the launch's tensors)"""
+    if not (torch.is_tensor(desc) and desc.dim() == 2 and desc.dtype == torch.float32):
+        raise ValueError('descriptors: a float32 [N, D] device tensor')
+    N = int(desc.shape[0])
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError('seed: an integer in [0, 2^64)')
+    if weight is not None:
+        weight = np.asarray(weight, dtype=np.float32)
+        if weight.shape != (N,):
+            raise ValueError('weight: %d floats for %d descriptors' % (weight.size, N))
+        weight = torch.from_numpy(np.ascontiguousarray(weight)).to(desc.device)
+    init = None if init is None or len(init) == 0 else np.asarray(init, dtype=np.int64)
+    picked, dist, mind, _ = lib.kcenter_sample(desc, n_select, weight=weight, init=init, seed=int(seed), sample=sample, origin=origin)
+    picks = picked.cpu().numpy().astype(np.int64)
+    return picks[picks >= 0], picked, dist, mind
+
+
+def badge_select(desc, n_select, weight=None, init=None, seed=0, sample=True, origin=True):
+    """batch selection in a gradient-embedding space (BADGE, Ash et al. 2020): n_select picks by k-means++ seeding - step s draws a
+    row with probability proportional to its squared distance to the nearest pick so far (lib.kcenter_sample, one call).  desc:
+    device f32 [N, D] (GradBank.desc, or any descriptors).  origin: the zero vector is a center before the first pick, so the first
+    draw is proportional to the squared gradient length - a sample the model is certain of sits at the origin and is never drawn
+    while others remain.  sample=False: greedy k-center instead of the draw (with origin: the largest gradient first).  weight: None,
+    or N floats (host) that multiply the squared distances; init: rows (host ints, in [0, N), no repeats: ValueError) that count as
+    asked already; seed: an int in [0, 2^64) - the same seed gives the same picks, bit for bit.  A NaN descriptor row is never picked.
+    -> (sel, picked, dist, mind): sel the picks as a numpy int array in pick order, shorter than n_select when the eligible rows run
+    out; picked i32 [n_select] (-1 past their end), dist f32 [n_select] and mind f32 [N] the launch's device tensors."""
+    return _badge(desc, n_select, weight=weight, init=init, seed=seed, sample=sample, origin=origin)
+
+
 def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='uncert_video', observe_by='uncert_frame',
                 renew_by='heuristic', acquire_by=None, soft_out=None, answer_noise=None, annotator_flip=None, questions_per_clip=1,
                 stop_entropy=None, temperature=None, calibrate=None, questions_at_once=1, hit_iou=0.7, stop_hit=None, select_by=None,
-                descriptors=None, diversity_init=None):
+                descriptors=None, diversity_init=None, selection_seed=None):
     """every rule between the switches of update_labels / run_round (their docstrings say what each switch does) -> RoundPolicy;
     raises ValueError, and touches nothing"""
     # the selection: the ranking's top half, or a diverse half of it
     if select_by not in SELECT_BY:
-        raise ValueError("select_by: None or 'kcenter'")
+        raise ValueError("select_by: None, 'kcenter' or 'badge'")
     if select_by is None and descriptors is not None:
-        raise ValueError("descriptors without select_by='kcenter': nothing reads them")
+        raise ValueError("descriptors without select_by='kcenter' or 'badge': nothing reads them")
     if select_by is None and diversity_init is not None:
-        raise ValueError("diversity_init without select_by='kcenter': nothing reads it")
+        raise ValueError("diversity_init without select_by='kcenter' or 'badge': nothing reads it")
     if diversity_init not in DIVERSITY_INIT:
         raise ValueError("diversity_init: None or 'answered'")
-    if select_by == 'kcenter' and not (torch.is_tensor(descriptors) and descriptors.dim() == 2 and descriptors.dtype == torch.float32
-                                       and 1 <= descriptors.shape[1] <= lib.KCENTER_MAX_D and descriptors.shape[0] >= 1):
-        raise ValueError("select_by='kcenter' needs descriptors: a float32 [N, D] device tensor, 1 <= D <= %d "
-                         "(DeviceDataset.clip_descriptors())" % lib.KCENTER_MAX_D)
+    if select_by is not None and not (torch.is_tensor(descriptors) and descriptors.dim() == 2 and descriptors.dtype == torch.float32
+                                      and 1 <= descriptors.shape[1] <= lib.KCENTER_MAX_D and descriptors.shape[0] >= 1):
+        raise ValueError("select_by='%s' needs descriptors: a float32 [N, D] device tensor, 1 <= D <= %d "
+                         "(DeviceDataset.clip_descriptors(), GradBank.desc)" % (select_by, lib.KCENTER_MAX_D))
+    if selection_seed is not None and select_by != 'badge':
+        raise ValueError("selection_seed without select_by='badge': nothing draws")
+    if selection_seed is not None and (isinstance(selection_seed, bool) or not isinstance(selection_seed, (int, np.integer))
+                                       or not 0 <= int(selection_seed) < 1 << 64):
+        raise ValueError('selection_seed: None or an integer in [0, 2^64)')
     readers = {"observe_by='info_gain'": observe_by == 'info_gain', "acquire_by='label_gain'": acquire_by == 'label_gain',
                "renew_by='posterior'": renew_by == 'posterior', 'soft_out': soft_out is not None, "rank_by='span_bald'": rank_by == 'span_bald',
                "rank_by='label_miss'": rank_by == 'label_miss', "renew_by='hit_prob'": renew_by == 'hit_prob'}
@@ -1388,8 +1519,8 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
             raise ValueError('annotator_flip: None or (rate in [0, 1], numpy.random.Generator)')
         annotator_flip = (float(annotator_flip[0]), annotator_flip[1])
     # ranking and the question: acquire_by decides both
-    if rank_by not in RANK_BY + RANK_BY_HIT and not (posterior == 'ensemble' and rank_by in RANK_BY_ENSEMBLE):
-        raise ValueError("rank_by: 'uncert_video', 'span_risk' or 'label_miss' ('span_bald' with posterior='ensemble')")
+    if rank_by not in RANK_BY + RANK_BY_HIT + RANK_BY_GRAD and not (posterior == 'ensemble' and rank_by in RANK_BY_ENSEMBLE):
+        raise ValueError("rank_by: 'uncert_video', 'span_risk', 'label_miss' or 'egl' ('span_bald' with posterior='ensemble')")
     if observe_by not in OBSERVE_BY:
         raise ValueError("observe_by: 'uncert_frame' or 'info_gain'")
     if renew_by not in RENEW_BY + RENEW_BY_HIT:
@@ -1404,7 +1535,14 @@ def check_round(posterior='deterministic', bank=None, mc_samples=None, rank_by='
     return RoundPolicy(posterior, rank_by, observe_by, renew_by, acquire_by, Q, None if stop_entropy is None else float(stop_entropy), noise,
                        None if temperature is None else float(temperature), calibrate, annotator_flip, any(readers.values()), M,
                        float(hit_iou), stop_hit=None if stop_hit is None else float(stop_hit), select_by=select_by, descriptors=descriptors,
-                       diversity_init=diversity_init)
+                       diversity_init=diversity_init, selection_seed=None if selection_seed is None else int(selection_seed))
+
+
+def grad_length(last_prop):
+    """prop_egl of every record (float64 [N]): the expected squared gradient length of the localizing loss at the span heads"""
+    if not all('prop_egl' in p for p in last_prop):
+        raise ValueError("rank_by='egl' needs records that hold 'prop_egl': run infer_trainset(grad_bank=)")
+    return np.array([float(p['prop_egl']) for p in last_prop], dtype=np.float64)
 
 
 def span_risk(last_prop):
@@ -1438,7 +1576,7 @@ def _round_calibrate(up, pol):
     return noise, dbg
 
 
-def _round_choose(up, pol, noise, risk, frames, old_idx):
+def _round_choose(up, pol, noise, risk, frames, old_idx, egl=None):
     """whom to ask and where, on the answers of the earlier rounds (before set_active_points) -> (order, the ranking of the samples;
     ask, every sample's frame)"""
     uv, observe = up.uncert_video.cpu().numpy(), up.observe.cpu().numpy()
@@ -1446,6 +1584,9 @@ def _round_choose(up, pol, noise, risk, frames, old_idx):
     order = np.argsort(uv if risk is None else risk, kind='stable')      # sorted(key=uncert_video), ties in sample order
     if risk is not None:
         dbg['span_risk'] = risk
+    if egl is not None:
+        order = np.argsort(-egl, kind='stable')                  # the longest expected gradient first, ties in sample order; rows at -1 last
+        dbg['egl'] = egl
     if pol.observe_by == 'info_gain' or pol.rank_by == 'span_bald':
         ens = up.query(frames=frames or noise is not None, noise=noise)
         if ens is not None:
@@ -1484,7 +1625,10 @@ def _round_select(pol, order, aps):
     if pol.select_by is None:
         return order[:n_select], {}
     init = [i for i, a in enumerate(aps) if len(a)] if pol.diversity_init == 'answered' else None
-    sel, picked, dist, mind = _diverse(pol.descriptors, order, n_select, weighted=True, init=init)
+    if pol.select_by == 'badge':                                 # D^2 sampling from the origin: the descriptors carry the uncertainty themselves
+        sel, picked, dist, mind = _badge(pol.descriptors, n_select, init=init, seed=pol.selection_seed or 0)
+    else:
+        sel, picked, dist, mind = _diverse(pol.descriptors, order, n_select, weighted=True, init=init)
     if len(sel) < n_select:
         asked = set(sel.tolist())
         sel = np.concatenate([sel, np.array([i for i in order.tolist() if i not in asked][:n_select - len(sel)], dtype=np.int64)])
@@ -1608,7 +1752,7 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
                   rank_by='uncert_video', observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_out=None,
                   answer_noise=None, annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None,
                   posterior='deterministic', questions_at_once=1, hit_iou=0.7, stop_hit=None, select_by=None, descriptors=None,
-                  diversity_init=None):
+                  diversity_init=None, selection_seed=None):
     """update_label.main (update_label.py:173-208) without the file IO.
 
     data_old / data_gt: lists [vid, duration, [start_time, end_time], sentence(, active points)] as in
@@ -1725,15 +1869,24 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     the ranking, best first.  The debug dict gains 'kcenter_picked' (int [ceil(N / 2)], -1 past the end of the eligible rows),
     'kcenter_dist' (float32, the pick's squared distance to the nearest earlier center) and 'cover_radius' (float: the largest
     squared distance of any sample to its nearest asked clip).  Deterministic, so every rank of a process group gets equal picks.
+    select_by='badge': the asked half is badge_select(descriptors, ceil(N / 2), seed=selection_seed or 0) - k-means++ seeding (D^2
+    sampling) from the origin in the descriptor space, meant for gradient embeddings (GradBank.desc of the last infer_trainset): a
+    clip is drawn with probability proportional to its squared distance to the clips drawn so far, the first to its squared
+    gradient length.  The ranking takes no part in the draw; it fills the half, best first, where the eligible rows run out (a NaN
+    descriptor is never drawn).  diversity_init and the three debug entries are as under 'kcenter'.  selection_seed: an int in [0,
+    2^64) - the same seed gives the same half.
+    rank_by='egl': the samples are ranked by 'prop_egl' of their records, largest first (infer_trainset(grad_bank=); ValueError when
+    a record lacks it); the debug dict gains 'egl'.
     """
     pol = check_round(posterior=posterior, bank=bank, mc_samples=mc_samples, rank_by=rank_by, observe_by=observe_by, renew_by=renew_by,
                       acquire_by=acquire_by, soft_out=soft_out, answer_noise=answer_noise, annotator_flip=annotator_flip,
                       questions_per_clip=questions_per_clip, stop_entropy=stop_entropy, temperature=temperature, calibrate=calibrate,
                       questions_at_once=questions_at_once, hit_iou=hit_iou, stop_hit=stop_hit, select_by=select_by, descriptors=descriptors,
-                      diversity_init=diversity_init)
+                      diversity_init=diversity_init, selection_seed=selection_seed)
     if pol.select_by is not None and int(pol.descriptors.shape[0]) != len(data_old):      # (raises before anything is touched)
         raise ValueError('descriptors: %d rows for %d samples' % (int(pol.descriptors.shape[0]), len(data_old)))
     risk = span_risk(last_prop) if pol.rank_by == 'span_risk' else None      # (raises before anything is touched)
+    egl = grad_length(last_prop) if pol.rank_by == 'egl' else None           # (the same)
     if len(data_old[0]) == 4:
         for r in data_old:
             r.append({'pos_idx': [], 'neg_idx': []})
@@ -1747,7 +1900,7 @@ def update_labels(data_old, data_gt, last_prop, coff, device='cuda:0', return_de
     noise, fitted = _round_calibrate(up, pol)
     idx = dict(gt_idx=np.array([[_round_half_even_index(t, r[1], int(v)) for t in r[2]] for r, v in zip(data_gt, up.vlen_h)]),
                old_idx=np.array([[_round_half_even_index(t, r[1], int(v)) for t in r[2]] for r, v in zip(data_old, up.vlen_h)]))
-    order, ask, chosen = _round_choose(up, pol, noise, risk, return_debug, idx['old_idx'])
+    order, ask, chosen = _round_choose(up, pol, noise, risk, return_debug, idx['old_idx'], egl=egl)
     sel, diverse = _round_select(pol, order, aps)
     asked = _round_ask(up, pol, noise, sel, ask, idx['gt_idx'], data_old, aps)
     if soft_out is not None:
@@ -1776,7 +1929,7 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
               observe_by='uncert_frame', renew_by='heuristic', acquire_by=None, soft_labels=None, answer_noise=None,
               annotator_flip=None, questions_per_clip=1, stop_entropy=None, temperature=None, calibrate=None, posterior='deterministic',
               rank_by='uncert_video', questions_at_once=1, hit_iou=0.7, stop_hit=None, select_by=None, descriptors=None,
-              diversity_init=None):
+              diversity_init=None, selection_seed=None, grad_bank=None, grad_hyp='prediction'):
     """One active-learning round of run_charades.py:9-41 on device-resident data:
          update_label.py <task> I   ->  main.py --mode train (epochs)   ->  main.py --mode infer_trainset
     dataset: DeviceDataset over the training records in the SAME order as data_old / data_gt / last_prop.
@@ -1812,7 +1965,12 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     holds label_path, label_conf_path and label_hit_path.
     select_by / descriptors / diversity_init: 'kcenter' asks a diverse half of the ranking instead of its top half (update_labels);
     the descriptors default to dataset.clip_descriptors(), computed once per call; metrics['diversity'] then holds kcenter_picked,
-    kcenter_dist and cover_radius.
+    kcenter_dist and cover_radius.  select_by='badge' (with selection_seed) draws the half by D^2 sampling instead and needs
+    descriptors=: the desc of the GradBank the round before returned.
+    grad_bank: None, True or a GradBank - the round's inference then fills it (True: a GradBank.for_dataset of this call), one
+    hual_al_grad_embed launch per batch under the hypothesis grad_hyp (infer_trainset), the records gain 'prop_egl' / 'prop_gnorm2'
+    (rank_by='egl' of the next round), and metrics['grad_bank'] is the bank: the next round passes descriptors=bank.desc.  Single
+    process only.
     soft_labels: None, or a weight lam in (0, 1] - the epochs then train every sample that has an answer and a live posterior on the
     blend (weight lam) of the reference's labels with the posterior's start / end marginals (update_labels(soft_out=),
     DeviceDataset.set_soft_labels); every other sample keeps weight 0 - a clip nobody has answered about would only be trained on the
@@ -1843,6 +2001,17 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         if select_by == 'kcenter' and descriptors is None:
             descriptors = dataset.clip_descriptors()
         switches.update(select_by=select_by, descriptors=descriptors, diversity_init=diversity_init)
+    if selection_seed is not None:
+        switches.update(selection_seed=selection_seed)
+    if grad_bank is not None and grad_bank is not False:
+        if world > 1:
+            raise ValueError('grad_bank is single-process: the rows of other ranks are not gathered')
+        if grad_hyp not in GRAD_HYP:
+            raise ValueError("grad_hyp: 'prediction' or 'pseudo'")
+        if grad_bank is not True and not (isinstance(grad_bank, GradBank) and grad_bank.N == len(dataset)):
+            raise ValueError('grad_bank: None, True or a GradBank over the dataset')
+    else:
+        grad_bank = None
     pol = check_round(**switches)                                # (on every rank, before rank 0 goes its own way)
     want_debug = pol.Q > 1 or pol.questions_at_once > 1 or calibrate is not None or pol.select_by is not None
     new_data = sessions = designs = calibration = diversity = None
@@ -1887,8 +2056,13 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
     t2 = time.perf_counter()
     if mc_samples is not None and bank is None:
         bank = McBank.for_dataset(dataset, device=model.device, info=mc_stat in lib.AL_STAT_INFO)
+    grad = {}                                                    # (a round without the bank: the call it was)
+    if grad_bank is not None:
+        grad_bank = GradBank.for_dataset(dataset, device=model.device) if grad_bank is True else grad_bank
+        grad = dict(grad_bank=grad_bank, grad_hyp=grad_hyp)
     records, ious = infer_trainset_sharded(model, dataset, batch_size, mc_dropout=mc_dropout, min_chars=4, mc_samples=mc_samples,
-                                           bank=bank if mc_samples is not None else None, mc_stat=mc_stat, span_conf=span_conf)
+                                           bank=bank if mc_samples is not None else None, mc_stat=mc_stat, span_conf=span_conf,
+                                           **grad)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     met = hdist.broadcast_object(iou_metrics(ious) if rank == 0 else None)
@@ -1908,6 +2082,8 @@ def run_round(model, dataset, data_old, data_gt, last_prop, task, I, epochs, bat
         m['calibration'] = calibration
     if diversity is not None:
         m['diversity'] = diversity
+    if grad_bank is not None:
+        m['grad_bank'] = grad_bank
     if log and rank == 0:
         log('round %d: update_label %.3f s | train %d steps %.3f s (%.0f clips/s) | infer_trainset %.3f s | pseudo-label '
             'R1@0.5 %.2f mIoU %.2f' % (I, m['update_s'], steps, m['train_s'], m['clips_per_s'], m['infer_s'], r5, mi))

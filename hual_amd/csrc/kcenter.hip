@@ -1,205 +1,71 @@
-// hual_kcenter_greedy (include/hual_seqpan.h): core-set selection - greedy k-center in a feature space, weighted by a per-row
-// score: step s picks the eligible row of maximal (w[i] * mind[i], w[i], -i), mind[i] the squared distance of row i to its nearest
-// center so far.  The whole selection is one C call: an opening launch, one update-only launch per init row, one launch per step and
-// one closing update, all on the caller's stream, no host synchronisation in between.
-//
-// A step is ONE launch over cdiv(N, 16) workgroups of four waves.  Every workgroup
-//   1. stages the newest center's row in LDS - its index is read from picked[s - 1] in device memory and range-checked: anything
-//      outside [0, N) (the -1 of an exhausted selection) makes the update a no-op;
-//   2. updates mind / assign of its 16 rows: one wave per row, the row's chunks of four floats dealt to the lanes (chunk c to lane
-//      c % 64, in ascending c), the lanes' sums folded by wave_sum64 - an order that depends on D alone, so bit-equal rows get
-//      bit-equal distances wherever they sit;
-//   3. reduces its rows' keys to one partial, publishes it (plain store, agent-scope release) and draws a ticket from a device-scope
-//      counter.  The workgroup that draws the last ticket (agent-scope acquire) reduces the partials, writes picked[s] and
-//      pick_dist[s], marks the row taken and returns the counter to zero.
-// No workgroup ever waits for another one: the ticket is a fetch-add whose value decides who reduces, nothing polls.  The keys are a
-// total order (the row index is unique), so the pick does not depend on which workgroup arrives last or in what order partials are
-// folded: a second launch returns equal bits.
-#include "common.h"
+// hual_kcenter_greedy and hual_kcenter_sample (include/hual_seqpan.h): the host side of the core-set selection - argument checks,
+// the workspace layout and the launch sequence.  The kernels are kcenter.h's; hual_kcenter_greedy instantiates <false, false>.
+#include "kcenter.h"
 #include "prof.h"
 
 namespace {
 
-constexpr int KC_THREADS = 256;      // four waves
-constexpr int KC_ROWS = 16;          // rows per workgroup: four per wave, their loads in flight together
-constexpr int KC_MAXD = 4096;
+inline uint64_t kc_round16(uint64_t b) { return (b + 15) & ~(uint64_t)15; }
 
-struct KcKey {                       // (score, w, -idx): idx < 0 is "no eligible row"
-  float score, w;
-  int idx;
-  float mind;                        // the row's mind, carried for pick_dist
-};
-
-__device__ __forceinline__ bool kc_better(const KcKey& a, const KcKey& b) {
-  if (a.idx < 0) return false;
-  if (b.idx < 0) return true;
-  if (a.score != b.score) return a.score > b.score;
-  if (a.w != b.w) return a.w > b.w;
-  return a.idx < b.idx;
-}
-
-struct KcArgs {
+struct KcCall {
   const float* x;
-  const float* weight;               // null: every weight 1
-  int N, D, ld, vec;                 // vec: rows are 16-byte aligned and D % 4 == 0 -> float4 loads
-  float* mind;
-  int32_t* assign;
-  int32_t* taken;                    // workspace: 0 free, 1 center (init or picked), 2 a row with a non-finite feature
-  uint32_t* counter;                 // workspace: [0] the ticket counter, [1] "a center exists"
-  float4* partial;                   // workspace: one key per workgroup
+  int N, D, ld;
+  const float* weight;
+  const int32_t* init;
+  int n_init, n_select;
   int32_t* picked;
   float* pick_dist;
+  float* mind;
+  int32_t* assign;
+  void* workspace;
+  uint64_t workspace_bytes;
+  void* stream;
 };
 
-// the four floats of chunk c of a row (columns 4c .. 4c + 3; beyond D: zeros, which add an exact +0 to the sum)
-__device__ __forceinline__ float4 kc_chunk(const float* row, int c, int D, int vec) {
-  if (vec) return ld4(row + 4 * c);
-  const int k = 4 * c;
-  return make_float4(row[k], k + 1 < D ? row[k + 1] : 0.f, k + 2 < D ? row[k + 2] : 0.f, k + 3 < D ? row[k + 3] : 0.f);
+// the launch sequence of one selection: opening, init updates, steps, closing update
+template <bool SAMPLE, bool ORIGIN>
+int kc_enqueue(const KcCall& c, const KcRng& rng) {
+  hipStream_t st = (hipStream_t)c.stream;
+  const int N = c.N, D = c.D;
+  KcArgs a{};
+  a.x = c.x; a.weight = c.weight; a.N = N; a.D = D; a.ld = c.ld;
+  a.vec = (D % 4 == 0 && c.ld % 4 == 0 && ((uintptr_t)c.x & 15) == 0) ? 1 : 0;
+  a.mind = c.mind; a.assign = c.assign; a.picked = c.picked; a.pick_dist = c.pick_dist;
+  char* ws = (char*)c.workspace;
+  a.counter = (uint32_t*)ws;
+  a.taken = (int32_t*)(ws + 16);
+  a.partial = (float4*)(ws + 16 + kc_round16(4ull * (uint64_t)N));
+  const int grid = hual::cdiv(N, KC_ROWS);
+  const double row_bytes = 4.0 * D * N;
+  HUAL_LAUNCH(0.0, row_bytes + 12.0 * N, kcenter_open_kernel<ORIGIN>, dim3(grid), dim3(KC_THREADS), 0, st, a);
+  for (int j = 0; j < c.n_init; ++j)                         // the init rows, in their order: update only, each marked taken
+    HUAL_LAUNCH(3.0 * D * N, row_bytes + 8.0 * N, (kcenter_step_kernel<SAMPLE, ORIGIN>), dim3(grid), dim3(KC_THREADS), 0, st, a, c.init + j, 1, 0,
+                0, rng);
+  for (int s = 0; s < c.n_select; ++s)
+    HUAL_LAUNCH(3.0 * D * N, row_bytes + 16.0 * N, (kcenter_step_kernel<SAMPLE, ORIGIN>), dim3(grid), dim3(KC_THREADS), 0, st, a,
+                s ? (const int32_t*)(c.picked + s - 1) : (const int32_t*)nullptr, 0, 1, s, rng);
+  // the closing update: mind and assign account for the last pick too
+  HUAL_LAUNCH(3.0 * D * N, row_bytes + 8.0 * N, (kcenter_step_kernel<SAMPLE, ORIGIN>), dim3(grid), dim3(KC_THREADS), 0, st, a,
+              (const int32_t*)(c.picked + c.n_select - 1), 0, 0, 0, rng);
+  HUAL_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
-// opening launch: mind = +inf, assign = -1, taken = 0 (2 for a row that holds a NaN or an infinity: d(i, i) is then NaN, and such a
-// row is never eligible), the counter and the center flag zero
-__global__ __launch_bounds__(KC_THREADS) void kcenter_open_kernel(KcArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nchunk = (a.D + 3) >> 2;
-  if (blockIdx.x == 0 && threadIdx.x < 2) a.counter[threadIdx.x] = 0u;
-  for (int r = 0; r < KC_ROWS / 4; ++r) {
-    const int row = blockIdx.x * KC_ROWS + wave * (KC_ROWS / 4) + r;
-    if (row >= a.N) break;                                   // (wave-uniform)
-    const float* p = a.x + (size_t)row * a.ld;
-    float acc = 0.f;
-    for (int c = lane; c < nchunk; c += 64) {
-      const float4 v = kc_chunk(p, c, a.D, a.vec);
-      acc += (v.x - v.x) + (v.y - v.y) + (v.z - v.z) + (v.w - v.w);      // 0, or NaN for a NaN or an infinity
-    }
-    acc = wave_sum64(acc);
-    if (lane == 0) {
-      a.mind[row] = __builtin_huge_valf();
-      a.assign[row] = -1;
-      a.taken[row] = acc == 0.f ? 0 : 2;
-    }
-  }
+// the argument rules the two entry points share -> 0, 1 (n_select == 0: nothing is owed) or an error
+int kc_check(const KcCall& c, const char* who) {      // (HUAL_REQUIRE puts a message together only where its rule fails)
+  HUAL_REQUIRE(c.N >= 1, std::string(who) + ": N >= 1");
+  HUAL_REQUIRE(c.D >= 1 && c.D <= KC_MAXD, std::string(who) + ": 1 <= D <= 4096");
+  HUAL_REQUIRE(c.ld >= c.D, std::string(who) + ": ld >= D");
+  HUAL_REQUIRE(c.n_select >= 0 && c.n_select <= c.N, std::string(who) + ": 0 <= n_select <= N");
+  HUAL_REQUIRE(c.n_init >= 0 && c.n_init <= c.N, std::string(who) + ": 0 <= n_init <= N");
+  HUAL_REQUIRE(c.n_init == 0 || c.init, std::string(who) + ": null pointer (init with n_init >= 1)");
+  if (c.n_select == 0) return 1;                             // nothing is owed: nothing is written
+  HUAL_REQUIRE(c.x && c.picked && c.pick_dist && c.mind && c.assign && c.workspace,
+               std::string(who) + ": null pointer (x, picked, pick_dist, mind, assign, workspace)");
+  HUAL_REQUIRE(c.workspace_bytes >= hual_kcenter_workspace_bytes(c.N), std::string(who) + ": workspace smaller than hual_kcenter_workspace_bytes(N)");
+  HUAL_REQUIRE(((uintptr_t)c.workspace & 15) == 0, std::string(who) + ": workspace must be 16-byte aligned");
+  return 0;
 }
-
-// update with the center whose index stands at *csrc (null: none), then - select - the pick of step s
-__global__ __launch_bounds__(KC_THREADS) void kcenter_step_kernel(KcArgs a, const int32_t* csrc, int mark, int select, int s) {
-  __shared__ __attribute__((aligned(16))) float smem[KC_MAXD + 4 * 4 + 4];
-  float* cen = smem;
-  float* wkey = smem + KC_MAXD;                              // four waves' keys, then the "I am last" word
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nchunk = (a.D + 3) >> 2;
-  int c_idx = csrc ? csrc[0] : -1;
-  if (c_idx < 0 || c_idx >= a.N) c_idx = -1;                 // range check: an index from memory never becomes an address unchecked
-  const bool has_center = c_idx >= 0 || a.counter[1] != 0u;  // (counter[1] is only ever set to 1, and only in launches where c_idx >= 0)
-  if (c_idx >= 0) {
-    const float* cp = a.x + (size_t)c_idx * a.ld;
-    for (int k = tid; k < 4 * nchunk; k += KC_THREADS) cen[k] = k < a.D ? cp[k] : 0.f;
-    if (blockIdx.x == 0 && tid == 0) {
-      a.counter[1] = 1u;
-      if (mark) a.taken[c_idx] = 1;
-    }
-    __syncthreads();
-  }
-  // ---- the wave's four rows: distances to the center, loads of the four rows in flight together
-  const int row0 = blockIdx.x * KC_ROWS + wave * 4;
-  float d[4] = {0.f, 0.f, 0.f, 0.f};
-  if (c_idx >= 0) {
-    const float* p[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[r] = a.x + (size_t)min(row0 + r, a.N - 1) * a.ld;      // rows beyond the end read the last row, and are dropped below
-    for (int c = lane; c < nchunk; c += 64) {
-      const float4 cv = *reinterpret_cast<const float4*>(cen + 4 * c);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float4 v = kc_chunk(p[r], c, a.D, a.vec);
-        const float dx = v.x - cv.x, dy = v.y - cv.y, dz = v.z - cv.z, dw = v.w - cv.w;
-        d[r] += dx * dx;
-        d[r] += dy * dy;
-        d[r] += dz * dz;
-        d[r] += dw * dw;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) d[r] = wave_sum64(d[r]);
-  }
-  KcKey best{0.f, 0.f, -1, 0.f};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = row0 + r;
-    if (row >= a.N) break;                                   // (wave-uniform)
-    float m = a.mind[row];
-    if (c_idx >= 0) {
-      const bool closer = d[r] < m;                          // a strictly smaller distance replaces: the first center that attains the minimum stays
-      if (closer || d[r] != d[r]) {                          // (a NaN distance makes mind NaN and keeps assign)
-        m = d[r];
-        if (lane == 0) {
-          a.mind[row] = m;
-          if (closer) a.assign[row] = c_idx;
-        }
-      }
-    }
-    if (select) {
-      const float w = a.weight ? a.weight[row] : 1.f;
-      const float score = has_center ? w * m : w;
-      const KcKey k{score, w, row, m};
-      if (a.taken[row] == 0 && w >= 0.f && score == score && kc_better(k, best)) best = k;
-    }
-  }
-  if (!select) return;
-  // ---- the workgroup's partial, the ticket, and in the workgroup that arrives last the pick
-  if (lane == 0) {
-    wkey[4 * wave] = best.score; wkey[4 * wave + 1] = best.w; wkey[4 * wave + 2] = __int_as_float(best.idx); wkey[4 * wave + 3] = best.mind;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int v = 1; v < 4; ++v) {
-      const KcKey k{wkey[4 * v], wkey[4 * v + 1], __float_as_int(wkey[4 * v + 2]), wkey[4 * v + 3]};
-      if (kc_better(k, best)) best = k;
-    }
-    a.partial[blockIdx.x] = make_float4(best.score, best.w, __int_as_float(best.idx), best.mind);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t ticket = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = ticket == gridDim.x - 1;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    wkey[16] = last ? 1.f : 0.f;
-  }
-  __syncthreads();
-  if (wkey[16] == 0.f) return;                               // (workgroup-uniform)
-  best = KcKey{0.f, 0.f, -1, 0.f};
-  for (int g = tid; g < (int)gridDim.x; g += KC_THREADS) {
-    const float4 v = a.partial[g];
-    const KcKey k{v.x, v.y, __float_as_int(v.z), v.w};
-    if (kc_better(k, best)) best = k;
-  }
-  for (int off = 32; off >= 1; off >>= 1) {
-    const KcKey k{__shfl_xor(best.score, off), __shfl_xor(best.w, off), __shfl_xor(best.idx, off), __shfl_xor(best.mind, off)};
-    if (kc_better(k, best)) best = k;
-  }
-  __syncthreads();                                           // (wkey[16] has been read by everyone)
-  if (lane == 0) {
-    wkey[4 * wave] = best.score; wkey[4 * wave + 1] = best.w; wkey[4 * wave + 2] = __int_as_float(best.idx); wkey[4 * wave + 3] = best.mind;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int v = 1; v < 4; ++v) {
-      const KcKey k{wkey[4 * v], wkey[4 * v + 1], __float_as_int(wkey[4 * v + 2]), wkey[4 * v + 3]};
-      if (kc_better(k, best)) best = k;
-    }
-    const bool found = best.idx >= 0 && best.idx < a.N;
-    a.picked[s] = found ? best.idx : -1;
-    a.pick_dist[s] = found ? best.mind : -1.f;
-    if (found) a.taken[best.idx] = 1;
-    __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-inline uint64_t kc_round16(uint64_t b) { return (b + 15) & ~(uint64_t)15; }
 
 }  // namespace
 
@@ -211,37 +77,19 @@ extern "C" uint64_t hual_kcenter_workspace_bytes(int N) {
 extern "C" int hual_kcenter_greedy(const float* x, int N, int D, int ld, const float* weight, const int32_t* init, int n_init, int n_select,
                                    int32_t* picked, float* pick_dist, float* mind, int32_t* assign, void* workspace, uint64_t workspace_bytes,
                                    void* stream) {
-  HUAL_REQUIRE(N >= 1, "hual_kcenter_greedy: N >= 1");
-  HUAL_REQUIRE(D >= 1 && D <= KC_MAXD, "hual_kcenter_greedy: 1 <= D <= 4096");
-  HUAL_REQUIRE(ld >= D, "hual_kcenter_greedy: ld >= D");
-  HUAL_REQUIRE(n_select >= 0 && n_select <= N, "hual_kcenter_greedy: 0 <= n_select <= N");
-  HUAL_REQUIRE(n_init >= 0 && n_init <= N, "hual_kcenter_greedy: 0 <= n_init <= N");
-  HUAL_REQUIRE(n_init == 0 || init, "hual_kcenter_greedy: null pointer (init with n_init >= 1)");
-  if (n_select == 0) return 0;                               // nothing is owed: nothing is written
-  HUAL_REQUIRE(x && picked && pick_dist && mind && assign && workspace,
-               "hual_kcenter_greedy: null pointer (x, picked, pick_dist, mind, assign, workspace)");
-  HUAL_REQUIRE(workspace_bytes >= hual_kcenter_workspace_bytes(N), "hual_kcenter_greedy: workspace smaller than hual_kcenter_workspace_bytes(N)");
-  HUAL_REQUIRE(((uintptr_t)workspace & 15) == 0, "hual_kcenter_greedy: workspace must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  KcArgs a{};
-  a.x = x; a.weight = weight; a.N = N; a.D = D; a.ld = ld;
-  a.vec = (D % 4 == 0 && ld % 4 == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
-  a.mind = mind; a.assign = assign; a.picked = picked; a.pick_dist = pick_dist;
-  char* ws = (char*)workspace;
-  a.counter = (uint32_t*)ws;
-  a.taken = (int32_t*)(ws + 16);
-  a.partial = (float4*)(ws + 16 + kc_round16(4ull * (uint64_t)N));
-  const int grid = hual::cdiv(N, KC_ROWS);
-  const double row_bytes = 4.0 * D * N;
-  HUAL_LAUNCH(0.0, row_bytes + 12.0 * N, kcenter_open_kernel, dim3(grid), dim3(KC_THREADS), 0, st, a);
-  for (int j = 0; j < n_init; ++j)                           // the init rows, in their order: update only, each marked taken
-    HUAL_LAUNCH(3.0 * D * N, row_bytes + 8.0 * N, kcenter_step_kernel, dim3(grid), dim3(KC_THREADS), 0, st, a, init + j, 1, 0, 0);
-  for (int s = 0; s < n_select; ++s)
-    HUAL_LAUNCH(3.0 * D * N, row_bytes + 16.0 * N, kcenter_step_kernel, dim3(grid), dim3(KC_THREADS), 0, st, a,
-                s ? (const int32_t*)(picked + s - 1) : (const int32_t*)nullptr, 0, 1, s);
-  // the closing update: mind and assign account for the last pick too
-  HUAL_LAUNCH(3.0 * D * N, row_bytes + 8.0 * N, kcenter_step_kernel, dim3(grid), dim3(KC_THREADS), 0, st, a,
-              (const int32_t*)(picked + n_select - 1), 0, 0, 0);
-  HUAL_CHECK_HIP(hipGetLastError());
-  return 0;
+  const KcCall c{x, N, D, ld, weight, init, n_init, n_select, picked, pick_dist, mind, assign, workspace, workspace_bytes, stream};
+  const int rc = kc_check(c, "hual_kcenter_greedy");
+  if (rc) return rc < 0 ? rc : 0;
+  return kc_enqueue<false, false>(c, KcRng{0u, 0u, 0u});
+}
+
+extern "C" int hual_kcenter_sample(const float* x, int N, int D, int ld, const float* weight, const int32_t* init, int n_init, int n_select,
+                                   uint64_t seed, uint32_t offset, int sample, int origin, int32_t* picked, float* pick_dist, float* mind,
+                                   int32_t* assign, void* workspace, uint64_t workspace_bytes, void* stream) {
+  const KcCall c{x, N, D, ld, weight, init, n_init, n_select, picked, pick_dist, mind, assign, workspace, workspace_bytes, stream};
+  const int rc = kc_check(c, "hual_kcenter_sample");
+  if (rc) return rc < 0 ? rc : 0;
+  const KcRng rng{(uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), offset};
+  if (sample) return origin ? kc_enqueue<true, true>(c, rng) : kc_enqueue<true, false>(c, rng);
+  return origin ? kc_enqueue<false, true>(c, rng) : kc_enqueue<false, false>(c, rng);
 }

@@ -27,8 +27,10 @@ __device__ __forceinline__ bool span_mass_live(double Z) { return Z > 0.0 && Z <
 // hual_al_evidence_grid (spancalib.hip) - one body, so the same logits give the same bits.  smf [2 * SPAN_WAVES] floats and smd
 // [2 * SPAN_WAVES] doubles of LDS scratch, FRESH: a caller that has read them, or ps / pe, puts a barrier in front.  Called by all
 // SPAN_THREADS threads; ends on a barrier, after which ps / pe are readable.
+// NW: the waves of the calling workgroup - SPAN_WAVES, or 4 in a 256-thread workgroup (gradembed.hip): waves 4.. of the wide form
+// hold no frame and add -inf to the max and exact zeros to the sum, in the same ascending fold, so both widths give the same bits.
 // heads_kernel's span stage (mask_logits, reproducible softmax; oracle/seqpan_ref.py::softmax_cr)
-template <class Start, class End>
+template <int NW = SPAN_WAVES, class Start, class End>
 __device__ __forceinline__ void span_probabilities_of(Start start, End end, int T, int v, float* ps, float* pe, float* smf, double* smd) {
   const int t = threadIdx.x;
   const bool in = t < T;
@@ -39,11 +41,11 @@ __device__ __forceinline__ void span_probabilities_of(Start start, End end, int 
   }
   // (smf / smd are fresh: no barrier in front.  Waves 4.. contribute -inf and exact zeros, as waves 4 - 7 of heads_kernel do)
   float mxs = zs, mxe = ze;
-  block_reduce<BlockMaxF, SPAN_WAVES, false>(mxs, mxe, smf);
+  block_reduce<BlockMaxF, NW, false>(mxs, mxe, smf);
   const float xs = in ? (float)exp((double)(zs - mxs)) : 0.f;
   const float xe = in ? (float)exp((double)(ze - mxe)) : 0.f;
   double dss = (double)xs, dse = (double)xe;
-  block_reduce<BlockSumD, SPAN_WAVES, false>(dss, dse, smd);
+  block_reduce<BlockSumD, NW, false>(dss, dse, smd);
   if (t < 256) {
     ps[t] = __fdiv_rn(xs, (float)dss);
     pe[t] = __fdiv_rn(xe, (float)dse);

@@ -191,6 +191,8 @@ def load():
     lib.hual_kcenter_workspace_bytes.restype = ctypes.c_uint64
     lib.hual_kcenter_workspace_bytes.argtypes = [i32]
     lib.hual_kcenter_greedy.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp]
+    lib.hual_kcenter_sample.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, u64, ctypes.c_uint32, i32, i32, vp, vp, vp, vp, vp, u64, vp]
+    lib.hual_al_grad_embed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -968,9 +970,28 @@ def kcenter_select(x, n_select, weight=None, init=None, out=None, workspace=None
     hold +inf in mind and -1 in assign).  workspace: a device uint8 tensor of at least kcenter_workspace_bytes(N) bytes to reuse.
     validate=False: a device int32 init is taken as it is, without the read-back - for a graph capture, where nothing can be read back
     (the kernel range-checks every index itself: a row outside [0, N) is skipped there)."""
+    return _kcenter('kcenter_select', None, x, n_select, weight, init, out, workspace, validate)
+
+
+def kcenter_sample(x, n_select, weight=None, init=None, seed=0, offset=0, sample=True, origin=True, out=None, workspace=None,
+                   validate=True):
+    """kcenter_select with two switches (hual_kcenter_sample: the same launches, outputs, workspace and eligibility rules).  origin: the
+    zero vector is a center before the first pick - mind opens as |x_i|^2 and assign -1 means "the origin".  sample: D^2 sampling -
+    step s draws the row with probability proportional to weight * mind (the argmax of (weight * mind) / E over unit exponentials E,
+    Philox4x32-7 at (step, row, HUAL_SITE_SELECT, offset) under `seed`), so a second call with the same seed and offset returns equal
+    bits; a row with weight * mind == 0 is taken only when nothing else is left.  seed: an int in [0, 2^64); offset: an int in
+    [0, 2^32) - ValueError otherwise.  sample=False, origin=False is kcenter_select, bit for bit."""
+    who = 'kcenter_sample'
+    for name, val, bits in (('seed', seed, 64), ('offset', offset, 32)):
+        if isinstance(val, bool) or not isinstance(val, int) or not 0 <= val < (1 << bits):
+            raise ValueError('%s: %s must be an integer in [0, 2^%d)' % (who, name, bits))
+    return _kcenter(who, (int(seed), int(offset), int(bool(sample)), int(bool(origin))), x, n_select, weight, init, out, workspace, validate)
+
+
+def _kcenter(who, sampler, x, n_select, weight, init, out, workspace, validate):
+    """the argument checks and the call kcenter_select and kcenter_sample share; sampler: None, or (seed, offset, sample, origin)"""
     import numpy as np
     import torch
-    who = 'kcenter_select'
     if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and x.stride(1) == 1
             and x.stride(0) >= x.shape[1]):
         raise HualError(who + ': x must be a float32 [N, D] tensor with contiguous rows, N >= 1')
@@ -1020,6 +1041,68 @@ def kcenter_select(x, n_select, weight=None, init=None, out=None, workspace=None
     elif not (torch.is_tensor(workspace) and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= need
               and workspace.device == dev and workspace.data_ptr() % 16 == 0):
         raise HualError(who + ': workspace must be a contiguous 16-byte aligned uint8 tensor of at least %d bytes on x\'s device' % need)
-    check(load().hual_kcenter_greedy(ptr(x), N, D, int(x.stride(0)), ptr(weight), ptr(init_d), n_init, n_select, ptr(out[0]), ptr(out[1]),
-                                     ptr(out[2]), ptr(out[3]), ptr(workspace), int(workspace.numel()), stream_ptr()))
+    head = (ptr(x), N, D, int(x.stride(0)), ptr(weight), ptr(init_d), n_init, n_select)
+    tail = (ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(workspace), int(workspace.numel()), stream_ptr())
+    if sampler is None:
+        check(load().hual_kcenter_greedy(*head, *tail))
+    else:
+        check(load().hual_kcenter_sample(*head, *sampler, *tail))
     return out      # (a workspace allocated here goes back to the caching allocator in stream order: behind the launches)
+
+
+# ---------------------------------------------------------------- gradient embeddings
+GRAD_EMBED_DIM = 256        # columns hual_al_grad_embed writes per row: g_s (0..127), g_e (128..255)
+GRAD_EMBED_MAX_T = 256
+
+
+def al_grad_embed(hs, he, s_logits, e_logits, v_len, hyp, desc, gnorm2, egl, rows=None):
+    """the gradient embeddings of the samples of one batch (hual_al_grad_embed), one launch enqueued on the current stream, after a
+    label-free forward.  hs / he: device f32 [B * T, 128], contiguous - the forward's head.hs / head.he; s_logits / e_logits: device f32
+    [B, ld] with contiguous rows of one stride ld, T <= ld <= 1024, 1 <= T <= 256; v_len: device i32 [B]; hyp: device i32 [B, 2], the
+    hypothesised (start, end) frame - an entry outside [0, v) means "no label for this head" (g = the expected feature); rows: device
+    i32 [B] or None - the bank row of sample b (None: b), an id outside [0, N) writes nothing.
+    Banks, written in place at the rows of the batch's samples: desc f32 [N, >= 256] with contiguous rows (columns 0..127 g_s, 128..255
+    g_e), gnorm2 f32 [N] = |g_s|^2 + |g_e|^2, egl f32 [N] = the expected squared gradient length under y ~ p.  A sample without frames
+    or with a non-finite logit among its frames gets a NaN descriptor and -1 in gnorm2 / egl.  -> (desc, gnorm2, egl)."""
+    import torch
+    who = 'al_grad_embed'
+    if not (torch.is_tensor(hs) and torch.is_tensor(he) and hs.dtype == he.dtype == torch.float32 and hs.dim() == he.dim() == 2
+            and hs.shape == he.shape and hs.shape[1] == 128 and hs.shape[0] >= 1 and hs.is_contiguous() and he.is_contiguous()
+            and hs.device == he.device):
+        raise HualError(who + ': hs / he must be contiguous float32 [B * T, 128] tensors on one device')
+    dev = hs.device
+    if not (torch.is_tensor(v_len) and v_len.dtype == torch.int32 and v_len.dim() == 1 and v_len.numel() >= 1 and v_len.is_contiguous()
+            and v_len.device == dev):
+        raise HualError(who + ': v_len must be a contiguous int32 [B] tensor on the device of hs')
+    B = int(v_len.numel())
+    if hs.shape[0] % B:
+        raise HualError(who + ': hs / he hold %d rows, not a multiple of B = %d' % (hs.shape[0], B))
+    T = int(hs.shape[0]) // B
+    if not 1 <= T <= GRAD_EMBED_MAX_T:
+        raise HualError(who + ': T must lie in [1, %d]' % GRAD_EMBED_MAX_T)
+    for name, z in (('s_logits', s_logits), ('e_logits', e_logits)):
+        if not (torch.is_tensor(z) and z.dtype == torch.float32 and z.dim() == 2 and z.shape[0] == B and z.stride(1) == 1
+                and z.stride(0) >= z.shape[1] and z.device == dev):
+            raise HualError('%s: %s must be a float32 [B, ld] tensor with contiguous rows on the device of hs' % (who, name))
+    ld = int(s_logits.stride(0)) if B > 1 else int(s_logits.shape[1])
+    if B > 1 and int(e_logits.stride(0)) != ld or s_logits.shape[1] != e_logits.shape[1] or s_logits.shape[1] < T:
+        raise HualError(who + ': s_logits / e_logits must share one shape [B, >= T] and one row stride')
+    if not T <= ld <= 1024:
+        raise HualError(who + ': the logits\' row stride must lie in [T, 1024]')
+    if not (torch.is_tensor(hyp) and hyp.dtype == torch.int32 and tuple(hyp.shape) == (B, 2) and hyp.is_contiguous() and hyp.device == dev):
+        raise HualError(who + ': hyp must be a contiguous int32 [B, 2] tensor on the device of hs')
+    if rows is not None and not (torch.is_tensor(rows) and rows.dtype == torch.int32 and tuple(rows.shape) == (B,) and rows.is_contiguous()
+                                 and rows.device == dev):
+        raise HualError(who + ': rows must be a contiguous int32 [B] tensor on the device of hs')
+    if not (torch.is_tensor(desc) and desc.dtype == torch.float32 and desc.dim() == 2 and desc.shape[0] >= 1
+            and desc.shape[1] >= GRAD_EMBED_DIM and desc.stride(1) == 1 and desc.stride(0) >= desc.shape[1] and desc.device == dev):
+        raise HualError(who + ': desc must be a float32 [N, >= %d] tensor with contiguous rows on the device of hs' % GRAD_EMBED_DIM)
+    N = int(desc.shape[0])
+    if rows is None and B > N:
+        raise HualError(who + ': without rows the bank needs at least B = %d rows' % B)
+    for name, o in (('gnorm2', gnorm2), ('egl', egl)):
+        if not (torch.is_tensor(o) and o.dtype == torch.float32 and tuple(o.shape) == (N,) and o.is_contiguous() and o.device == dev):
+            raise HualError('%s: %s must be a contiguous float32 [N] tensor on the device of hs' % (who, name))
+    check(load().hual_al_grad_embed(ptr(hs), ptr(he), ptr(s_logits), ptr(e_logits), ptr(v_len), ptr(hyp), ptr(rows), B, T, ld, N, ptr(desc),
+                                    int(desc.stride(0)), ptr(gnorm2), ptr(egl), stream_ptr()))
+    return desc, gnorm2, egl

@@ -375,12 +375,14 @@ class Runner:
 
     # ------------------------------------------------------------------ main.py --mode infer_trainset (:99-111)
     def infer_trainset(self, path=None, mc_dropout=None, load_best=True, weights=None, mc_samples=None, mc_stat='range', bank=None,
-                       span_conf=False):
+                       span_conf=False, grad_bank=None, grad_hyp='prediction'):
         """results/<task>/<suffix>.pkl of runner_utils.py:103-104.  mc_dropout=None: as the reference runs.
         weights: 'ema' (the default with train.ema_decay) or 'raw'.  mc_samples=K (with mc_dropout): K stochastic passes folded into
         `bank` (al.McBank; default: one of this call only) - the records then hold 'prop_uncert' instead of prop_logits1/2: the statistic
         mc_stat = 'range' or 'std', or 'bald', 'entropy' or 'expected_entropy' (a given bank was then built with info=True).
-        span_conf=True: the records also hold 'prop_conf' and 'prop_span_entropy' (al.infer_trainset)."""
+        span_conf=True: the records also hold 'prop_conf' and 'prop_span_entropy' (al.infer_trainset).
+        grad_bank: an al.GradBank over the training set - the pass fills it with the gradient embeddings of the span heads under the
+        hypothesis grad_hyp, and the records also hold 'prop_egl' and 'prop_gnorm2' (al.infer_trainset; single process only)."""
         if load_best:
             hdist.barrier()
             self.load(os.path.join(self.ckpt_dir, 'best_SeqPAN.npz'))
@@ -388,7 +390,8 @@ class Runner:
             self.train_set = DeviceDataset(*self._host_train, device=self.model.device)
         with self._weights(weights):
             records, ious = al.infer_trainset_sharded(self.model, self.train_set, self.batch_size, mc_dropout=mc_dropout, min_chars=4,
-                                                      mc_samples=mc_samples, bank=bank, mc_stat=mc_stat, span_conf=span_conf)
+                                                      mc_samples=mc_samples, bank=bank, mc_stat=mc_stat, span_conf=span_conf,
+                                                      **({} if grad_bank is None else dict(grad_bank=grad_bank, grad_hyp=grad_hyp)))
         if self.rank != 0:
             return None, hdist.broadcast_object(None)
         if path:

@@ -49,6 +49,8 @@ extern "C" {
 #define HUAL_SITE_TRI 24
 #define HUAL_SITE_GUMBEL 28   /* gumbel noise of the matching head (layers.py:163-166): RNG row = b*T+t, one call = the 4 classes */
 #define HUAL_SITE_FE 32
+#define HUAL_SITE_SELECT 256  /* not a dropout site: the exponentials of hual_kcenter_sample, c0 = step, c1 = row, word x.  Above every
+                                 dropout site (the largest is HUAL_SITE_FE + 16 * pass + 8) */
 
 /* keys of configs/<task>/SeqPAN.yaml read by models/model.py (model.py:17,36-43,61,83,101,122) */
 typedef struct hual_cfg {
@@ -1151,6 +1153,53 @@ uint64_t hual_kcenter_workspace_bytes(int N);
 int hual_kcenter_greedy(const float* x, int N, int D, int ld, const float* weight, const int32_t* init, int n_init, int n_select,
                         int32_t* picked, float* pick_dist, float* mind, int32_t* assign, void* workspace, uint64_t workspace_bytes,
                         void* stream);
+
+/* hual_kcenter_sample: hual_kcenter_greedy's selection with two switches (HUAL_ABI_VERSION unchanged: one new symbol).  The same
+ * arguments, outputs, workspace, launch count, eligibility rules and kernels (csrc/kcenter.h, templated on the switches; with
+ * sample == 0 and origin == 0 the call returns hual_kcenter_greedy's bits).
+ *  - origin != 0: the zero vector is a center before the first pick.  The opening launch writes mind[i] = |x_i|^2 in the distance
+ *    routine's own order, so it equals d(i, 0) bit for bit; assign[i] = -1 means "the origin"; a center exists from step 0 on, so
+ *    the first score is w[i] * |x_i|^2.  Over gradient embeddings the greedy first pick is then the row of largest gradient.
+ *  - sample != 0: D^2 sampling (k-means++ seeding; BADGE, Ash et al. 2020).  The score of row i at step s is (w[i] * mind[i]) / E(i, s),
+ *    w[i] / E(i, s) while there is no center: one float32 product, one correctly rounded float32 division.  E(i, s) =
+ *    float32(-ln((k + 0.5) * 2^-24)), the logarithm evaluated in float64, k the top 24 bits of word x of Philox4x32-7 at counter
+ *    (c0 = s, c1 = i, c2 = HUAL_SITE_SELECT, c3 = offset) under the key (seed low word, seed high word).  The E are independent unit
+ *    exponentials (on a 2^24 grid), and the argmax of m_i / E_i is a draw with probability m_i / sum m: the pick is a draw
+ *    proportional to w * mind.  The key stays the total order (score, w, -i): a row with w * mind == 0 - a duplicate of a center -
+ *    scores an exact zero, has probability 0 and is taken only when nothing else is left, in (w, -i) order.  pick_dist is the
+ *    row's mind, as in the greedy call.  The draws depend on (seed, offset, s, i) alone: arrival order and the ticket change nothing,
+ *    and a second call or a graph replay with the same seed returns equal bits. */
+int hual_kcenter_sample(const float* x, int N, int D, int ld, const float* weight, const int32_t* init, int n_init, int n_select,
+                        uint64_t seed, uint32_t offset, int sample, int origin, int32_t* picked, float* pick_dist, float* mind,
+                        int32_t* assign, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gradient embeddings for batch-mode acquisition (HUAL_ABI_VERSION unchanged: one new symbol).  The descriptor space of
+ * hual_clip_mean_features never saw the model; BADGE (Ash et al., ICLR 2020) describes a sample by the gradient of its loss with
+ * respect to the last layer under the model's own hypothesised label.  For SeqPAN that layer is start_dense / end_dense, Dense(1) on
+ * the hidden rows head.hs / head.he, under a softmax cross entropy: g_s = sum_t (p_s(t) - y_s(t)) h_s(t) in R^128, likewise g_e.
+ *
+ * hual_al_grad_embed: one launch, one 256-thread workgroup per sample of a batch, after a label-free forward.
+ * Inputs: hs, he f32 [B * T, 128] (the forward's head.hs / head.he, row b * T + t); s_logits, e_logits f32 [B, ld]; v_len i32 [B];
+ * hyp i32 [B, 2], the hypothesised (start, end) frame; rows i32 [B] or NULL, the bank row of sample b (NULL: b; an id outside [0, N)
+ * writes nothing; two samples of one launch must not name one row); 1 <= T <= 256 (the forward's own limit), T <= ld <= 1024.
+ * Outputs, banks over the whole set: desc f32 [N, ld_desc >= 256], columns 0..127 g_s and 128..255 g_e (columns beyond 255 are not
+ * written); gnorm2 f32 [N] = |g_s|^2 + |g_e|^2; egl f32 [N] = sum over the two heads of sum_t p(t) |h(t) - mu|^2, mu = sum_t p(t)
+ * h(t): the expectation of |g|^2 over y ~ p (the expected gradient length).
+ *  - v = v_len[b] clamped to [0, T]; p_s, p_e are the span family's masked softmax over the first v frames (hual_span_argmax's
+ *    numbers, bit for bit); y is one-hot at hyp.  A hyp entry outside [0, v) means "no label for this head": g = mu, the expected
+ *    feature, so a caller that wants egl alone needs no hypothesis.
+ *  - mu and g are accumulated in float32 in ascending t, one fused multiply-add per frame (the weight of the hypothesised frame is
+ *    float32(p - 1)).  egl is a second pass over float32(h - mu), squared, weighted and added in float64 in ascending t - never
+ *    E|h|^2 - |mu|^2.  The 256 columns' squares (gnorm2) and sums (egl) are added in float64 in a fixed order.
+ *  - A row with v < 1 or a non-finite logit among its v frames gets NaN in its 256 descriptor columns - hual_kcenter_* never picks
+ *    such a row and lets it move no other row - and -1.0f in gnorm2 and egl.
+ * No atomics, nothing grid wide: a second launch returns equal bits.  Allocates nothing and does not synchronise: capturable.
+ * Argument errors (a null pointer other than rows; B < 1; N < 1; T outside [1, 256]; ld outside [T, 1024]; ld_desc < 256) return
+ * HUAL_ERR_INVALID before any HIP call. */
+int hual_al_grad_embed(const float* hs, const float* he, const float* s_logits, const float* e_logits, const int32_t* v_len,
+                       const int32_t* hyp, const int32_t* rows, int B, int T, int ld, int N, float* desc, int ld_desc, float* gnorm2,
+                       float* egl, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hook for bench.py's roofline leg (not part of the reference's surface): between begin and end every
